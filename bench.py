@@ -1,6 +1,6 @@
 """bench.py -- images/sec of one MUNIT training step (dis_update + gen_update) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--batch 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 256] [--batch 8] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one synthetic batch: MUNIT_Trainer.update_learning_rate,
@@ -10,13 +10,18 @@ configs[1]: config_256.yaml geometry (AdaINGen_double + MsImageDis, gen_state 1,
 recon_mask 1, aux losses 0), 256x256, batch 8, fp32.  N > 1 is weak scaling: every rank runs the same
 per-GPU batch on its own shard of the global batch (data seed 7 + rank, identical model seed).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+A plain run sets up, warms up, times exactly --steps steps and prints ONE JSON line from rank 0 (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, `timing`, ...).  --full adds what takes runs of its own:
   roofline     -- the dominant kernel, chosen by measured time: every convolution pass (forward, backward-data,
                   backward-weight) is bracketed by HIP events in extra instrumented steps of this same run; `frac` =
                   executed FLOPs / duration / fp32 MFMA peak (<= 1), `algorithmic_frac` next to it, a top-3 table, and the
                   step-level fractions on executed and on algorithmic FLOPs
+  other_modes  -- reuse_dis_forward and BASELINE.json's two other single-GPU configurations, each on a fresh trainer
   cpu_baseline -- the CPU oracle (oracle/munit_oracle.py, a torch-CPU restatement of the
                   reference step: kind "port") timed on this host's cores on a bounded sample
+
+--dump-outputs DIR writes what the last timed step handed its caller (dump_outputs) as DIR/<name>.npy; the inputs,
+weights and sample are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -58,6 +63,37 @@ def make_batch(batch, size, rank=0):
     m_a = (torch.rand(batch, 1, size, size, generator=g) > 0.5).float()
     m_b = (torch.rand(batch, 1, size, size, generator=g) > 0.5).float()
     return x_a, x_b, m_a, m_b
+
+
+DUMP_LOSSES = ("loss_dis_a", "loss_dis_b", "loss_dis_total", "loss_gen_adv_a", "loss_gen_adv_b", "loss_gen_recon_x_a",
+               "loss_gen_recon_x_b", "loss_gen_recon_s_a", "loss_gen_recon_s_b", "loss_gen_recon_c_a", "loss_gen_recon_c_b",
+               "loss_gen_cycrecon_x_a", "loss_gen_cycrecon_x_b", "loss_gen_total")
+DUMP_WEIGHT_VALUES = 15 << 20    # float32 values of weights over all networks (60 MiB; the losses add a few bytes)
+
+
+def dump_outputs(trainer, out_dir):
+    """--dump-outputs: what the last dis_update + gen_update handed its caller -- the losses and the weights after the two
+    optimizer steps -- as out_dir/<name>.npy (float32).  A network's weights are its state_dict flattened in key order
+    (logical layout, not the optimizer's flat buffer); when all networks together exceed DUMP_WEIGHT_VALUES, each network
+    writes a fixed sample of its share instead (<net>_weights_sample.npy: the values at a seeded random choice of indices,
+    in index order)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name in DUMP_LOSSES:
+        v = getattr(trainer, name)
+        v = v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.float32(v)
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float32).reshape(()))
+    nets = ([("gen", trainer.gen)] if trainer.gen_state == 1 else [("gen_a", trainer.gen_a), ("gen_b", trainer.gen_b)]) + \
+        [("dis_a", trainer.dis_a), ("dis_b", trainer.dis_b)]
+    flat = [(n, torch.cat([t.detach().float().reshape(-1) for t in m.state_dict().values()])) for n, m in nets]
+    share = DUMP_WEIGHT_VALUES // len(flat)
+    sample = sum(v.numel() for _, v in flat) > DUMP_WEIGHT_VALUES
+    for name, v in flat:
+        if sample and v.numel() > share:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            np.save(os.path.join(out_dir, name + "_weights_sample.npy"), v[idx.to(v.device)].cpu().numpy())
+        else:
+            np.save(os.path.join(out_dir, name + "_weights.npy"), v.cpu().numpy())
 
 
 PMC_SUMMARY = "profiles/r04_pmc_hbm_mfma.txt"
@@ -298,6 +334,11 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--batch", type=int, default=8, help="per-GPU batch (pairs per update)")
     ap.add_argument("--gen-state", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline, other_modes, cpu_baseline (each can be left out "
+                         "with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write the losses and weights of the last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--dry-run", action="store_true", help="launcher check only: gloo rendezvous on the CPU, no GPU work")
@@ -307,6 +348,8 @@ def main():
                          "bf16s = configs[2] (use with --batch 32): bf16 storage of the trunk activations + bf16 MFMA, "
                          "fp32 accumulate / statistics / weights; bf16 = bf16 MFMA operands only, fp32 storage")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -371,6 +414,8 @@ def main():
         elapsed = float(t)
     loss_total = float(trainer.loss_gen_total)
     assert loss_total == loss_total, "loss is NaN"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, args.dump_outputs)     # before anything of --full steps the trainer again
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = args.batch * world * args.steps / elapsed
@@ -394,7 +439,7 @@ def main():
                    "ms_per_step_min": round(per_step_ms[0], 3), "ms_per_step_max": round(per_step_ms[-1], 3)},
     }
 
-    if not args.no_roofline and args.precision == "f32":
+    if args.full and not args.no_roofline and args.precision == "f32":
         # Every rank runs these extra steps (they contain the gradient all-reduces, so the collectives must stay
         # matched across ranks); rank 0 reports.
         step_flop = GFLOP_PER_PAIR_256 * 1e9 * (args.size / 256.0) ** 2 * args.batch
@@ -483,7 +528,7 @@ def main():
                 "step_counted_algorithmic_tflop": round(flops["alg"] / 1e12, 3),
                 "conv_ms_per_step_single_stream": round(sum(g_["ms"] for g_ in groups.values()) / n_prof, 2),
             }
-    if rank == 0 and args.precision in ("bf16", "bf16s") and not args.no_roofline:
+    if args.full and rank == 0 and args.precision in ("bf16", "bf16s") and not args.no_roofline:
         # build extension (no reference counterpart): step-level fraction against the dense bf16 MFMA peak and, for
         # comparison with the headline, against the fp32 MFMA peak ("report vs both")
         step_flop = GFLOP_PER_PAIR_256 * 1e9 * (args.size / 256.0) ** 2 * args.batch
@@ -493,7 +538,7 @@ def main():
                            "kernel": "whole step (algorithmic conv+linear FLOPs / step time)",
                            "step_frac_vs_f32_mfma_peak": round(step_flop / sec / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
                            "step_algorithmic_tflop": round(step_flop / 1e12, 3)}
-    if rank == 0 and world == 1 and args.precision == "f32" and not args.no_modes:
+    if args.full and rank == 0 and world == 1 and args.precision == "f32" and not args.no_modes:
         del trainer
         torch.cuda.empty_cache()
         out["other_modes"] = {}
@@ -532,7 +577,7 @@ def main():
                 out["other_modes"][name] = time_configuration(dev, size_m, batch_m, prec_m, peak)
                 torch.cuda.empty_cache()
             ops.set_compute("f32")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.size)
     if rank == 0:
         print(json.dumps(out), flush=True)
