@@ -1942,6 +1942,13 @@ extern "C" int munit_linear_fwd(const float* x, const float* w, const float* bia
 extern "C" int munit_linear_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* db, int B,
                                 int K, int N, float beta, void* ws, size_t ws_bytes, munit_stream_t stream) {
   const munit_conv_desc d = linear_desc(B, K, N, MUNIT_ACT_NONE, 0.f, MUNIT_COMPUTE_F32);
+  // both passes share ws: refuse a workspace too small for either before the first launch, not after dx is written
+  const size_t need = std::max(dx != nullptr ? munit_conv2d_dgrad_workspace_bytes(&d) : 0,
+                               dw != nullptr ? munit_conv2d_wgrad_workspace_bytes(&d) : 0);
+  if (ws_bytes < need) {
+    munit_set_error("linear_bwd: workspace %zu < %zu", ws_bytes, need);
+    return MUNIT_ERR_WORKSPACE;
+  }
   if (dx != nullptr) {
     const int rc = munit_conv2d_dgrad(&d, dy, w, nullptr, dx, ws, ws_bytes, stream);
     if (rc) return rc;

@@ -70,7 +70,37 @@ CONV_CASES = [
     # sub-pixel layers at the extents of the 64x64 step tests: several 8x8-tile blocks per axis in the backward-data
     (256, 128, 5, 1, 2, "reflect", 1, "none", 2, 16, 16),
     (128, 64, 5, 1, 2, "reflect", 1, "none", 1, 32, 32),
+    # F(3x3, 2x2) forms that production reaches at the default thresholds and no case above does (tests/test_cpu_dispatch.py
+    # lists them; CONV_CASES_TARGETS pins them): the reflect backward-weight FAST loader (config_256.yaml at a 96x96 crop,
+    # batch 2), the same loader on one 8-tile chunk (through test_conv_stride2_winograd_on_small_shapes), and the zero-padded
+    # forward, backward-data and backward-weight at a real grid size (the discriminator of a zero-padded config_256 at a
+    # 384x384 crop, batch 3: fake + real = 6 samples; twin batch, see TWIN_CASES)
+    (64, 128, 4, 2, 1, "reflect", 0, "none", 2, 96, 96),
+    (64, 128, 4, 2, 1, "reflect", 0, "none", 2, 12, 12),
+    (64, 128, 4, 2, 1, "zero", 0, "none", 6, 192, 192),
 ]
+
+# cases whose second half of the batch repeats the first: the kernels run the full batch, the fp64 reference half of it
+# (tests/test_gpu_shapes.py, TWIN_BATCH)
+TWIN_CASES = {(64, 128, 4, 2, 1, "zero", 0, "none", 6, 192, 192)}
+
+
+# the linears of the op tests as (B, K, N, act): test_linear and test_linear_entry_points (the MLP's 4096-wide output)
+LINEAR_CASES = [(5, 16, 256, "relu"), (5, 256, 4096, "relu")]
+
+# CONV_CASES entries added to reach a kernel form no other op test runs, with the kernel each pass must take (None: any);
+# tests/test_cpu_dispatch.py asserts these names on the CPU
+_S2W = " + wino_wgrad_reduce_kernel"
+CONV_CASES_TARGETS = {
+    (64, 128, 4, 2, 1, "reflect", 0, "none", 2, 96, 96): (None, None, "conv_wino_wgrad_kernel<true, true, false>" + _S2W),
+    (64, 128, 4, 2, 1, "zero", 0, "none", 6, 192, 192): ("conv_wino_kernel<1, 1>", "conv_wino_kernel<1, 2>",
+                                                         "conv_wino_wgrad_kernel<true, false, false>" + _S2W),
+}
+# the same under MUNIT_WINO_S2_MIN_BLOCKS=1 (test_conv_stride2_winograd_on_small_shapes)
+CONV_CASES_TARGETS_S2_MIN1 = {
+    (64, 128, 4, 2, 1, "reflect", 0, "none", 2, 12, 12): ("conv_wino_kernel<0, 1>", None,
+                                                         "conv_wino_wgrad_kernel<true, true, false>" + _S2W),
+}
 
 
 def ref_conv(x, w, b, stride, pad, pad_type, ups, act):
@@ -83,13 +113,19 @@ def ref_conv(x, w, b, stride, pad, pad_type, ups, act):
 def test_conv_fwd_bwd(case):
     from munit_amd import ops
     cin, cout, k, stride, pad, pt, ups, act, B, H, W = case
-    x = rnd((B, cin, H, W), 1)
+    twin = case in TWIN_CASES
+    nref = B // 2 if twin else B
+    x = rnd((nref, cin, H, W), 1)
     w = rnd((cout, cin, k, k), 2, (2.0 / (cin * k * k)) ** 0.5)
     b = rnd((cout,), 3, 0.1)
     xr, wr, br = (t.clone().requires_grad_(True) for t in (x, w, b))
     yr = ref_conv(xr, wr, br, stride, pad, pt, ups, act)
     dy = rnd(tuple(yr.shape), 4)
     yr.backward(dy)
+    gx, gw, gb = xr.grad, wr.grad, br.grad
+    if twin:      # the device sums each distinct sample twice into the parameter gradients
+        x, dy, yr = torch.cat([x, x]), torch.cat([dy, dy]), torch.cat([yr, yr]).detach()
+        gx, gw, gb = torch.cat([gx, gx]), 2 * gw, 2 * gb
 
     xd = x.float().to(dev()).requires_grad_(True)
     wd = w.float().to(dev()).contiguous(memory_format=torch.channels_last).requires_grad_(True)
@@ -98,9 +134,11 @@ def test_conv_fwd_bwd(case):
     assert tuple(y.shape) == tuple(yr.shape)
     assert nerr(y, yr) <= FWD_TOL, nerr(y, yr)
     y.backward(dy.float().to(dev()))
-    assert nerr(xd.grad, xr.grad) <= BWD_TOL, ("dx", nerr(xd.grad, xr.grad))
-    assert nerr(wd.grad, wr.grad) <= BWD_TOL, ("dw", nerr(wd.grad, wr.grad))
-    assert nerr(bd.grad, br.grad) <= BWD_TOL, ("db", nerr(bd.grad, br.grad))
+    if twin:
+        assert torch.equal(y[B // 2:], y[:B // 2]) and torch.equal(xd.grad[B // 2:], xd.grad[:B // 2]), "twin samples differ"
+    assert nerr(xd.grad, gx) <= BWD_TOL, ("dx", nerr(xd.grad, gx))
+    assert nerr(wd.grad, gw) <= BWD_TOL, ("dw", nerr(wd.grad, gw))
+    assert nerr(bd.grad, gb) <= BWD_TOL, ("db", nerr(bd.grad, gb))
 
 
 def test_conv_stride2_winograd_on_small_shapes():
@@ -356,3 +394,41 @@ def test_linear_entry_points():
                                     vp(dw.data_ptr()), vp(db.data_ptr()), B, K, N, ctypes.c_float(0.0), vp(ws.data_ptr()),
                                     ctypes.c_size_t(nws), st), "linear_bwd")
     assert nerr(dx, xr.grad) <= BWD_TOL and nerr(dw, wr.grad) <= BWD_TOL and nerr(db, br.grad) <= BWD_TOL
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# contract of the raw C entry points (tests/conv_contract.py): guard bands, NaN poison, full writes, determinism, prepared
+# images, `add`, `beta`, db == NULL and the workspace size -- on every op case, the BASELINE-shape layers and the linears
+# ------------------------------------------------------------------------------------------------------------------------
+def _contract_cases():
+    from tests.test_gpu_shapes import LAYERS
+    return list(CONV_CASES) + [(ci, co, k, s, p, "reflect", u, a, b, h, w) for _, ci, co, k, s, p, u, a, b, h, w in LAYERS]
+
+
+def _bf16s_form(c):
+    """The kinds of layer the bf16-storage trainer runs on bf16 tensors: 64-multiples of channels on both sides, reflect
+    padding, 4x4 / stride 2 down-sampling, 3x3 trunk, nearest x2 + 5x5 up-sampling."""
+    cin, cout, k, stride, pad, pt, ups, act, B, H, W = c
+    kind = (k, stride, pad, ups) in ((4, 2, 1, 0), (3, 1, 1, 0), (5, 1, 2, 1))
+    return cin % 64 == 0 and cout % 64 == 0 and pt == "reflect" and kind
+
+
+_CID = lambda c: "c%d-%d_k%ds%d_%s_u%d_%s_b%d_%dx%d" % (c[0], c[1], c[2], c[3], c[5], c[6], c[7], c[8], c[9], c[10])
+
+
+@pytest.mark.parametrize("case", _contract_cases(), ids=_CID)
+def test_conv_entry_point_contract(case):
+    from tests.conv_contract import check_conv_case
+    check_conv_case(case)
+
+
+@pytest.mark.parametrize("case", [c for c in _contract_cases() if _bf16s_form(c)], ids=_CID)
+def test_conv_entry_point_contract_bf16_storage(case):
+    from tests.conv_contract import check_conv_case
+    check_conv_case(case, bf16=True)
+
+
+@pytest.mark.parametrize("case", LINEAR_CASES, ids=lambda c: "b%d_%d-%d_%s" % c)
+def test_linear_entry_point_contract(case):
+    from tests.conv_contract import check_linear
+    check_linear(*case)
