@@ -189,7 +189,7 @@ int munit_act_bwd(int act, float slope, const float* y, const float* dy, float* 
  * networks.py:230-239, done by address).  relu: the activation act() as MUNIT_ACT_* -- 0 none, 1 ReLU,
  * 2 LeakyReLU(0.2), 3 tanh (networks.py:668-681 pairs any norm with any activation).  residual may be NULL
  * (ResBlock's `out += residual`, networks.py:620-624).
- * stats: [B][C][2] (mean, rstd) written for the backward.  C % 4 == 0.
+ * stats: [B][C][2] (mean, rstd) written for the backward.  C % 4 == 0, C <= 1024.
  * ------------------------------------------------------------------------------------ */
 size_t munit_instnorm_workspace_bytes(int B, int HW, int C);
 int munit_instnorm_fwd(const float* x, float* y, float* stats, int B, int HW, int C,
@@ -212,7 +212,7 @@ int munit_instnorm_bwd_bf16(const void* x, const void* dy, const float* stats, v
 /* ------------------------------------------------------------------------------------
  * MUNIT's custom LayerNorm (scripts/networks.py:851-878): per-sample mean and UNBIASED
  * std over C*H*W, y = act( (x - mean) / (std + eps) * gamma[c] + beta[c] ), act = MUNIT_ACT_* in `relu`.
- * stats: [B][2] (mean, std).  C % 4 == 0.
+ * stats: [B][2] (mean, std).  C % 4 == 0, C <= 1024.
  * ------------------------------------------------------------------------------------ */
 size_t munit_layernorm_workspace_bytes(int B, int HW, int C);
 int munit_layernorm_fwd(const float* x, float* y, float* stats, int B, int HW, int C,

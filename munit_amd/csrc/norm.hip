@@ -15,6 +15,11 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int MAX_SPLIT = 64;
+// Largest channel count the entry points take: C / 4 <= NT channel quads, so that every thread of a block that walks all
+// the quads of a plane (make_lay(C): in_stats / in_bwd_stats on the non-sliced path, ln_bwd_stats always) makes exactly one
+// pass of the quad loop and reaches its __syncthreads() as often as every other thread.  Past NT quads the trip count
+// would depend on threadIdx.x wherever C / 4 is not a multiple of NT.
+constexpr int MAX_NORM_C = 4 * NT;
 
 // Activation behind the normalisation (networks.py:668-681, 695-701 pair any norm with any activation).  The `relu` argument of
 // the entry points is an activation code: 0 none, 1 ReLU, 2 LeakyReLU(0.2) (the reference's fixed slope, networks.py:672),
@@ -709,7 +714,7 @@ int instnorm_fwd_t(const T* x, T* y, float* stats, int B, int HW, int C, const f
                    int b_off, const T* residual, int relu, float eps, void* ws, size_t ws_bytes, munit_stream_t stream) {
   MUNIT_CHECK_ARG(x && y && stats && ws, "instnorm_fwd: null pointer");
   MUNIT_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C % 4 == 0, "instnorm_fwd: bad dims B=%d HW=%d C=%d", B, HW, C);
-  MUNIT_CHECK_ARG(C <= 4096, "instnorm_fwd: C=%d too large", C);
+  MUNIT_CHECK_ARG(C <= MAX_NORM_C, "instnorm_fwd: C=%d too large", C);
   if (ws_bytes < munit_instnorm_workspace_bytes(B, HW, C)) {
     munit_set_error("instnorm_fwd: workspace too small");
     return MUNIT_ERR_WORKSPACE;
@@ -747,7 +752,7 @@ int instnorm_bwd_t(const T* x, const T* dy, const float* stats, T* dx, int B, in
                    float* d_adain, int ad_ld, int w_off, int b_off, int relu, void* ws, size_t ws_bytes,
                    munit_stream_t stream) {
   MUNIT_CHECK_ARG(x && dy && stats && dx && ws, "instnorm_bwd: null pointer");
-  MUNIT_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 4096, "instnorm_bwd: bad dims");
+  MUNIT_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= MAX_NORM_C, "instnorm_bwd: bad dims");
   if (ws_bytes < munit_instnorm_workspace_bytes(B, HW, C)) {
     munit_set_error("instnorm_bwd: workspace too small");
     return MUNIT_ERR_WORKSPACE;
@@ -815,7 +820,7 @@ template <typename T>
 int layernorm_fwd_t(const T* x, T* y, float* stats, int B, int HW, int C, const float* gamma, const float* beta, int relu,
                     float eps, void* ws, size_t ws_bytes, munit_stream_t stream) {
   MUNIT_CHECK_ARG(x && y && stats && gamma && beta && ws, "layernorm_fwd: null pointer");
-  MUNIT_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 4096, "layernorm_fwd: bad dims");
+  MUNIT_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= MAX_NORM_C, "layernorm_fwd: bad dims");
   MUNIT_CHECK_ARG((long long)HW * C > 1, "layernorm_fwd: unbiased std needs more than one element");
   if (ws_bytes < munit_layernorm_workspace_bytes(B, HW, C)) {
     munit_set_error("layernorm_fwd: workspace too small");
@@ -837,7 +842,7 @@ int layernorm_bwd_t(const T* x, const T* dy, const float* stats, T* dx, int B, i
                     const float* beta, float* dgamma, float* dbeta, float acc, int relu, float eps, void* ws,
                     size_t ws_bytes, munit_stream_t stream) {
   MUNIT_CHECK_ARG(x && dy && stats && dx && gamma && beta && dgamma && dbeta && ws, "layernorm_bwd: null pointer");
-  MUNIT_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= 4096, "layernorm_bwd: bad dims");
+  MUNIT_CHECK_ARG(B > 0 && HW > 0 && C > 0 && C % 4 == 0 && C <= MAX_NORM_C, "layernorm_bwd: bad dims");
   if (ws_bytes < munit_layernorm_workspace_bytes(B, HW, C)) {
     munit_set_error("layernorm_bwd: workspace too small");
     return MUNIT_ERR_WORKSPACE;

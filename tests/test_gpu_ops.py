@@ -432,3 +432,372 @@ def test_conv_entry_point_contract_bf16_storage(case):
 def test_linear_entry_point_contract(case):
     from tests.conv_contract import check_linear
     check_linear(*case)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# normalisation at the shapes where the split logic changes regime (tests/test_cpu_norm_regimes.py maps every case to its
+# regime and requires each regime production reaches, and each edge it lists, to be run here; every case has a regime of
+# its own)
+# ------------------------------------------------------------------------------------------------------------------------
+NORM_CASES = [
+    # kind, dtype, B, C, H, W
+    ("in", "f32", 2, 64, 1, 1),             # HW = 1
+    ("in", "f32", 2, 16, 8, 8),             # HW = 64: one split
+    ("adain", "f32", 3, 12, 127, 1),        # HW = 127: the last one-split extent; C = 12: QB = 3, idle lanes
+    ("in", "f32", 2, 4, 16, 8),             # HW = 128: two splits; C = 4: one quad, 256 pixel lanes
+    ("adain", "f32", 2, 68, 43, 3),         # HW = 129: a short last split; C = 68: a partial second fold block
+    ("adain", "f32", 33, 12, 64, 64),       # B = 33: 62 splits
+    ("in", "f32", 1, 64, 64, 64),           # B = 1, HW = 4096: the 64-split cap
+    ("adain", "f32", 32, 128, 32, 32),      # B = 32
+    ("adain", "f32", 2, 192, 64, 64),       # 3 slices: 64 / 3 -> 21 splits, short last split
+    ("in", "f32", 1, 320, 24, 32),          # 5 slices: 12 / 5 -> 2 splits
+    ("adain", "f32", 1, 128, 20, 32),       # 2 slices, 5 splits
+    ("adain", "f32", 1, 1024, 16, 16),      # the largest C: 16 slices
+    ("in", "f32", 1, 1020, 16, 8),          # the largest non-sliced C: 255 quads
+    ("in", "f32", 1, 16, 64, 64),           # non-sliced at the cap
+    ("adain", "f32", 1, 16, 2, 64),
+    ("in", "f32", 1, 16, 5, 64),
+    ("adain", "f32", 1, 64, 2, 64),
+    ("in", "f32", 1, 64, 5, 64),
+    ("adain", "f32", 1, 64, 43, 3),
+    ("in", "f32", 1, 64, 107, 3),
+    ("adain", "f32", 1, 128, 87, 3),
+    ("in", "f32", 1, 128, 2, 64),
+    ("ln", "f32", 2, 4, 1, 2),              # HW * C = 8
+    ("ln", "f32", 9, 12, 64, 64),           # 9 x 64 = 576 partial rows in ln_bwd_param_kernel
+    ("ln", "f32", 2, 1020, 4, 4),           # the largest C of ln_bwd_stats: 255 quads
+    ("ln", "f32", 1, 16, 64, 64),
+    ("ln", "f32", 1, 16, 2, 64),
+    ("ln", "f32", 1, 16, 5, 64),
+    ("ln", "f32", 1, 16, 97, 2),
+    ("ln", "f32", 1, 16, 107, 3),
+    ("adain", "bf16", 32, 256, 64, 64),     # bf16 storage: config #3's trunk, 4 slices x 16 splits
+    ("in", "bf16", 33, 12, 64, 64),         # bf16, non-sliced, 62 splits
+    ("in", "bf16", 1, 64, 64, 64),          # bf16, sliced at the cap
+    ("ln", "bf16", 1, 12, 64, 64),
+    ("ln", "bf16", 1, 16, 64, 64),
+]
+_NID = lambda c: "%s_%s_b%d_c%d_%dx%d" % c
+ACT_CODES = ("none", "relu", "lrelu", "tanh")
+BF16_OUT, BF16_DX = 8e-3, 1.2e-2          # tests/test_gpu_bf16s.py: bf16 outputs / dx
+
+
+def _norm_setup(case, i):
+    """Activation code and residual of case i (cycled over NORM_CASES); ReLU / LeakyReLU never with a residual, so the
+    reference can take the device's branches from the sign of y."""
+    act = ACT_CODES[i % 4]
+    return act, act in ("none", "tanh") and case[0] != "ln" and (i // 4) % 2 == 0
+
+
+def _pin(pre, y_dev, act):
+    """The reference's ReLU / LeakyReLU on the branches the device took (tests/test_gpu_shapes.py, pinned_relu)."""
+    from tests.test_gpu_shapes import KINK_FRAC, KINK_NOISE
+    mask = (y_dev.detach().float() > 0).cpu()
+    dis = (pre.detach() > 0) != mask
+    n = int(dis.sum())
+    if n:
+        worst = float(pre.detach()[dis].abs().max()) / float(pre.detach().abs().max())
+        assert worst <= KINK_NOISE and n <= KINK_FRAC * pre.numel(), (n, worst)
+    if act == "relu":
+        return torch.where(mask, pre, torch.zeros_like(pre))
+    return torch.where(mask, pre, pre * 0.2)
+
+
+def _act_ref(pre, y_dev, act):
+    if act in ("relu", "lrelu"):
+        return _pin(pre, y_dev, act)
+    return torch.tanh(pre) if act == "tanh" else pre
+
+
+def run_norm(kind, dt, shape, act, residual, x=None, seed=1):
+    """Device norm (ops) and its fp64 reference on the same (fp32- or bf16-rounded) values.  Returns
+    [(name, device tensor, reference, tolerance)], including the statistics, compared directly."""
+    from munit_amd import ops
+    B, C, H, W = shape
+    q = (lambda t: t.float().bfloat16().double()) if dt == "bf16" else (lambda t: t.float().double())
+    tdt = torch.bfloat16 if dt == "bf16" else torch.float32
+    fwd_tol, dx_tol = (BF16_OUT, BF16_DX) if dt == "bf16" else (FWD_TOL, BWD_TOL)
+    x = q(rnd(shape, seed, 1.7) + 0.4 if x is None else x)
+    dy = q(rnd(shape, seed + 3))
+    res = q(rnd(shape, seed + 4))
+    cl = lambda t: t.to(tdt).to(dev()).contiguous(memory_format=torch.channels_last)
+    xr, xd = x.clone().requires_grad_(True), cl(x).requires_grad_(True)
+    out, extra = [], []
+    prev = ops.get_compute()
+    ops.set_compute("bf16s" if dt == "bf16" else "f32")
+    try:
+        if kind == "ln":
+            g = torch.rand(C, generator=torch.Generator().manual_seed(seed + 1), dtype=torch.float64) + 0.2
+            bt = rnd((C,), seed + 2, 0.3)
+            gr, br = g.clone().requires_grad_(True), bt.clone().requires_grad_(True)
+            gd, bd = g.float().to(dev()).requires_grad_(True), bt.float().to(dev()).requires_grad_(True)
+            y = ops.layer_norm(xd, gd, bd, act)
+            pre = O.munit_layer_norm(xr, gr, br)
+            flat = x.reshape(B, -1)
+            st_ref = torch.stack([flat.mean(1), flat.std(1, unbiased=True)], 1)
+            extra = [("dgamma", gd, gr), ("dbeta", bd, br)]
+            stats_of = lambda: y.grad_fn.saved_tensors[1]
+        else:
+            rd = cl(res) if residual else None
+            if kind == "adain":
+                params = rnd((B, 4 * C), seed + 2) + 0.5
+                w_off, b_off = 3 * C, C
+                pr, pd = params.clone().requires_grad_(True), params.float().to(dev()).requires_grad_(True)
+                y = ops.adain(xd, pd, w_off, b_off, act, rd)
+                pre = O.adain(xr, pr[:, w_off:w_off + C], pr[:, b_off:b_off + C])
+                extra = [("d_adain", pd, pr)]
+            else:
+                y = ops.instance_norm(xd, act, rd)
+                pre = O.instance_norm(xr)
+            mu = x.mean(dim=(2, 3))
+            var = ((x - mu[:, :, None, None]) ** 2).mean(dim=(2, 3))
+            st_ref = torch.stack([mu, 1.0 / torch.sqrt(var + 1e-5)], 2)
+            stats_of = lambda: y.grad_fn.saved_tensors[1]
+        yr = _act_ref(pre, y, act)
+        if residual:
+            yr = yr + res
+        stats = stats_of()
+        out.append(("y", y, yr, fwd_tol))
+        out.append(("mean", stats[..., 0], st_ref[..., 0], FWD_TOL))
+        out.append(("std" if kind == "ln" else "rstd", stats[..., 1], st_ref[..., 1], FWD_TOL))
+        yr.backward(dy)
+        y.backward(cl(dy))
+    finally:
+        ops.set_compute(prev)
+    out.append(("dx", xd.grad, xr.grad, dx_tol))
+    out += [(n, d.grad, r.grad, BWD_TOL) for n, d, r in extra]
+    return out
+
+
+def _assert_all(results, what):
+    errs = {n: nerr(d, r) for n, d, r, _ in results}
+    bad = {n: e for (n, d, r, tol), e in zip(results, errs.values()) if not e <= tol}
+    assert not bad, (what, bad, errs)
+
+
+@pytest.mark.parametrize("i", range(len(NORM_CASES)), ids=lambda i: _NID(NORM_CASES[i]))
+def test_norm_regime(i):
+    kind, dt, B, C, H, W = NORM_CASES[i]
+    act, residual = _norm_setup(NORM_CASES[i], i)
+    _assert_all(run_norm(kind, dt, (B, C, H, W), act, residual, seed=i + 1), (NORM_CASES[i], act, residual))
+
+
+@pytest.mark.parametrize("kind", ["in", "adain"])
+def test_norm_constant_plane(kind):
+    """Variance 0 in every third channel: AdaIN gives its bias there, all gradients finite and equal to the fp64 ones."""
+    B, C, H, W = 2, 68, 9, 15
+    x = rnd((B, C, H, W), 3, 1.3)
+    x[:, ::3] = rnd((B, C, 1, 1), 4)[:, ::3]
+    res = run_norm(kind, "f32", (B, C, H, W), "relu" if kind == "adain" else "none", False, x=x)
+    for n, d, r, _ in res:
+        assert bool(torch.isfinite(d.detach().float()).all()), (kind, n)
+    _assert_all(res, kind)
+
+
+@pytest.mark.parametrize("kind", ["in", "adain", "ln"])
+def test_norm_large_mean(kind):
+    """Offset 1e3, spread 1e-2 (the fp64 reference runs on the same fp32 values): the pivot keeps the variance free of
+    cancellation, so the statistics hold the fp32 bound.  y, dx and the parameter gradients are computed from the fp32
+    mean, whose rounding (ulp(1e3) = 6e-5 against a spread of 1e-2) shifts every normalised value of a plane alike: they
+    are held to that, eight ulps of the mean in units of the standard deviation."""
+    B, C, H, W = 2, 64 if kind != "ln" else 12, 16, 16
+    x = (1e3 + rnd((B, C, H, W), 5, 1e-2)).float().double()
+    res = run_norm(kind, "f32", (B, C, H, W), "none", False, x=x)
+    cond = 8 * 2.0 ** -24 * 1e3 / 1e-2
+    _assert_all([(n, d, r, t if n in ("mean", "rstd", "std") else max(t, cond)) for n, d, r, t in res], kind)
+
+
+@pytest.mark.parametrize("H,W", [(h, w) for h in range(1, 6) for w in range(1, 6)])
+def test_avgpool_borders(H, W):
+    from munit_amd import ops
+    x = rnd((1, 64, H, W), H * 10 + W)
+    xr = x.clone().requires_grad_(True)
+    yr = O.avgpool_3s2(xr)
+    dy = rnd(tuple(yr.shape), 2)
+    yr.backward(dy)
+    xd = x.float().to(dev()).requires_grad_(True)
+    y = ops.avgpool3s2(xd)
+    assert tuple(y.shape) == tuple(yr.shape) and nerr(y, yr) <= 1e-6
+    y.backward(dy.float().to(dev()))
+    assert nerr(xd.grad, xr.grad) <= 1e-6
+
+
+def test_avgpool_pyramid():
+    """The discriminator's input pyramid at batch 8: 256 -> 128 -> 64, three channels."""
+    from munit_amd import ops
+    x = rnd((8, 3, 256, 256), 9)
+    xr = x.clone().requires_grad_(True)
+    yr = O.avgpool_3s2(O.avgpool_3s2(xr))
+    dy = rnd(tuple(yr.shape), 2)
+    yr.backward(dy)
+    xd = x.float().to(dev()).requires_grad_(True)
+    y = ops.avgpool3s2(ops.avgpool3s2(xd))
+    assert tuple(y.shape) == (8, 3, 64, 64) and nerr(y, yr) <= 1e-6
+    y.backward(dy.float().to(dev()))
+    assert nerr(xd.grad, xr.grad) <= 1e-6
+
+
+@pytest.mark.parametrize("shape,positive", [((2, 256, 1, 1), False), ((8, 256, 32, 32), True), ((3, 100, 7, 7), False)])
+def test_global_avgpool_shapes(shape, positive):
+    from munit_amd import ops
+    x = rnd(shape, 1)
+    if positive:
+        x = x.clamp_min(0)
+    xr = x.clone().requires_grad_(True)
+    yr = xr.mean(dim=(2, 3), keepdim=True)
+    dy = rnd(tuple(yr.shape), 2)
+    yr.backward(dy)
+    xd = x.float().to(dev()).requires_grad_(True)
+    y = ops.global_avgpool(xd)
+    assert nerr(y, yr) <= 1e-6
+    y.backward(dy.float().to(dev()))
+    assert nerr(xd.grad, xr.grad) <= 1e-6
+
+
+@pytest.mark.parametrize("shape,masked", [((1, 1, 1, 1), False), ((1, 1, 1, 262145), False), ((8, 3, 256, 256), True),
+                                          ((8, 256, 64, 64), False)], ids=["n1", "n262145", "image_masked", "content"])
+def test_l1_mean_sizes(shape, masked):
+    """One element; one past a full pass of 1024 x 256 threads (the grid-stride wrap of the partial kernel); the image
+    reconstruction with a mask and the content code of config_256 at batch 8.  Every seventh element has a == b exactly:
+    gradient 0, as torch.sign."""
+    from munit_amd import ops
+    a, b = rnd(shape, 1).float().double(), rnd(shape, 2).float().double()
+    b.view(-1)[::7] = a.view(-1)[::7]
+    m = None
+    if masked:
+        B, _, H, W = shape
+        m = (torch.rand(B, 1, H, W, generator=torch.Generator().manual_seed(3)) > 0.5).double()
+    lr = O.l1_masked(a, b, m) if masked else O.l1(a, b)
+    ad, bd = (t.float().to(dev()).requires_grad_(True) for t in (a, b))
+    l = ops.l1_mean(ad, bd, m.float().to(dev()) if masked else None)
+    assert abs(float(l) - float(lr)) <= 1e-6 * abs(float(lr))
+    torch.autograd.backward([l], [torch.tensor(12.0, device=dev())])
+    g = 12.0 * torch.sign(a - b) / a.numel()
+    if masked:
+        g = g * (1 - m)
+    assert nerr(ad.grad, g) <= 1e-6 and nerr(bd.grad, -g) <= 1e-6
+    assert bool((ad.grad.cpu().view(-1)[::7] == 0).all())
+
+
+def test_l1_mean_bf16_content_code():
+    """bf16 storage: the content-code reconstruction of config #3 (32 x 256 x 64 x 64)."""
+    from munit_amd import ops
+    shape = (32, 256, 64, 64)
+    a, b = rnd(shape, 13).float().bfloat16(), rnd(shape, 14).float().bfloat16()
+    ad = a.to(dev()).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    bd = b.to(dev()).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    a, b = a.double(), b.double()
+    out = ops.l1_mean(ad, bd)
+    ref = float((a - b).abs().mean())
+    assert out.dtype == torch.float32 and abs(float(out.detach()) - ref) <= 1e-6 * ref
+    out.backward()
+    g = torch.sign(a - b) / a.numel()
+    assert nerr(ad.grad, g) <= BF16_OUT and nerr(bd.grad, -g) <= BF16_OUT
+
+
+@pytest.mark.parametrize("target", [0.0, 1.0])
+def test_mse_const_sizes(target):
+    """n = 1 and the discriminator outputs of config #2 (256 x 256, batch 8): 16 x 16, 8 x 8, 4 x 4."""
+    from munit_amd import ops
+    for shape in [(1, 1, 1, 1), (8, 1, 16, 16), (8, 1, 8, 8), (8, 1, 4, 4)]:
+        x = rnd(shape, 5)
+        xr = x.clone().requires_grad_(True)
+        lr = torch.mean((xr - target) ** 2)
+        (3.0 * lr).backward()
+        xd = x.float().to(dev()).requires_grad_(True)
+        l = ops.mse_const(xd, target)
+        assert abs(float(l) - float(lr)) <= 1e-6 * float(lr), (shape, target)
+        torch.autograd.backward([l], [torch.tensor(3.0, device=dev())])
+        assert nerr(xd.grad, xr.grad) <= 1e-6, (shape, target)
+
+
+ADAM_WRAP = 2048 * 256 * 4 + 5      # past one grid-stride pass of the float4 loop, with a 1-element tail
+
+
+@pytest.mark.parametrize("n", [1, 3, ADAM_WRAP])
+@pytest.mark.parametrize("wd", [0.0, 1e-2])
+@pytest.mark.parametrize("step", [1, 1000])
+def test_adam_sizes(n, wd, step):
+    """One update from a live state against O.adam_update in fp64: bias correction at steps 1 and 1000, weight decay 0 and
+    1e-2, the scalar tail alone (n = 1, 3) and the grid-stride wrap."""
+    from munit_amd import ops
+    p, g = rnd((n,), 1).float().double(), rnd((n,), 2, 0.01).float().double()
+    m, v = rnd((n,), 3, 0.01).float().double(), (rnd((n,), 4, 0.01) ** 2).float().double()
+    pd, gd, md, vd = (t.float().to(dev()).contiguous() for t in (p, g, m, v))
+    O.adam_update(p, g, m, v, step, 1e-4, 0.5, 0.999, 1e-8, wd)
+    ops.adam_step(pd, gd, md, vd, 1e-4, 0.5, 0.999, 1e-8, wd, step)
+    ep, em, ev = float((pd.double().cpu() - p).abs().max()), nerr(md, m), nerr(vd, v)
+    assert ep <= 2e-6 and em <= 1e-6 and ev <= 1e-6, (ep, em, ev)
+
+
+def test_extraadam_wrap():
+    """ExtraAdam modes 0, 1, 2 (first extrapolation, a further one, the step) at the grid-stride wrap size."""
+    from munit_amd import ops
+    n = ADAM_WRAP
+    p0 = rnd((n,), 1).float().double()
+    gs = [rnd((n,), 10 + k, 0.3).float().double() for k in range(3)]
+    pr = [p0.clone()]
+    st = O.ExtraAdamState(pr, 1e-3, (0.5, 0.999), 1e-2)
+    pd = p0.float().to(dev()).contiguous()
+    md, vd, sd = torch.zeros(n, device=dev()), torch.zeros(n, device=dev()), torch.zeros(n, device=dev())
+    for k, (mode, code) in enumerate([("extrapolation", 0), ("extrapolation", 1), ("step", 2)]):
+        getattr(st, mode)([gs[k]])
+        ops.extraadam_step(pd, gs[k].float().to(dev()).contiguous(), md, vd, sd, 1e-3, 0.5, 0.999, 1e-8, 1e-2, k + 1, code)
+        assert float((pd.double().cpu() - pr[0]).abs().max()) <= 2e-6, (k, mode)
+    assert nerr(md, st.m[0]) <= 1e-6 and nerr(vd, st.v[0]) <= 1e-6
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# contract of the non-conv entry points (tests/kernel_contract.py)
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("i", range(len(NORM_CASES)), ids=lambda i: _NID(NORM_CASES[i]))
+def test_norm_entry_point_contract(i):
+    """Guards, poison, full writes, determinism, d_adain columns, LayerNorm acc, the short workspace -- and the split
+    partials left in the workspace equal tests/test_cpu_norm_regimes.py's restatement of the split logic."""
+    from tests import kernel_contract as K
+    from tests.test_cpu_norm_regimes import partial_doubles
+    kind, dt, B, C, H, W = NORM_CASES[i]
+    act, residual = _norm_setup(NORM_CASES[i], i)
+    code = ACT_CODES.index(act)
+    if kind == "ln":
+        nf, nb = K.check_layernorm(B, H * W, C, dt == "bf16", code)
+    else:
+        nf, nb = K.check_instnorm(B, H * W, C, dt == "bf16", kind == "adain", residual, code)
+    want = (partial_doubles(kind, B, H * W, C, False), partial_doubles(kind, B, H * W, C, True))
+    assert (nf, nb) == want, ("split partials in the workspace", NORM_CASES[i], (nf, nb), want)
+
+
+@pytest.mark.parametrize("B,H,W,C", [(1, 1, 1, 64), (2, 2, 3, 64), (1, 5, 4, 64), (8, 256, 256, 3), (3, 13, 7, 5)])
+def test_pool_entry_point_contract(B, H, W, C):
+    from tests import kernel_contract as K
+    K.check_avgpool(B, H, W, C)
+    K.check_gap(B, H * W, C)
+
+
+def test_pointwise_entry_point_contract():
+    from tests import kernel_contract as K
+    for n in (1, 3, 1027, 262145):
+        K.check_act_bwd(n)
+        K.check_scale(n)
+    K.check_weighted_sum()
+
+
+@pytest.mark.parametrize("npix,C,masked,bf16", [(1, 1, False, False), (262145, 1, True, False), (8 * 64 * 64, 3, True, False),
+                                               (2 * 16 * 16, 256, False, True), (262145, 2, True, True)])
+def test_loss_entry_point_contract(npix, C, masked, bf16):
+    from tests import kernel_contract as K
+    K.check_l1(npix, C, masked, bf16)
+    if not bf16:
+        K.check_mse(npix * C, float(masked))
+
+
+@pytest.mark.parametrize("n", [1, 3, 1027, ADAM_WRAP])
+def test_optimizer_entry_point_contract(n):
+    from tests import kernel_contract as K
+    K.check_adam(n)
+
+
+@pytest.mark.parametrize("B,h,w", [(1, 8, 8), (3, 17, 12)])
+def test_image_entry_point_contract(B, h, w):
+    from tests import kernel_contract as K
+    K.check_image(B, h, w)
