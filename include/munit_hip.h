@@ -320,6 +320,44 @@ size_t munit_mask_preprocess_workspace_bytes(int B, int out_h, int out_w);
 int munit_mask_preprocess(const unsigned char* pool, const munit_image_desc* descs, int B, int out_h,
                           int out_w, float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Semantic-consistency loss (scripts/trainer.py:706-771): the frozen Resnet34_8s segmentation network
+ * (scripts/utils.py:933-983, scripts/resnet.py) and its head.  The convolutions run through munit_conv2d_* with
+ * BatchNorm folded into their weights; the dilated 3x3 layers of layer3 / layer4 run undilated on the phase images
+ * of munit_space_to_batch.  Images and activations are NHWC fp32.
+ * ------------------------------------------------------------------------------------ */
+/* seg_transform of (x + 1) / 2 (utils.py:159-174): y = ((x + 1) / 2 - mean_c) / std_c with the ImageNet statistics;
+ * x, y: npix pixels of 3 channels.  bwd: dx = dy / std_c / 2. */
+int munit_seg_input_fwd(const float* x, float* y, size_t npix, munit_stream_t stream);
+int munit_seg_input_bwd(const float* dy, float* dx, size_t npix, munit_stream_t stream);
+/* Space-to-batch by f (inverse 0): y[(n*f + py)*f + px][i][j][c] = x[n][i*f + py][j*f + px][c], x [N][H][W][C],
+ * H % f == W % f == 0.  inverse 1: the way back -- x is then the phase-major [N*f*f][H/f][W/f][C] input and y the
+ * [N][H][W][C] output (N, H, W always describe the plain layout).  A dilation-d 3x3 conv
+ * with zero pad d is the undilated pad-1 conv on every phase image; applied twice with f = 2 it gives the d = 4 phases.
+ * A permutation: each pass is the other's adjoint. */
+int munit_space_to_batch(const float* x, float* y, int N, int H, int W, int C, int f, int inverse, munit_stream_t stream);
+/* nn.MaxPool2d(3, stride=2, padding=1): y [B][Ho][Wo][C], Ho = (H - 1) / 2 + 1.  idx (one byte per output) receives the
+ * window position kh*3 + kw of the winner: the FIRST maximal element in window order (kh-major), torch's tie rule.
+ * bwd: dx[h][w] = sum of dy over the windows whose recorded winner is (h, w) (a gather; deterministic). */
+int munit_maxpool3s2_fwd(const float* x, float* y, unsigned char* idx, int B, int H, int W, int C, munit_stream_t stream);
+int munit_maxpool3s2_bwd(const float* dy, const unsigned char* idx, float* dx, int B, int H, int W, int C,
+                         munit_stream_t stream);
+/* BasicBlock tail y = relu(a + r), n % 4 == 0 (backward: munit_act_bwd with MUNIT_ACT_RELU on y). */
+int munit_add_relu_fwd(const float* a, const float* r, float* y, size_t n, munit_stream_t stream);
+/* Head: logits [B][h][w][19] are up-sampled bilinearly (align_corners = False) to [B][h*S][w*S] on the fly.
+ * labels [B][h*S][w*S] int32 in 0..18.  mask [B][h*S][w*S] (values 0 / 1) or NULL.  NULL: nn.CrossEntropyLoss over the
+ * 19 classes.  Otherwise the masked form of trainer.py:746-769: logits (1 - m) * z with m appended as a 20th class,
+ * target (1 - m) * label + 19 m.  out = (sum of the pixel losses) / norm (one device float; norm = pixels per mean, so
+ * one call over a batch of two images per pair gives the sum of the two means).  bwd: dlogits [B][h][w][19] =
+ * gout[0] / norm * adjoint of the up-sample of the pixel gradients (a gather; deterministic).  ws: _workspace_bytes. */
+size_t munit_seg_ce_workspace_bytes(int B, int h, int w, int S);
+int munit_seg_ce_fwd(const float* logits, const int* labels, const float* mask, int B, int h, int w, int S, float norm,
+                     float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
+int munit_seg_ce_bwd(const float* logits, const int* labels, const float* mask, int B, int h, int w, int S, float norm,
+                     const float* gout, float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream);
+/* labels = argmax over the 19 up-sampled logits (first maximal class on ties: torch's max(1)[1]). */
+int munit_seg_labels(const float* logits, int B, int h, int w, int S, int* labels, munit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

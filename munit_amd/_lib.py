@@ -109,6 +109,16 @@ SIGNATURES = {
     "munit_image_preprocess": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "munit_mask_preprocess_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "munit_mask_preprocess": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "munit_seg_input_fwd": (c_int, [_P, _P, c_size_t, _P]),
+    "munit_seg_input_bwd": (c_int, [_P, _P, c_size_t, _P]),
+    "munit_space_to_batch": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "munit_maxpool3s2_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "munit_maxpool3s2_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "munit_add_relu_fwd": (c_int, [_P, _P, _P, c_size_t, _P]),
+    "munit_seg_ce_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "munit_seg_ce_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
+    "munit_seg_ce_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
+    "munit_seg_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 _lib = None

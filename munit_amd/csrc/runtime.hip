@@ -17,7 +17,9 @@ extern "C" const char* munit_last_error(void) { return g_err; }
 // 2: munit_conv_desc carries in_dtype / out_dtype (a caller built against version 1 passes a short struct); the hipGraph
 // entry points of version 1 (munit_adam_step_graph, munit_store_floats, munit_stream_cross_wait) are gone.
 // 3: + munit_comm_unique_id / _init / _allreduce / _destroy, munit_shutdown (comm.hip); nothing removed or changed.
-extern "C" int munit_version(void) { return 4; }
+// 5: + the Resnet34_8s semantic-loss kernels (seg.hip): munit_seg_input_*, munit_space_to_batch, munit_maxpool3s2_*,
+// munit_add_relu_fwd, munit_seg_ce_*, munit_seg_labels; nothing removed or changed.
+extern "C" int munit_version(void) { return 5; }
 
 // waiter stream waits for everything enqueued so far on signaler (both on the current device): hipEventRecord +
 // hipStreamWaitEvent on one cached event per (thread, device) -- the wait captures the event's state when it is issued, so

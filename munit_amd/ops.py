@@ -28,6 +28,9 @@ PROFILE = None
 MASK_SINK = None
 # likewise for the other kink of the objective: the sign of (input - target) behind every L1 term, in call order
 L1_SINK = None
+# likewise for the frozen segmentation network of the semantic loss (munit_amd/segmentation.py): its ReLU sign patterns,
+# max-pool winners and pseudo-labels, in call order, kept apart so that the generator's kink order above is untouched
+SEG_SINK = None
 # bench.py sets this to {"alg": 0.0, "exec": 0.0} to add up, over one step, the algorithmic FLOPs of every convolution /
 # linear pass (SURVEY.md section 8d's definition) and the FLOPs the kernels actually issue (sub-pixel and box-sum
 # forms execute fewer).
@@ -278,9 +281,10 @@ def prepare_weights_batch(table, n):
 # ------------------------------------------------------------------------------------------
 # raw (non-autograd) entry points, also used by the tests
 # ------------------------------------------------------------------------------------------
-def conv2d_fwd_raw(x, weight, bias, stride, pad, pad_type, upsample, act, slope=0.2, owner=None, out_dtype=None):
+def conv2d_fwd_raw(x, weight, bias, stride, pad, pad_type, upsample, act, slope=0.2, owner=None, out_dtype=None, seg=False):
     """out_dtype: torch.float32 / torch.bfloat16 of y; default = x's dtype when Cout is a multiple of 64, else fp32
-    (3-channel images, small heads).  A bf16 x runs the bf16-storage kernels (weights stay fp32 parameters)."""
+    (3-channel images, small heads).  A bf16 x runs the bf16-storage kernels (weights stay fp32 parameters).
+    seg: a layer of the segmentation network (its ReLU signs go to SEG_SINK, not MASK_SINK)."""
     lib = _lib.load()
     x, weight = nhwc(x), nhwc(weight)
     _same_device(x, weight, bias)
@@ -304,8 +308,9 @@ def conv2d_fwd_raw(x, weight, bias, stride, pad, pad_type, upsample, act, slope=
             e1.record()
             PROFILE.append((0, pl, e0, e1))
         _count(pl, 0)
-    if MASK_SINK is not None and act in ("relu", "lrelu"):
-        MASK_SINK.append(y > 0)
+    sink = SEG_SINK if seg else MASK_SINK
+    if sink is not None and act in ("relu", "lrelu"):
+        sink.append(y > 0)
     return y
 
 
@@ -874,3 +879,271 @@ def scale_(x, alpha):
     with _on(x):
         _lib.check(lib.munit_scale(_p(x), _p(x), x.numel(), c_float(alpha), 0, _stream()), "scale")
     return x
+
+
+# ------------------------------------------------------------------------------------------
+# frozen Resnet34_8s of the semantic-consistency loss (munit_amd/segmentation.py; include/munit_hip.h, seg.hip).  The
+# network's parameters never get a gradient: these Functions return gradients of their activations only.
+# ------------------------------------------------------------------------------------------
+class _SegInput(Function):
+    """seg_transform((x + 1) / 2) of several images into ONE batch (trainer.py:720-725): the pair x_ab, x_ba runs the
+    network as a single 2B batch without a concatenation kernel."""
+    @staticmethod
+    @_guarded
+    def forward(ctx, *xs):
+        lib = _lib.load()
+        xs = [nhwc(x) for x in xs]
+        for x in xs:
+            _require(x, "segmentation input")
+            if x.dim() != 4 or x.shape[1] != 3 or x.shape[2:] != xs[0].shape[2:]:
+                raise RuntimeError("munit_amd.seg_input: images must be (B, 3, H, W) of one size, got %s" % (tuple(x.shape),))
+        _same_device(*xs)
+        _, _, h, w = xs[0].shape
+        y = empty_nhwc(sum(x.shape[0] for x in xs), 3, h, w, xs[0])
+        off = 0
+        for x in xs:
+            n = x.shape[0] * h * w
+            _lib.check(lib.munit_seg_input_fwd(_p(x), c_void_p(y.data_ptr() + off * 12), n, _stream()), "seg_input_fwd")
+            off += n
+        ctx.sizes = [x.shape for x in xs]
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        dy = nhwc(dy)
+        out, off = [], 0
+        for i, shp in enumerate(ctx.sizes):
+            n = shp[0] * shp[2] * shp[3]
+            if ctx.needs_input_grad[i]:
+                dx = empty_nhwc(shp[0], 3, shp[2], shp[3], dy)
+                _lib.check(lib.munit_seg_input_bwd(c_void_p(dy.data_ptr() + off * 12), _p(dx), n, _stream()),
+                           "seg_input_bwd")
+                out.append(dx)
+            else:
+                out.append(None)
+            off += n
+        return tuple(out)
+
+
+def seg_input(*xs):
+    return _SegInput.apply(*xs)
+
+
+class _FrozenConv(Function):
+    """Convolution (+ bias + optional ReLU) with a frozen weight.  w_dgrad: the weight backward-data multiplies by -- the
+    weight itself, or for the odd-kernel stride-2 layers its zero-extension to an even kernel (same output extent on
+    even inputs, same result; the phase form of backward-data needs KH % stride == 0).  link_in: dx += the gradient parked
+    there (the block's skip path); link_out: park dx there instead of returning it (the downsample branch, whose gradient
+    the block's first convolution adds)."""
+    @staticmethod
+    @_guarded
+    def forward(ctx, x, weight, bias, w_dgrad, stride, pad, act, link_in, link_out):
+        _require(x, "conv input")
+        x = nhwc(x)
+        y = conv2d_fwd_raw(x, weight, bias, stride, pad, "zero", False, act, seg=True)
+        ctx.cfg = (stride, pad, act, x.shape)
+        ctx.w_dgrad = w_dgrad
+        ctx.links = (link_in, link_out)
+        ctx.save_for_backward(y if act != "none" else None)
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        stride, pad, act, x_shape = ctx.cfg
+        link_in, link_out = ctx.links
+        dy = nhwc(dy)
+        if act != "none":
+            dy = act_bwd_raw(act, 0.0, y, dy)
+        add = None
+        if link_in is not None:
+            add = link_in.take()
+            if add is None:
+                raise RuntimeError("munit_amd: the skip gradient of a segmentation block was not formed before its first "
+                                   "convolution's backward")
+        dx = conv2d_dgrad_raw(dy, ctx.w_dgrad, x_shape, stride, pad, "zero", False, add=add)
+        if link_out is not None:
+            link_out.park(dx)
+            dx = None
+        return dx, None, None, None, None, None, None, None, None
+
+
+def frozen_conv(x, weight, bias, w_dgrad, stride, pad, act="none", link_in=None, link_out=None):
+    return _FrozenConv.apply(x, weight, bias, w_dgrad, stride, pad, act, link_in, link_out)
+
+
+class _MaxPool3s2(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, x):
+        lib = _lib.load()
+        _require(x, "maxpool input")
+        x = nhwc(x)
+        b, c, h, w = x.shape
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        y = empty_nhwc(b, c, ho, wo, x)
+        idx = torch.empty((b, ho, wo, c), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.munit_maxpool3s2_fwd(_p(x), _p(y), _p(idx), b, h, w, c, _stream()), "maxpool3s2_fwd")
+        if SEG_SINK is not None:
+            SEG_SINK.append(idx)
+        ctx.shape = x.shape
+        ctx.save_for_backward(idx)
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        (idx,) = ctx.saved_tensors
+        b, c, h, w = ctx.shape
+        dy = nhwc(dy)
+        dx = empty_nhwc(b, c, h, w, dy)
+        _lib.check(lib.munit_maxpool3s2_bwd(_p(dy), _p(idx), _p(dx), b, h, w, c, _stream()), "maxpool3s2_bwd")
+        return dx
+
+
+def maxpool3s2(x):
+    """nn.MaxPool2d(3, 2, 1) (scripts/resnet.py); ties go to the first maximal element in window order."""
+    return _MaxPool3s2.apply(x)
+
+
+class _AddRelu(Function):
+    """BasicBlock tail relu(a + r).  link: park the gradient of r there (the identity skip: the block's first convolution
+    adds it in its backward-data epilogue) and return none for r."""
+    @staticmethod
+    @_guarded
+    def forward(ctx, a, r, link):
+        lib = _lib.load()
+        a, r = nhwc(a), nhwc(r)
+        _require(a, "block output")
+        _require(r, "block residual")
+        if a.shape != r.shape:
+            raise RuntimeError("munit_amd.add_relu: shapes differ (%s vs %s)" % (tuple(a.shape), tuple(r.shape)))
+        y = torch.empty_like(a)
+        _lib.check(lib.munit_add_relu_fwd(_p(a), _p(r), _p(y), a.numel(), _stream()), "add_relu_fwd")
+        if SEG_SINK is not None:
+            SEG_SINK.append(y > 0)
+        ctx.link = link
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        d = act_bwd_raw("relu", 0.0, y, nhwc(dy))
+        if ctx.link is not None:
+            ctx.link.park(d)
+            return d, None, None
+        return d, d, None
+
+
+def add_relu(a, r, link=None):
+    return _AddRelu.apply(a, r, link)
+
+
+def space_to_batch_raw(x, f, inverse=False):
+    """x (N, C, H, W) -> (N*f*f, C, H/f, W/f) phase-major (inverse: the way back)."""
+    lib = _lib.load()
+    x = nhwc(x)
+    _require(x, "space_to_batch input")
+    n, c, h, w = x.shape
+    out = empty_nhwc(n // (f * f), c, h * f, w * f, x) if inverse else empty_nhwc(n * f * f, c, h // f, w // f, x)
+    if inverse:
+        if n % (f * f):
+            raise RuntimeError("munit_amd.batch_to_space: batch %d is not a multiple of %d" % (n, f * f))
+        _lib.check(lib.munit_space_to_batch(_p(x), _p(out), n // (f * f), h * f, w * f, c, f, 1, _stream()), "batch_to_space")
+    else:
+        _lib.check(lib.munit_space_to_batch(_p(x), _p(out), n, h, w, c, f, 0, _stream()), "space_to_batch")
+    return out
+
+
+class _SpaceToBatch(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, x, f, inverse):
+        ctx.cfg = (f, inverse)
+        return space_to_batch_raw(x, f, inverse)
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        f, inverse = ctx.cfg
+        return space_to_batch_raw(dy, f, not inverse), None, None
+
+
+def space_to_batch(x, f, inverse=False):
+    return _SpaceToBatch.apply(x, f, inverse)
+
+
+def _seg_head_args(logits, labels, mask, scale):
+    logits = nhwc(logits)
+    _require(logits, "segmentation logits")
+    b, k, h, w = logits.shape
+    if k != 19:
+        raise RuntimeError("munit_amd.seg head: 19 classes expected, got %d" % k)
+    if labels.dtype != torch.int32 or tuple(labels.shape) != (b, h * scale, w * scale) or not labels.is_contiguous():
+        raise RuntimeError("munit_amd.seg head: labels must be contiguous int32 (%d, %d, %d)" % (b, h * scale, w * scale))
+    if mask is not None:
+        _require(mask, "segmentation mask")
+        if mask.numel() != b * h * scale * w * scale or not mask.is_contiguous():
+            raise RuntimeError("munit_amd.seg head: mask must hold one contiguous value per pixel")
+    _same_device(logits, labels, mask)
+    return logits, b, h, w
+
+
+class _SegCE(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, logits, labels, mask, scale, norm):
+        lib = _lib.load()
+        logits, b, h, w = _seg_head_args(logits, labels, mask, scale)
+        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
+        out = torch.empty((), device=logits.device, dtype=torch.float32)
+        _lib.check(lib.munit_seg_ce_fwd(_p(logits), _p(labels), _p(mask), b, h, w, scale, c_float(norm), _p(out), _p(ws),
+                                        ws.numel(), _stream()), "seg_ce_fwd")
+        ctx.cfg = (scale, norm)
+        ctx.save_for_backward(logits, labels, mask)
+        return out
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, gout):
+        lib = _lib.load()
+        logits, labels, mask = ctx.saved_tensors
+        scale, norm = ctx.cfg
+        b, _, h, w = logits.shape
+        gout = gout.contiguous()
+        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
+        dl = torch.empty_like(logits)
+        _lib.check(lib.munit_seg_ce_bwd(_p(logits), _p(labels), _p(mask), b, h, w, scale, c_float(norm), _p(gout), _p(dl),
+                                        _p(ws), ws.numel(), _stream()), "seg_ce_bwd")
+        return dl, None, None, None, None
+
+
+def seg_cross_entropy(logits, labels, mask=None, scale=8, norm=None):
+    """nn.CrossEntropyLoss of the bilinearly up-sampled logits (trainer.py:746-771): the masked 20-class form when `mask`
+    (one 0/1 value per output pixel) is given, else the plain 19-class one.  Sum of the pixel losses / norm (default:
+    all pixels, i.e. the mean)."""
+    if norm is None:
+        norm = labels.numel()
+    return _SegCE.apply(logits, labels, mask, int(scale), float(norm))
+
+
+def seg_labels(logits, scale=8):
+    """argmax over the 19 up-sampled logits, int32 (B, H, W) (first maximal class on ties)."""
+    lib = _lib.load()
+    logits = nhwc(logits)
+    _require(logits, "segmentation logits")
+    b, k, h, w = logits.shape
+    if k != 19:
+        raise RuntimeError("munit_amd.seg_labels: 19 classes expected, got %d" % k)
+    with _on(logits):
+        labels = torch.empty((b, h * scale, w * scale), dtype=torch.int32, device=logits.device)
+        _lib.check(lib.munit_seg_labels(_p(logits), b, h, w, scale, _p(labels), _stream()), "seg_labels")
+    if SEG_SINK is not None:
+        SEG_SINK.append(labels)
+    return labels

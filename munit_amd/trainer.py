@@ -15,8 +15,9 @@ What is different underneath (none of it changes results beyond fp32 rounding):
     inside dis_update (x_ba / x_ab are detached at trainer.py:1178-1179);
   * loss scalars stay on the device; nothing synchronises the host inside an update.
 
-Aux losses outside the AdaINGen + MsImageDis path (VGG, semantic segmentation, domain
-classifiers, synthetic pairs) raise NotImplementedError when their weight is non-zero.
+The semantic-consistency loss (semantic_w > 0 with a semantic_ckpt_path) runs the user's frozen Resnet34_8s on
+the device (munit_amd/segmentation.py).  The other aux losses (VGG, domain classifiers, synthetic pairs) raise
+NotImplementedError when their weight is non-zero.
 """
 import os
 import warnings
@@ -27,7 +28,8 @@ from torch.optim import Optimizer
 
 from . import ops
 from .networks import AdaINGen, AdaINGen_double, ContentEncoder, InstanceNorm2d, MsImageDis, _ApplyRefreshesImages
-from .utils import get_model_list, get_scheduler, normalize_config, weights_init
+from .segmentation import colorize, seg_loss
+from .utils import get_model_list, get_scheduler, load_segmentation_model, normalize_config, weights_init
 
 
 class FusedAdam(Optimizer):
@@ -475,6 +477,12 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.dis_a.apply(weights_init("gaussian"))
         self.dis_b.apply(weights_init("gaussian"))
 
+        # semantic-consistency loss (trainer.py:136-142): the user's Resnet34_8s checkpoint, frozen, in eval mode
+        self.segmentation_model = None
+        if self.semantic_w:
+            self._check_semantic(hyperparameters)
+            self.segmentation_model = load_segmentation_model(hyperparameters["semantic_ckpt_path"], 19)
+
         self._consts = {}
         # deferred discriminator exchange + step (data parallel, _defer_dis_step)
         self._dis_pending, self._dis_event, self._dis_waited = None, None, set()
@@ -489,8 +497,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         bad = []
         if hp.get("vgg_w", 0) > 0:
             bad.append("vgg_w")
-        if hp.get("semantic_w", 0) > 0:
-            bad.append("semantic_w")
+        if hp.get("semantic_w", 0) > 0 and not hp.get("semantic_ckpt_path"):
+            bad.append("semantic_w (without a semantic_ckpt_path)")
         if hp.get("domain_adv_w", 0) > 0:
             bad.append("domain_adv_w")
         for k in ("adv_lambda", "dfeat_lambda", "sem_seg_lambda", "output_classifier_lambda", "output_adv_lambda"):
@@ -500,6 +508,32 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             raise NotImplementedError(
                 "munit_amd covers the AdaINGen + MsImageDis training step only; set these weights to 0 "
                 "(they need external checkpoints / models outside the hot path): " + ", ".join(bad))
+
+    @staticmethod
+    def _check_semantic(hp):
+        if hp.get("precision", "f32") != "f32":
+            raise NotImplementedError("munit_amd: semantic_w > 0 runs in fp32 only (precision %r)" % hp["precision"])
+        h, w = hp["crop_image_height"], hp["crop_image_width"]
+        if h != w:
+            raise ValueError("munit_amd: semantic_w > 0 needs a square crop (the reference resizes the mask to "
+                             "(crop_image_height, crop_image_height)); got %dx%d" % (h, w))
+        if h % 32:
+            raise ValueError("munit_amd: semantic_w > 0 needs a crop that is a multiple of 32 (the segmentation network's "
+                             "1/8-resolution features split into 4 x 4 phases); got %d" % h)
+
+    def _semantic_loss(self, x_a, x_b, x_ab, x_ba, mask_a, mask_b):
+        """seg(x_a, x_ab, mask_a) + seg(x_b, x_ba, mask_b) (trainer.py:504-509) as one pass over each image pair."""
+        mask = None
+        if not self.full_adaptation and (mask_a is not None or mask_b is not None):
+            if mask_a is None or mask_b is None:
+                raise ValueError("munit_amd: the masked semantic loss needs both mask_a and mask_b")
+            for m in (mask_a, mask_b):
+                if m.dim() != 4 or m.shape[1] != 1 or m.shape[2:] != x_a.shape[2:]:
+                    raise ValueError("munit_amd: semantic-loss masks must be (B, 1, H, W) at the image size %s, got %s"
+                                     % (tuple(x_a.shape[2:]), tuple(m.shape)))
+            mask = torch.cat([mask_a.float(), mask_b.float()]).contiguous()
+        loss, _ = seg_loss(self.segmentation_model, [x_a, x_b], [x_ab, x_ba], mask)
+        return loss
 
     def _bind(self, device):
         self.dis_opt.bind(device)
@@ -612,6 +646,9 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         hp = hyperparameters
         if synth and hp.get("recon_synth_w", 0) > 0:
             raise NotImplementedError("munit_amd: synthetic-pair reconstruction loss is outside the hot path")
+        if semantic_gt_a is not None or semantic_gt_b is not None:
+            raise NotImplementedError("munit_amd: the semantic loss against a synthetic ground truth (semantic_gt_a / "
+                                      "semantic_gt_b, merge_classes) is outside the hot path; only pseudo-labels are built")
         self._check_aux(normalize_config(hp))
         self.gen_opt.zero_grad()
         # the reference draws these even when guided == 1 leaves them unused (trainer.py:366-367)
@@ -699,11 +736,15 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             br.join(self.loss_gen_recon_x_a, self.loss_gen_recon_x_b, self.loss_gen_recon_s_a, self.loss_gen_recon_s_b,
                     self.loss_gen_recon_c_a, self.loss_gen_recon_c_b, self.loss_gen_cycrecon_x_a,
                     self.loss_gen_cycrecon_x_b, self.loss_gen_adv_a, self.loss_gen_adv_b)
+            self.loss_sem_seg = 0
+            if self.semantic_w:
+                br.join(x_ab, x_ba)
+                self.loss_sem_seg = self._semantic_loss(x_a, x_b, x_ab, x_ba, mask_a, mask_b)
         finally:
             for p in d_params:
                 p.requires_grad_(True)
         self.loss_gen_vgg_a = self.loss_gen_vgg_b = 0
-        self.loss_sem_seg = self.domain_adv_loss = self.loss_classifier_sr = self.loss_output_classifier_sr = 0
+        self.domain_adv_loss = self.loss_classifier_sr = self.loss_output_classifier_sr = 0
 
         pairs = [(hp["gan_w"], self.loss_gen_adv_a), (hp["gan_w"], self.loss_gen_adv_b),
                  (hp["recon_x_w"], self.loss_gen_recon_x_a), (hp["recon_s_w"], self.loss_gen_recon_s_a),
@@ -712,6 +753,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         if cyc:
             pairs += [(hp["recon_x_cyc_w"], self.loss_gen_cycrecon_x_a),
                       (hp["recon_x_cyc_w"], self.loss_gen_cycrecon_x_b)]
+        if self.semantic_w:
+            pairs.append((hp["semantic_w"], self.loss_sem_seg))
         self.loss_gen_total = ops.weighted_sum([t.detach() for _, t in pairs], [w for w, _ in pairs])
         live = [(w, t) for w, t in pairs if w != 0 and t.requires_grad]
         xch = None
@@ -739,7 +782,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self._log(comet_exp, ("loss_gen_adv_a", "loss_gen_adv_b", "loss_gen_recon_x_a", "loss_gen_recon_s_a",
                               "loss_gen_recon_c_a", "loss_gen_recon_x_b", "loss_gen_recon_s_b",
                               "loss_gen_recon_c_b", "loss_gen_cycrecon_x_a", "loss_gen_cycrecon_x_b",
-                              "loss_gen_total"))
+                              "loss_gen_total") + (("loss_sem_seg",) if self.semantic_w else ()))
 
     # ---- dis_update (trainer.py:1133-1190) ---------------------------------------------
     def dis_update(self, x_a, x_b, hyperparameters, comet_exp=None):
@@ -897,6 +940,14 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                     outs[5].append(self._dec(c_a, s_b_fake, 2))
         x_a_recon, x_b_recon, x_ba1, x_ba2, x_ab1, x_ab2 = (torch.cat(o) for o in outs)
         self.train()
+        if self.semantic_w:
+            self.segmentation_model.eval()
+            # colour-coded label maps of the originals and the first translations (trainer.py:854-925)
+            with torch.no_grad():
+                seg = self.segmentation_model
+                rgb_a, rgb_b = colorize(ops.seg_labels(seg(x_a, x_b))).split(x_a.size(0))
+                rgb_ab, rgb_ba = colorize(ops.seg_labels(seg(x_ab1, x_ba1))).split(x_a.size(0))
+            return x_a, x_a_recon, rgb_a, x_ab1, rgb_ab, x_ab2, x_b, x_b_recon, rgb_b, x_ba1, rgb_ba, x_ba2
         return x_a, x_a_recon, x_ab1, x_ab2, x_b, x_b_recon, x_ba1, x_ba2
 
     def sample_syn(self, x_a, x_b):

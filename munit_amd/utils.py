@@ -95,3 +95,9 @@ def get_model_list(dirname, key):
     names = sorted(n for n in os.listdir(dirname)
                    if key in n and ".pt" in n and os.path.isfile(os.path.join(dirname, n)))
     return os.path.join(dirname, names[-1]) if names else None
+
+
+def load_segmentation_model(ckpt_path, classes):
+    """utils.py:974-983 under the reference's name (munit_amd/segmentation.py)."""
+    from .segmentation import load_segmentation_model as load
+    return load(ckpt_path, classes)
