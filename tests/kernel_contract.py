@@ -13,7 +13,12 @@ short is refused with every output still holding its poison.  Per entry point:
   * losses: da / db == NULL; munit_weighted_sum at n = 1, 32 and its refusal at 33;
   * optimisers: the gradient stays intact, ExtraAdam mode 0 saves p, modes 1 / 2 leave the saved copy alone, a buffer
     that is not 16-byte aligned is refused by Adam;
-  * munit_scale: accumulate 0 into NaN, 1 into a live buffer; munit_act_bwd: all four codes."""
+  * munit_scale: accumulate 0 into NaN, 1 into a live buffer; munit_act_bwd: all four codes;
+  * the segmentation kernels (seg.hip; tests/test_gpu_semantic.py runs these): munit_seg_ce_fwd and _bwd each refuse a
+    workspace one byte short of their OWN need, munit_seg_ce_workspace_bytes covers both, the loss does not depend on what
+    the workspace held; the max-pool's uint8 winner plane is guarded, every entry in 0..8 and in bounds; every refusal the
+    code states (x == y, H % f, W % f, inverse, n % 4, null pointers, norm <= 0, the 2^40 size limit) leaves every output
+    untouched."""
 import ctypes
 from ctypes import c_double, c_float, c_size_t, c_void_p
 
@@ -530,3 +535,211 @@ def check_image(B, out_h, out_w):
         assert rc == ERR_WORKSPACE, (what, label, rc)
         assert holds_poison(a.view(o, torch.float32)), "%s: %s written before the workspace refusal" % (what, label)
         L.verify(label + " one byte short (refused)")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the frozen segmentation network's kernels (munit_amd/csrc/seg.hip)
+# ------------------------------------------------------------------------------------------------------------------------
+SEG_GRID_CAP = 16384 * 256            # seg.hip: grid-stride loops of at most 16384 blocks of 256 threads
+NCLS = 19
+HEAD_LIMIT = 1 << 40
+
+
+def _refusals(a, inputs, what, outs, calls, code=ERR_ARG):
+    """Every (label, call) must be refused with `code` before anything is written."""
+    L = Launches(a, inputs, what)
+    for label, call in calls:
+        for o in outs:
+            poison(a.view(o, torch.float32), 0)
+        refused(L, call(), outs, label, code=code)
+
+
+def check_seg_input(npix):
+    lib = _lib.load()
+    n = 3 * npix
+    what = "seg_input npix=%d" % npix
+    a = _plain(dict(x=n * 4, dy=n * 4, y=n * 4, dx=n * 4), ["x", "dy"], ["y", "dx"], what,
+               lambda a: [("fwd", lambda: lib.munit_seg_input_fwd(_p(a, "x"), _p(a, "y"), c_size_t(npix), stream()), ["y"]),
+                          ("bwd", lambda: lib.munit_seg_input_bwd(_p(a, "dy"), _p(a, "dx"), c_size_t(npix), stream()), ["dx"])])
+    _refusals(a, ["x", "dy"], what, ["y", "dx"],
+              [("fwd, x = NULL", lambda: lib.munit_seg_input_fwd(None, _p(a, "y"), c_size_t(npix), stream())),
+               ("fwd, y = NULL", lambda: lib.munit_seg_input_fwd(_p(a, "x"), None, c_size_t(npix), stream())),
+               ("bwd, dy = NULL", lambda: lib.munit_seg_input_bwd(None, _p(a, "dx"), c_size_t(npix), stream())),
+               ("bwd, dx = NULL", lambda: lib.munit_seg_input_bwd(_p(a, "dy"), None, c_size_t(npix), stream()))])
+
+
+def check_space_to_batch(N, H, W, C, f):
+    lib = _lib.load()
+    n = N * H * W * C
+    what = "space_to_batch %s" % ((N, H, W, C, f),)
+
+    def s2b(a, src, dst, inv, h=H, w=W, ff=f):
+        return lib.munit_space_to_batch(_p(a, src) if src else None, _p(a, dst) if dst else None, N, h, w, C, ff, inv, stream())
+
+    a = _plain(dict(x=n * 4, y=n * 4, back=n * 4), ["x"], ["y", "back"], what,
+               lambda a: [("split", lambda: s2b(a, "x", "y", 0), ["y"]), ("inverse", lambda: s2b(a, "y", "back", 1), ["back"])])
+    assert torch.equal(a.bytes("back"), a.bytes("x")), what + ": the inverse does not restore the input"
+    calls = [("x == y", lambda: s2b(a, "y", "y", 0)), ("inverse = 2", lambda: s2b(a, "x", "y", 2)),
+             ("inverse = -1", lambda: s2b(a, "x", "y", -1)), ("x = NULL", lambda: s2b(a, None, "y", 0)),
+             ("y = NULL", lambda: s2b(a, "x", None, 0)), ("f = 0", lambda: s2b(a, "x", "y", 0, ff=0))]
+    if f > 1:
+        calls += [("H % f", lambda: s2b(a, "x", "y", 0, h=H - 1)), ("W % f", lambda: s2b(a, "x", "y", 1, w=W - 1))]
+    keep = a.bytes("y").clone()
+    L = Launches(a, ["x"], what)
+    for label, call in calls:
+        poison(a.view("back", torch.float32), 0)
+        refused(L, call(), ["back"], label, code=ERR_ARG)
+        assert torch.equal(a.bytes("y"), keep), "%s %s: y written before the refusal" % (what, label)
+
+
+def check_seg_maxpool(B, H, W, C):
+    """munit_maxpool3s2_{fwd,bwd}: the uint8 winner plane is guarded like every tensor, prefilled with two out-of-range
+    byte values, and every entry must come back in 0..8 naming an in-bounds element."""
+    lib = _lib.load()
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    nx, ny = B * H * W * C, B * Ho * Wo * C
+    what = "maxpool3s2 %s" % ((B, H, W, C),)
+    a = Arena(dict(x=nx * 4, dy=ny * 4, y=ny * 4, idx=ny, dx=nx * 4), _dev())
+    _outs(a, y=4, dx=4)
+    fill_random(a.view("x", torch.float32), 111)
+    a.view("x", torch.float32).sub_(3.0)                # mostly negative: the zero padding must not win
+    fill_random(a.view("dy", torch.float32), 112)
+    L = Launches(a, ["x", "dy"], what)
+
+    def f(x="x", y="y", idx="idx", b=B):
+        return lib.munit_maxpool3s2_fwd(_p(a, x) if x else None, _p(a, y) if y else None, _p(a, idx) if idx else None, b, H,
+                                        W, C, stream())
+
+    def bw(dy="dy", idx="idx", dx="dx", c=C):
+        return lib.munit_maxpool3s2_bwd(_p(a, dy) if dy else None, _p(a, idx) if idx else None, _p(a, dx) if dx else None, B,
+                                        H, W, c, stream())
+
+    res = []
+    for k in (0, 1):
+        poison(a.view("y", torch.float32), k)
+        a.bytes("idx").fill_(0xE0 + k)
+        L.after(f(), "fwd, payload %d" % k)
+        assert no_nan(a.view("y", torch.float32)), what + " fwd: NaN in y"
+        res.append((a.bytes("y").clone(), a.bytes("idx").clone()))
+    assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]), what + " fwd: two runs differ"
+    win = a.bytes("idx").view(B, Ho, Wo, C).long()
+    assert int(win.max()) <= 8, what + " fwd: a winner outside 0..8 (an entry not written)"
+    row = 2 * torch.arange(Ho, device=win.device).view(1, Ho, 1, 1) - 1 + win // 3
+    col = 2 * torch.arange(Wo, device=win.device).view(1, 1, Wo, 1) - 1 + win % 3
+    assert bool(((row >= 0) & (row < H) & (col >= 0) & (col < W)).all()), what + " fwd: a winner outside the image"
+    x = a.view("x", torch.float32).view(B, H, W, C)
+    bi = torch.arange(B, device=win.device).view(B, 1, 1, 1).expand_as(win)
+    ci = torch.arange(C, device=win.device).view(1, 1, 1, C).expand_as(win)
+    assert torch.equal(x[bi, row, col, ci], a.view("y", torch.float32).view(B, Ho, Wo, C)), what + " fwd: y is not the winner"
+    L.inputs["idx"] = a.bytes("idx").clone()
+    res = []
+    for k in (0, 1):
+        poison(a.view("dx", torch.float32), k)
+        L.after(bw(), "bwd, payload %d" % k)
+        assert no_nan(a.view("dx", torch.float32)), what + " bwd: NaN in dx"
+        res.append(a.bytes("dx").clone())
+    assert torch.equal(res[0], res[1]), what + " bwd: two runs differ"
+    for label, call in (("fwd, x = NULL", lambda: f(x=None)), ("fwd, y = NULL", lambda: f(y=None)),
+                        ("fwd, idx = NULL", lambda: f(idx=None)), ("fwd, B = 0", lambda: f(b=0)),
+                        ("bwd, dy = NULL", lambda: bw(dy=None)), ("bwd, idx = NULL", lambda: bw(idx=None)),
+                        ("bwd, dx = NULL", lambda: bw(dx=None)), ("bwd, C = 0", lambda: bw(c=0))):
+        poison(a.view("y", torch.float32), 0)
+        poison(a.view("dx", torch.float32), 0)
+        refused(L, call(), ["y", "dx"], label, code=ERR_ARG)
+
+
+def check_add_relu(n):
+    lib = _lib.load()
+    what = "add_relu n=%d" % n
+
+    def f(a, x="a", r="r", y="y", m=n):
+        return lib.munit_add_relu_fwd(_p(a, x) if x else None, _p(a, r) if r else None, _p(a, y) if y else None, c_size_t(m),
+                                      stream())
+
+    a = _plain(dict(a=n * 4, r=n * 4, y=n * 4), ["a", "r"], ["y"], what, lambda a: [("fwd", lambda: f(a), ["y"])])
+    s = a.view("a", torch.float32) + a.view("r", torch.float32)
+    assert torch.equal(a.view("y", torch.float32), torch.where(s > 0, s, torch.zeros_like(s))), what + ": wrong values"
+    _refusals(a, ["a", "r"], what, ["y"],
+              [("n % 4 = 1", lambda: f(a, m=n + 1)), ("n % 4 = 3", lambda: f(a, m=n - 1)), ("a = NULL", lambda: f(a, x=None)),
+               ("r = NULL", lambda: f(a, r=None)), ("y = NULL", lambda: f(a, y=None))])
+
+
+def check_seg_head(B, h, w, S, masked):
+    """munit_seg_ce_fwd / _bwd / munit_seg_labels / munit_seg_ce_workspace_bytes at (B, h, w, S)."""
+    lib = _lib.load()
+    npix = B * h * S * w * S
+    nl = B * h * w * NCLS
+    nws = lib.munit_seg_ce_workspace_bytes(B, h, w, S)
+    # Each pass's own need restates seg.hip's layout on purpose (one fp32 partial per block of grid_for(npix); the gradient
+    # at the up-sampled resolution): the header has one query for both passes, so "one byte short of its own need" can only
+    # be probed this way.  A change of that layout has to change these two lines with it.
+    need_f = max(1, min((npix + 255) // 256, 16384)) * 4          # one partial sum per block
+    need_b = npix * NCLS * 4                                      # the gradient at the up-sampled resolution
+    assert nws >= need_f and nws >= need_b, (nws, need_f, need_b)
+    a = Arena(dict(lg=nl * 4, labels=npix * 4, mask=npix * 4, gout=4, out=4, dl=nl * 4, lab=npix * 4, ws=nws), _dev())
+    _outs(a, out=4, dl=4, lab=4)
+    fill_random(a.view("lg", torch.float32), 121)
+    a.view("lg", torch.float32).mul_(3.0)
+    g = torch.Generator(device=_dev()).manual_seed(122)
+    a.view("labels", torch.int32).copy_(torch.randint(0, NCLS, (npix,), generator=g, device=_dev(), dtype=torch.int32))
+    a.view("mask", torch.float32).copy_((torch.rand(npix, generator=g, device=_dev()) < 0.4).float())
+    a.view("gout", torch.float32).fill_(1.5)
+    what = "seg head %s" % ((B, h, w, S, masked),)
+    L = Launches(a, ["lg", "labels", "mask", "gout"], what)
+    norm = float(npix)
+
+    def args(lg="lg", labels="labels"):
+        return (_p(a, lg) if lg else None, _p(a, labels) if labels else None, _p(a, "mask") if masked else None)
+
+    def f(nb=nws, nrm=norm, out="out", ws="ws", dims=(B, h, w, S), **kw):
+        return lib.munit_seg_ce_fwd(*args(**kw), *dims, c_float(nrm), _p(a, out) if out else None, _p(a, ws) if ws else None,
+                                    c_size_t(nb), stream())
+
+    def bw(nb=nws, nrm=norm, gout="gout", dl="dl", ws="ws", dims=(B, h, w, S), **kw):
+        return lib.munit_seg_ce_bwd(*args(**kw), *dims, c_float(nrm), _p(a, gout) if gout else None,
+                                    _p(a, dl) if dl else None, _p(a, ws) if ws else None, c_size_t(nb), stream())
+
+    def labels(lg="lg", lab="lab", dims=(B, h, w, S)):
+        return lib.munit_seg_labels(_p(a, lg) if lg else None, *dims, _p(a, lab) if lab else None, stream())
+
+    r = _two_payloads(L, f, ["out"], "fwd")
+    for fill in (0x00, 0x3F):                   # the loss does not depend on what the workspace held
+        poison(a.view("out", torch.float32), 0)
+        a.bytes("ws").fill_(fill)
+        L.after(f(), "fwd, workspace of 0x%02x bytes" % fill)
+        assert torch.equal(a.bytes("out"), r["out"]), what + ": the loss depends on the workspace's content"
+    L.after(f(need_f), "fwd, exactly its own need")
+    assert torch.equal(a.bytes("out"), r["out"])
+    _two_payloads(L, bw, ["dl"], "bwd")
+    res = []
+    for k in (0, 1):
+        poison(a.view("lab", torch.float32), k)
+        L.after(labels(), "labels, payload %d" % k)
+        lab = a.view("lab", torch.int32)
+        assert int(lab.min()) >= 0 and int(lab.max()) < NCLS, what + ": a label outside 0..18 (an entry not written)"
+        res.append(a.bytes("lab").clone())
+    assert torch.equal(res[0], res[1]), what + ": two label runs differ"
+
+    def refuse(call, label, code=ERR_ARG):
+        for o in ("out", "dl", "lab"):
+            poison(a.view(o, torch.float32), 0)
+        a.bytes("ws").fill_(GUARD_BYTE)
+        refused(L, call(), ["out", "dl", "lab"], label, code=code)
+
+    # each pass refuses a workspace one byte short of ITS OWN need
+    refuse(lambda: f(need_f - 1), "fwd, workspace one byte short", ERR_WORKSPACE)
+    refuse(lambda: bw(need_b - 1), "bwd, workspace one byte short", ERR_WORKSPACE)
+    big = (4096, 4096, 4096, 8)                 # 2^36 * 64 pixels: over the 2^40 limit; refused before any launch
+    assert big[0] * big[1] * big[2] * big[3] * big[3] * NCLS >= HEAD_LIMIT
+    for label, call in (("fwd, logits = NULL", lambda: f(lg=None)), ("fwd, labels = NULL", lambda: f(labels=None)),
+                        ("fwd, out = NULL", lambda: f(out=None)), ("fwd, ws = NULL", lambda: f(ws=None)),
+                        ("fwd, norm = 0", lambda: f(nrm=0.0)), ("fwd, norm < 0", lambda: f(nrm=-1.0)),
+                        ("fwd, B = 0", lambda: f(dims=(0, h, w, S))), ("fwd, S = 0", lambda: f(dims=(B, h, w, 0))),
+                        ("fwd, too large", lambda: f(dims=big)),
+                        ("bwd, logits = NULL", lambda: bw(lg=None)), ("bwd, labels = NULL", lambda: bw(labels=None)),
+                        ("bwd, gout = NULL", lambda: bw(gout=None)), ("bwd, dlogits = NULL", lambda: bw(dl=None)),
+                        ("bwd, ws = NULL", lambda: bw(ws=None)), ("bwd, norm = 0", lambda: bw(nrm=0.0)),
+                        ("bwd, h = 0", lambda: bw(dims=(B, 0, w, S))), ("bwd, too large", lambda: bw(dims=big)),
+                        ("labels, logits = NULL", lambda: labels(lg=None)), ("labels, labels = NULL", lambda: labels(lab=None)),
+                        ("labels, w = 0", lambda: labels(dims=(B, h, 0, S))), ("labels, too large", lambda: labels(dims=big))):
+        refuse(call, label)

@@ -8,7 +8,13 @@ hooks on O.conv_block / O.upsample2 / the 1x1 heads / the MLP linears) for every
 configs/config_256.yaml's networks at several crops, batches and padding modes, asks the library which kernel carries each
 pass (munit_conv2d_kernel_name mirrors the dispatch of the entry points), and requires each (pass, kernel) pair to be one
 that an op test runs.  It also requires every kernel name the dispatch can return to be covered, so that a new branch
-cannot land without an op test, and pins the kernel names of the cases added for that purpose (CONV_CASES_TARGETS)."""
+cannot land without an op test, and pins the kernel names of the cases added for that purpose (CONV_CASES_TARGETS).
+
+The frozen Resnet34_8s of the semantic loss (tests/seg_layers.py lists its 37 convolutions from the module itself) is a
+second production grid: every square crop that is a multiple of 32 from 64 to 512, B and 2B images.  Its layers differ
+from the generators' by zero padding, a bias, the zero-extended backward-data filter of the stride-2 layers and the `add`
+operand, so a layer counts as covered only by a case of tests/test_gpu_semantic.py::SEG_CONV_CASES (run through
+ops.frozen_conv) that has the layer's channels, filter and stride and takes the same (pass, kernel name)."""
 import json
 import os
 import re
@@ -27,6 +33,7 @@ BATCHES = (1, 2, 3, 4, 8, 16, 32)
 CROPS_256 = (64, 96, 128, 192, 256, 384, 512, (256, 512), (360, 480))
 # reachable only with a MUNIT_DEBUG_* switch set (MUNIT_DEBUG_NO_WGRAD_PK): the op tests never force a debug fallback
 DEBUG_ONLY = {"conv_lanes_wgrad_kernel"}
+SEG_CROPS = tuple(range(64, 513, 32))
 
 
 @pytest.fixture(scope="module")
@@ -277,3 +284,106 @@ def test_layer_enumeration_matches_the_parameter_list():
     drec = _trace(lambda: O.dis_forward(_meta_state(dshapes), "", x, hp["dis"]))
     assert len(drec) == sum(1 for k in dshapes if k.endswith("weight")) == 15
     assert [l[8] for l in drec if l[2] == 1] == [6, 3, 1]          # the heads of the three scales (96, 48, 24 pixels in)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the frozen segmentation network
+# ------------------------------------------------------------------------------------------------------------------
+def seg_case(c, which):
+    """Op-case tuple of pass `which` (0 forward, 1 backward-data) of a SEG_CONV_CASES entry (cin, cout, k, stride, pad,
+    act, B, H, W): backward-data of a stride-2 odd kernel multiplies by the filter zero-extended to the next even size."""
+    cin, cout, k, stride, pad, act, b, h, w = c
+    if which == 0:
+        return (cin, cout, k, stride, pad, "zero", 0, act, b, h, w)
+    return (cin, cout, k + (k % 2 if stride == 2 else 0), stride, pad, "zero", 0, "none", b, h, w)
+
+
+def seg_key(lib, case, which):
+    """(pass, kernel name, cin, cout, filter, stride) of an op-case tuple"""
+    return (which, kernel_names(lib, case)[which]) + case[:4]
+
+
+def seg_production_cases():
+    """{(pass, op case): label} of the frozen network over SEG_CROPS x (B, 2B images for B in BATCHES)."""
+    from tests import seg_layers as SL
+    cases = {}
+    for crop in SEG_CROPS:
+        for n in sorted({m * b for b in BATCHES for m in (1, 2)}):
+            for l in SL.seg_layers(crop, n):
+                label = "%s, crop %d, %d images" % (l.name, crop, n)
+                cases.setdefault((0, l.case), label)
+                cases.setdefault((1, SL.dgrad_case(l)), label)
+    return cases
+
+
+def seg_covered(lib, cases):
+    return {seg_key(lib, seg_case(c, p), p) for c in cases for p in (0, 1)}
+
+
+def seg_missing(lib, cases, prod):
+    """`prod`: seg_production_cases(), built once by the caller (195 traces of the network)."""
+    cov = seg_covered(lib, cases)
+    missing = {}
+    for (p, case), label in prod.items():
+        key = seg_key(lib, case, p)
+        if key not in cov:
+            best = missing.get(key)
+            if best is None or macs(case) < macs(best[0]):
+                missing[key] = (case, label)
+    return missing
+
+
+def test_every_segmentation_conv_form_is_covered_by_a_segmentation_op_case(lib):
+    from tests.test_gpu_semantic import SEG_CONV_CASES
+    prod = seg_production_cases()
+    assert len(prod) > 1000, len(prod)
+    missing = seg_missing(lib, SEG_CONV_CASES, prod)
+    assert not missing, ("kernel forms the frozen Resnet34_8s dispatches to that no SEG_CONV_CASES entry of the same "
+                         "channels / filter / stride runs (cheapest layer of each):\n" + "\n".join(
+                             "  %s %s: %s  (%s, %.2f GMAC)" % (PASSES[k[0]], k[1], c, lab, macs(c) / 1e9)
+                             for k, (c, lab) in sorted(missing.items())))
+    # the generator op cases alone leave the network's forms open (the LDS-patch fold backward-data of layer4 at crop 96
+    # among them): the grid above is not vacuous
+    open_ = seg_missing(lib, [], prod)
+    assert any(k[:2] == (1, "conv_igemm_kernel<.., 2, 3> (LDS-patch fold)") and "crop 96" in lab and k[3] == 512
+               for k, (c, lab) in open_.items()), sorted(open_)
+
+
+def test_segmentation_cases_keep_their_kernels(lib):
+    """Every SEG_CONV_CASES entry pins the (forward, backward-data) kernels it was added for."""
+    from tests.test_gpu_semantic import SEG_CONV_CASES, SEG_CONV_CASES_TARGETS
+    assert set(SEG_CONV_CASES_TARGETS) == set(SEG_CONV_CASES) and len(set(SEG_CONV_CASES)) == len(SEG_CONV_CASES)
+    for c, want in SEG_CONV_CASES_TARGETS.items():
+        got = tuple(kernel_names(lib, seg_case(c, p))[p] for p in (0, 1))
+        assert got == want, (c, got, want)
+
+
+def test_segmentation_layer_list_matches_the_state_dict():
+    """One record per conv weight of the state dict (36 + fc), named after it, with the weight's shape; the stride-2 odd
+    kernels carry the even backward-data filter; each block's first convolution takes the skip gradient as `add`, each
+    downsample parks its dx."""
+    from munit_amd.segmentation import Resnet34_8s
+    from tests import seg_layers as SL
+    with torch.device("meta"):
+        sd = Resnet34_8s().state_dict()
+    convs = {k[len("resnet34_8s."):-len(".weight")]: tuple(v.shape) for k, v in sd.items() if v.dim() == 4}
+    assert len(convs) == 37
+    for crop, n in ((64, 1), (96, 2), (512, 64)):
+        layers, batches = SL.trace(crop, n)
+        assert batches == [4 * n, 16 * n, 4 * n, n]
+        assert len(layers) == 37 and len({l.name for l in layers}) == 37
+        for l in layers:
+            cin, cout, k, stride, pad, pt, ups, act, b, h, w = l.case
+            key = l.name.replace(".downsample", ".downsample.0")
+            assert convs[key] == (cout, cin, k, k), (l, convs[key])
+            assert l.bias and pt == "zero" and not ups and h == w
+            assert l.kd == (k + 1 if stride == 2 else k)
+            assert l.add == (l.name.endswith(".conv1") and l.name != "conv1")
+            assert l.parked == l.name.endswith(".downsample")
+            assert act == ("relu" if l.name.endswith("conv1") else "none")
+        by = {l.name: l.case for l in layers}
+        assert by["conv1"][8:] == (n, crop, crop) and by["layer1.0.conv1"][8:] == (n, crop // 4, crop // 4)
+        assert by["layer2.3.conv2"][8:] == (n, crop // 8, crop // 8)
+        assert by["layer3.0.conv1"][8:] == (4 * n, crop // 16, crop // 16)
+        assert by["layer4.2.conv2"][8:] == by["fc"][8:] == (16 * n, crop // 32, crop // 32)
+        assert [l.name for l in layers if l.case[3] == 2] == ["conv1", "layer2.0.conv1", "layer2.0.downsample"]

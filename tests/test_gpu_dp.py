@@ -185,6 +185,117 @@ def test_two_rank_step_matches_the_oracle_on_the_joint_batch(tmp_path):
           (gc.worst_max, gc.worst_l2, gc.median))
 
 
+def _semantic_hp(ckpt, batch):
+    import bench
+    hp = bench.bench_hp(SIZE, batch)
+    hp["semantic_w"] = 3
+    hp["semantic_ckpt_path"] = ckpt
+    return hp
+
+
+def _semantic_worker(rank, world, tmpdir, ckpt, no_overlap):
+    if no_overlap:                                  # read once, when munit_amd.trainer is imported (a fresh process here)
+        os.environ["MUNIT_NO_OVERLAP_EXCHANGE"] = "1"
+    else:
+        os.environ.pop("MUNIT_NO_OVERLAP_EXCHANGE", None)
+    import torch.distributed as dist
+    sys.path.insert(0, ROOT)
+    import bench
+    from munit_amd import trainer as T
+    assert T.OVERLAP_EXCHANGE == (not no_overlap)
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", init_method="file://" + os.path.join(tmpdir, "rdzv%d" % no_overlap), rank=rank,
+                            world_size=world)
+    dev = torch.device("cuda:0")
+    hp = _semantic_hp(ckpt, B)
+    batch = tuple(t.to(dev) for t in bench.make_batch(B, SIZE, rank))
+    torch.manual_seed(1234)
+    tr = T.MUNIT_Trainer(dict(hp))
+    tr.to(dev)
+    assert tr.segmentation_model is not None
+    g_dis, g_gen, dis_p, _ = _step(tr, hp, batch)
+    if no_overlap:
+        assert tr.last_exchange is None and tr._dis_pending is None
+        fired = []
+    else:
+        stages = tr.last_exchange.stages
+        assert len(stages) == 2 and all(st["fired"] for st in stages), stages
+        assert stages[0]["ranges"] == [tuple(r) for r in tr._early_ranges]
+        assert stages[1]["ranges"] == [tuple(r) for r in tr._trunk_ranges]
+        fired = [bool(st["fired"]) for st in stages]
+    torch.save({"g_gen": g_gen, "g_dis": g_dis, "dis_p": dis_p, "fired": fired, "loss_sem_seg": float(tr.loss_sem_seg.detach()),
+                "gen_p": tr.gen_opt.flat_p.detach().cpu().clone()}, os.path.join(tmpdir, "sem%d_rank%d.pt" % (no_overlap, rank)))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_two_rank_step_with_semantic_loss_is_the_mean_of_the_single_rank_steps(tmp_path):
+    """semantic_w: 3 under data-parallel: the staged gradient exchange is armed on tensors whose gradients have one more
+    contributor (the frozen segmentation network's backward into both decoders).  Two gloo ranks on one GPU, half-batches;
+    the all-reduced flat generator gradient must be the mean of the gradients two single processes compute on the same
+    half-batches (with the discriminator weights the ranks stepped to), per tensor by tests/parity.GradCheck's pinned
+    bounds (5e-5 max and L2, median 1e-5; every sample takes the same branches on both sides, so no kink is in play).
+    Once with the overlapped exchange, both stages reported as fired, and once with MUNIT_NO_OVERLAP_EXCHANGE=1: the two
+    give bitwise the same averaged gradients and weights."""
+    import torch.multiprocessing as mp
+    import bench
+    from munit_amd.trainer import MUNIT_Trainer
+    from tests import semantic_oracle as S
+    from tests.parity import GradCheck, trainer_named_params
+    ckpt = str(tmp_path / "seg.pth")
+    torch.save({k: v.cpu() for k, v in S.make_model(0).state_dict().items()}, ckpt)
+    runs = {}
+    for no_overlap in (0, 1):
+        mp.spawn(_semantic_worker, args=(2, str(tmp_path), ckpt, no_overlap), nprocs=2, join=True)
+        r = [torch.load(tmp_path / ("sem%d_rank%d.pt" % (no_overlap, k)), weights_only=True) for k in range(2)]
+        for key in ("g_gen", "g_dis", "dis_p", "gen_p"):
+            assert torch.equal(r[0][key], r[1][key]), (no_overlap, key)
+        assert r[0]["fired"] == r[1]["fired"] == ([] if no_overlap else [True, True])
+        runs[no_overlap] = r
+    for key in ("g_gen", "g_dis", "dis_p", "gen_p"):         # staged and serial exchange: the same bits
+        assert torch.equal(runs[0][0][key], runs[1][0][key]), key
+
+    dev = torch.device("cuda:0")
+    hp = _semantic_hp(ckpt, B)
+    dp = runs[0]
+    single = []
+    for rank in range(2):
+        x_a, x_b, m_a, m_b = (t.to(dev) for t in bench.make_batch(B, SIZE, rank))
+        torch.manual_seed(1234)
+        tr = MUNIT_Trainer(dict(hp))
+        tr.to(dev)
+        torch.manual_seed(11)
+        tr.update_learning_rate()
+        tr.dis_update(x_a, x_b, hp)
+        torch.cuda.synchronize()
+        with torch.no_grad():                        # gen_update on the discriminators the ranks stepped to
+            tr.dis_opt.flat_p.copy_(dp[0]["dis_p"].to(dev))
+            tr.dis_opt.invalidate_prepared()
+        tr.gen_update(x_a, x_b, hp, m_a, m_b)
+        torch.cuda.synchronize()
+        assert tr.last_exchange is None
+        sem = float(tr.loss_sem_seg.detach())
+        assert sem > 0 and abs(sem - dp[rank]["loss_sem_seg"]) <= 1e-6 * sem, (rank, sem, dp[rank]["loss_sem_seg"])
+        single.append(tr.gen_opt.flat_g.detach().clone())
+    mean = (single[0].double() + single[1].double()) / 2
+    gnames, _ = trainer_named_params(tr)
+    tr.gen_opt.flat_g.copy_(dp[0]["g_gen"].to(dev))
+    got = [p._munit_grad.detach().double().cpu().clone() for _, p in gnames]
+    tr.gen_opt.flat_g.copy_(mean.float())
+    gc = GradCheck(pinned=True)
+    n_checked = 0
+    for (n, p), g in zip(gnames, got):
+        want = p._munit_grad.detach().double().cpu()
+        if float(want.abs().max()) < 1e-7:           # conv bias ahead of an instance norm: mathematically zero
+            continue
+        gc.add("gen." + n, g, want)
+        n_checked += 1
+    gc.finish()
+    assert n_checked >= 80
+    print("two ranks with semantic_w 3 vs the mean of the single-rank gradients: worst max %.2e, worst L2 %.2e, median %.2e"
+          % (gc.worst_max, gc.worst_l2, gc.median))
+
+
 _NCCL_WORKER = r"""
 import os, sys, json, torch, torch.distributed as dist
 sys.path.insert(0, %(root)r)
