@@ -172,7 +172,10 @@ int munit_linear_bwd(const float* x, const float* w, const float* dy, float* dx,
 double munit_conv2d_executed_flops(const munit_conv_desc* d, int pass);
 /* Name, as rocprofv3 shows it, of the kernel (or kernel group) that carries `pass` of this layer: the dispatch of the three
  * entry points stated as text.  Measurement only (bench.py picks the dominant kernel of the step by measured time and names
- * it with this). Static storage; never NULL. */
+ * it with this).  The name depends on the whole descriptor, d->compute, d->in_dtype and d->out_dtype included: the bf16-storage
+ * tiles, the bf16 backward-weight kernels and the CT = 1 / CT = 2 variants on fp32 tensors each have a name of their own, asked
+ * of the same host predicates the launches act on.  A descriptor the entry point would refuse at launch is named
+ * "refused: <reason>"; one that fails munit_conv2d_out_hw "invalid".  Static storage; never NULL. */
 const char* munit_conv2d_kernel_name(const munit_conv_desc* d, int pass);
 
 /* dx = dy * act'(y) for the fused activations (y = post-activation output). n elements. */

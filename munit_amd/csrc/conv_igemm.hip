@@ -1033,20 +1033,67 @@ size_t splitk_bytes(int M, int Cout, int Ktot, int phases) {
   return ks > 1 ? align_up((size_t)ks * phases * M * Cout * sizeof(float), 256) : 0;
 }
 
+// Which conv_igemm_kernel instantiation a launch takes, or why it is refused.  launch_igemm acts on it and
+// munit_igemm_kernel_name names it: the decision is written once.
+enum IgemmForm {
+  IG_REFUSED_BF16_CIN, IG_REFUSED_CIN4_FOLD, IG_REFUSED_BF16_FOLD, IG_REFUSED_FOLD_UNALIGNED,
+  IG_CIN4,      // <bn, true, ROLE, 5>: 4-channel taps
+  IG_BF16S,     // <bn, true, ROLE, 4>: bf16 tensors, direct-to-LDS
+  IG_PATCH,     // <bn, true, 2, 3>: LDS-patch fold
+  IG_DMA,       // <bn, true, ROLE, 3>: fp32, tiles global -> LDS directly
+  IG_CT2,       // <bn, true, ROLE, 2>: f32x3
+  IG_CT1,       // <bn, true, ROLE, 1>: operands rounded to bf16 in LDS
+  IG_F32,       // <bn, true, ROLE>
+  IG_UNALIGNED  // <bn, false, ROLE>: fp32 arithmetic whatever p.ct says
+};
+IgemmForm igemm_form(const IgemmParams& p, int role) {
+  // bf16 tensors are seen as float tensors with half the channels (a tile row is 128 bytes either way)
+  if (p.bf16s && (p.Cin % (2 * BK) != 0 || NWAVES != 8)) return IG_REFUSED_BF16_CIN;
+  const int cin = p.bf16s ? p.Cin / 2 : p.Cin, w_row = p.bf16s ? p.w_row / 2 : p.w_row;
+  const bool aligned = (cin % BK == 0) && (w_row % 4 == 0);
+  if (p.cin4) return role == 2 ? IG_REFUSED_CIN4_FOLD : IG_CIN4;
+  if (p.bf16s) return role == 2 && (!p.patch || p.frame) ? IG_REFUSED_BF16_FOLD : IG_BF16S;
+  if (role == 2) {
+    if (!aligned) return IG_REFUSED_FOLD_UNALIGNED;
+    if (p.ct == 0 && p.patch && !p.frame && NWAVES == 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_PATCH")) return IG_PATCH;
+    return p.ct == 2 ? IG_CT2 : p.ct == 1 ? IG_CT1 : IG_F32;
+  }
+  if (aligned && p.ct == 0 && NWAVES == 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_DMA")) return IG_DMA;
+  if (!aligned) return IG_UNALIGNED;
+  return p.ct == 2 ? IG_CT2 : p.ct == 1 ? IG_CT1 : IG_F32;
+}
+int igemm_bn(const IgemmParams& p) { return p.Cout <= 64 ? 64 : 128; }
+
+#define IGEMM_LAUNCH(...)                                                                                  \
+  do {                                                                                                     \
+    if (bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<64, __VA_ARGS__>), grid, block, 0, st, q);         \
+    else hipLaunchKernelGGL((conv_igemm_kernel<128, __VA_ARGS__>), grid, block, 0, st, q);                 \
+  } while (0)
+
 template <int ROLE>
 int launch_igemm(const IgemmParams& p, int phases, hipStream_t st, void* slab = nullptr, size_t slab_bytes = 0) {
-  const int bn = p.Cout <= 64 ? 64 : 128;
+  const int bn = igemm_bn(p);
   IgemmParams q = p;
-  if (p.bf16s) {
-    // bf16 tensors seen as float tensors with half the channels (a tile row is 128 bytes either way)
-    if (p.Cin % (2 * BK) != 0 || NWAVES != 8) {
+  const IgemmForm form = igemm_form(p, ROLE);
+  switch (form) {
+    case IG_REFUSED_BF16_CIN:
       munit_set_error("conv_igemm: bf16 storage needs a multiple of 64 input channels (got %d)", p.Cin);
       return MUNIT_ERR_ARG;
-    }
+    case IG_REFUSED_CIN4_FOLD:
+      munit_set_error("conv_igemm: 4-channel taps are not a folded-backward-data form");
+      return MUNIT_ERR_ARG;
+    case IG_REFUSED_BF16_FOLD:
+      munit_set_error("conv_igemm: bf16-storage folded backward-data exists for the LDS-patch form only");
+      return MUNIT_ERR_ARG;
+    case IG_REFUSED_FOLD_UNALIGNED:
+      munit_set_error("conv_igemm: folded backward-data needs Cout %% 32 == 0");
+      return MUNIT_ERR_ARG;
+    default: break;
+  }
+  if (p.bf16s) {
     q.Cin = p.Cin / 2; q.Ktot = p.Ktot / 2; q.w_row = p.w_row / 2; q.w_phase = p.w_phase / 2;
     slab = nullptr;   // no split-K in this mode
   }
-  const bool aligned = (q.Cin % BK == 0) && (q.w_row % 4 == 0);
   q.n_tiles = cdiv(p.Cout, bn);
   const int m_tiles = cdiv(p.M, BM);
   q.ksplit = 1;
@@ -1061,54 +1108,19 @@ int launch_igemm(const IgemmParams& p, int phases, hipStream_t st, void* slab = 
   }
   dim3 grid((unsigned)(m_tiles * q.n_tiles), (unsigned)phases, (unsigned)q.ksplit);
   dim3 block(NTHR);
-  if (p.cin4) {
-    if constexpr (ROLE == 2) {
-      munit_set_error("conv_igemm: 4-channel taps are not a folded-backward-data form");
-      return MUNIT_ERR_ARG;
-    } else {
-      if (bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<64, true, ROLE, 5>), grid, block, 0, st, q);
-      else hipLaunchKernelGGL((conv_igemm_kernel<128, true, ROLE, 5>), grid, block, 0, st, q);
-    }
-  } else if (p.bf16s) {
-    if constexpr (ROLE == 2) {
-      if (!p.patch || p.frame) {
-        munit_set_error("conv_igemm: bf16-storage folded backward-data exists for the LDS-patch form only");
-        return MUNIT_ERR_ARG;
-      }
-    }
-    if (bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<64, true, ROLE, 4>), grid, block, 0, st, q);
-    else hipLaunchKernelGGL((conv_igemm_kernel<128, true, ROLE, 4>), grid, block, 0, st, q);
-  } else if constexpr (ROLE == 2) {
-    if (!aligned) {
-      munit_set_error("conv_igemm: folded backward-data needs Cout %% 32 == 0");
-      return MUNIT_ERR_ARG;
-    }
-    if (p.ct == 0 && p.patch && !p.frame && NWAVES == 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_PATCH")) {
-      if (bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<64, true, 2, 3>), grid, block, 0, st, q);
-      else hipLaunchKernelGGL((conv_igemm_kernel<128, true, 2, 3>), grid, block, 0, st, q);
-    } else if (bn == 64) {
-      if (p.ct == 2) hipLaunchKernelGGL((conv_igemm_kernel<64, true, 2, 2>), grid, block, 0, st, q);
-      else if (p.ct == 1) hipLaunchKernelGGL((conv_igemm_kernel<64, true, 2, 1>), grid, block, 0, st, q);
-      else hipLaunchKernelGGL((conv_igemm_kernel<64, true, 2>), grid, block, 0, st, q);
-    } else {
-      if (p.ct == 2) hipLaunchKernelGGL((conv_igemm_kernel<128, true, 2, 2>), grid, block, 0, st, q);
-      else if (p.ct == 1) hipLaunchKernelGGL((conv_igemm_kernel<128, true, 2, 1>), grid, block, 0, st, q);
-      else hipLaunchKernelGGL((conv_igemm_kernel<128, true, 2>), grid, block, 0, st, q);
-    }
-  } else if (aligned && p.ct == 0 && NWAVES == 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_DMA")) {
-    // single-gather fp32 variants: tiles go global -> LDS directly
-    if (bn == 64) hipLaunchKernelGGL((conv_igemm_kernel<64, true, ROLE, 3>), grid, block, 0, st, q);
-    else hipLaunchKernelGGL((conv_igemm_kernel<128, true, ROLE, 3>), grid, block, 0, st, q);
-  } else if (bn == 64) {
-    if (aligned && p.ct == 2) hipLaunchKernelGGL((conv_igemm_kernel<64, true, ROLE, 2>), grid, block, 0, st, q);
-    else if (aligned && p.ct == 1) hipLaunchKernelGGL((conv_igemm_kernel<64, true, ROLE, 1>), grid, block, 0, st, q);
-    else if (aligned) hipLaunchKernelGGL((conv_igemm_kernel<64, true, ROLE>), grid, block, 0, st, q);
-    else hipLaunchKernelGGL((conv_igemm_kernel<64, false, ROLE>), grid, block, 0, st, q);
-  } else {
-    if (aligned && p.ct == 2) hipLaunchKernelGGL((conv_igemm_kernel<128, true, ROLE, 2>), grid, block, 0, st, q);
-    else if (aligned && p.ct == 1) hipLaunchKernelGGL((conv_igemm_kernel<128, true, ROLE, 1>), grid, block, 0, st, q);
-    else if (aligned) hipLaunchKernelGGL((conv_igemm_kernel<128, true, ROLE>), grid, block, 0, st, q);
-    else hipLaunchKernelGGL((conv_igemm_kernel<128, false, ROLE>), grid, block, 0, st, q);
+  switch (form) {
+    case IG_CIN4:
+      if constexpr (ROLE != 2) IGEMM_LAUNCH(true, ROLE, 5);
+      break;
+    case IG_BF16S: IGEMM_LAUNCH(true, ROLE, 4); break;
+    case IG_PATCH: IGEMM_LAUNCH(true, 2, 3); break;
+    case IG_DMA: IGEMM_LAUNCH(true, ROLE, 3); break;    // single-gather fp32 variants (never ROLE 2, see igemm_form)
+    case IG_CT2: IGEMM_LAUNCH(true, ROLE, 2); break;
+    case IG_CT1: IGEMM_LAUNCH(true, ROLE, 1); break;
+    case IG_F32: IGEMM_LAUNCH(true, ROLE); break;
+    default:                                            // IG_UNALIGNED (never ROLE 2)
+      if constexpr (ROLE != 2) IGEMM_LAUNCH(false, ROLE);
+      break;
   }
   MUNIT_CHECK_LAUNCH("conv_igemm");
   if (q.ksplit > 1) {
@@ -1199,6 +1211,52 @@ int build_cin4(const Cin4Plan& c, const float* x3, long long npix, const float* 
 bool cin4_fwd_ok(const munit_conv_desc* d) {
   return d->Cin == 3 && d->in_dtype == MUNIT_DTYPE_F32 && d->upsample == 0 && d->KH * d->KW <= 64 && d->Cout % 4 == 0 &&
          NWAVES == 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_CIN4");
+}
+
+void set_cin4(IgemmParams* p, const Cin4Plan& c) { p->Ktot = c.kpad; p->w_row = c.kpad; p->cin4 = 1; }
+
+// Launch parameters of the forward entry point (pointers left null): the entry point launches them and
+// munit_igemm_kernel_name asks igemm_form about the very same structs.
+IgemmParams fwd_params(const munit_conv_desc* d, int Ho, int Wo) {
+  IgemmParams p{};
+  p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin;
+  p.ups = d->upsample; p.Hu = d->H << p.ups; p.Wu = d->W << p.ups;
+  p.Ho = Ho; p.Wo = Wo; p.Cout = d->Cout;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
+  p.reflect = d->pad_mode == MUNIT_PAD_REFLECT;
+  p.Ktot = d->KH * d->KW * d->Cin;
+  p.w_row = p.Ktot;
+  p.y_sw = d->Cout;
+  p.y_sh = (long long)Wo * d->Cout;
+  p.y_sb = (long long)Ho * Wo * d->Cout;
+  p.M = d->B * Ho * Wo;
+  p.act = d->act; p.slope = d->slope;
+  p.ct = d->compute;
+  p.ps = 1;
+  p.bf16s = d->in_dtype == MUNIT_DTYPE_BF16;
+  p.out_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
+  return p;
+}
+// the four 3x3 phase convs of the sub-pixel form, from the layer's forward parameters
+IgemmParams subpixel_phase_params(const IgemmParams& p, const munit_conv_desc* d, int Wo) {
+  IgemmParams q = p;
+  q.ups = 0; q.Hu = d->H; q.Wu = d->W;
+  q.Ho = d->H; q.Wo = d->W;                 // one GEMM row per source pixel and phase
+  q.KH = 3; q.KW = 3; q.pad = 1; q.reflect = 0;
+  q.Ktot = 9 * d->Cin; q.w_row = q.Ktot;
+  q.y_sw = 2 * d->Cout;
+  q.y_sh = (long long)2 * Wo * d->Cout;
+  q.M = d->B * d->H * d->W;
+  q.ps = 2;
+  q.w_phase = (long long)d->Cout * q.Ktot;
+  q.y_phase_row = (long long)Wo * d->Cout;
+  q.y_phase_col = d->Cout;
+  return q;
+}
+// ... and its frame of `ring` pixels through the generic 25-tap gather
+void set_subpixel_frame(IgemmParams* p, const munit_conv_desc* d, int Ho, int Wo, int ring) {
+  p->frame = ring;
+  p->M = d->B * (2 * ring * Wo + 2 * ring * (Ho - 2 * ring));
 }
 
 // 3x3 / stride 1 / pad 1 fp32 layers with wide channel counts: Winograd F(2x2, 3x3) (conv_wino.hip)
@@ -1345,24 +1403,8 @@ extern "C" int munit_conv2d_fwd_prepared(const munit_conv_desc* d, const void* x
   }
   void* slabs = ws ? reinterpret_cast<char*>(ws) + img_bytes : nullptr;
   const size_t slab_bytes = ws ? ws_bytes - img_bytes : 0;
-  IgemmParams p{};
+  IgemmParams p = fwd_params(d, Ho, Wo);
   p.x = reinterpret_cast<const float*>(x); p.w = wimg; p.bias = bias; p.y = y;
-  p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin;
-  p.ups = d->upsample; p.Hu = d->H << p.ups; p.Wu = d->W << p.ups;
-  p.Ho = Ho; p.Wo = Wo; p.Cout = d->Cout;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-  p.reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-  p.Ktot = d->KH * d->KW * d->Cin;
-  p.w_row = p.Ktot;
-  p.y_sw = d->Cout;
-  p.y_sh = (long long)Wo * d->Cout;
-  p.y_sb = (long long)Ho * Wo * d->Cout;
-  p.M = d->B * Ho * Wo;
-  p.act = d->act; p.slope = d->slope;
-  p.ct = d->compute;
-  p.ps = 1;
-  p.bf16s = d->in_dtype == MUNIT_DTYPE_BF16;
-  p.out_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
   if (cin4_fwd_ok(d)) {
     const long long npix = (long long)d->B * d->H * d->W;
     const Cin4Plan c = plan_cin4(npix, d->Cout, d->KH * d->KW);
@@ -1370,25 +1412,14 @@ extern "C" int munit_conv2d_fwd_prepared(const munit_conv_desc* d, const void* x
     if (rc) return rc;
     p.x = reinterpret_cast<const float*>(ws);
     p.w = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ws) + c.x4_bytes);
-    p.Ktot = c.kpad; p.w_row = c.kpad; p.cin4 = 1;
+    set_cin4(&p, c);
     return launch_igemm<0>(p, 1, st);
   }
   if (it.kind == MUNIT_PREP_SUBPIXEL || it.kind == MUNIT_PREP_SUBPIXEL_WINOGRAD) {
     // (1) four phase convs (3x3 over the source, merged weights) write every output pixel; the 2-pixel
     // frame, where reflect padding breaks the merge, is then (2) recomputed by the generic 25-tap gather.
-    IgemmParams q = p;
+    const IgemmParams q = subpixel_phase_params(p, d, Wo);
     int ring = 2;                             // width of the frame the generic gather recomputes
-    q.ups = 0; q.Hu = d->H; q.Wu = d->W;
-    q.Ho = d->H; q.Wo = d->W;                 // one GEMM row per source pixel and phase
-    q.KH = 3; q.KW = 3; q.pad = 1; q.reflect = 0;
-    q.Ktot = 9 * d->Cin; q.w_row = q.Ktot;
-    q.y_sw = 2 * d->Cout;
-    q.y_sh = (long long)2 * Wo * d->Cout;
-    q.M = d->B * d->H * d->W;
-    q.ps = 2;
-    q.w_phase = (long long)d->Cout * q.Ktot;
-    q.y_phase_row = (long long)Wo * d->Cout;
-    q.y_phase_col = d->Cout;
     if (it.kind == MUNIT_PREP_SUBPIXEL_WINOGRAD) {
       WinoParams wq{};
       wq.x = reinterpret_cast<const float*>(x); wq.u = wimg; wq.bias = bias; wq.y = reinterpret_cast<float*>(y);
@@ -1410,8 +1441,7 @@ extern "C" int munit_conv2d_fwd_prepared(const munit_conv_desc* d, const void* x
       rc = launch_igemm<0>(q, 4, st);
     }
     if (rc) return rc;
-    p.frame = ring;
-    p.M = d->B * (2 * ring * Wo + 2 * ring * (Ho - 2 * ring));
+    set_subpixel_frame(&p, d, Ho, Wo, ring);
     // the frame launch multiplies by the original 5x5 weights: fp32 -> w itself; bf16 storage -> their bf16 copy,
     // which the image carries behind the merged phase weights
     p.w = it.bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const bf16_t*>(wimg) + (size_t)4 * 9 * d->Cout * d->Cin) : w;
@@ -1558,6 +1588,70 @@ int plan_dgrad(const munit_conv_desc* d, DgradPlan* pl) {
                                 pl->TH * pl->TW * d->Cout, pl->ps * pl->ps);
   return MUNIT_OK;
 }
+
+// Launch parameters of the backward-data entry point (pointers left null), shared with munit_igemm_kernel_name like
+// fwd_params.  Folded forms: the pad / up-sampling adjoint sits in the gather, GEMM rows are the source pixels of dx.
+IgemmParams dgrad_fold_params(const munit_conv_desc* d, const DgradPlan& pl) {
+  IgemmParams p{};
+  p.B = d->B; p.H = pl.Ho; p.W = pl.Wo; p.Cin = d->Cout;   // GEMM "input" = dy
+  p.ups = 0; p.Hu = pl.Ho; p.Wu = pl.Wo;
+  p.Ho = d->H; p.Wo = d->W; p.Cout = d->Cin;               // GEMM rows = source pixels of dx
+  p.KH = d->KH; p.KW = d->KW; p.stride = 1; p.pad = d->KH - 1; p.reflect = 0;
+  p.Ktot = d->KH * d->KW * d->Cout;
+  p.w_row = p.Ktot;
+  p.y_sw = d->Cin;
+  p.y_sh = (long long)d->W * d->Cin;
+  p.y_sb = (long long)d->H * d->W * d->Cin;
+  p.M = d->B * d->H * d->W;
+  p.act = MUNIT_ACT_NONE; p.slope = 0.f;
+  p.ct = d->compute;
+  p.ps = 1;
+  p.f_pad = d->pad; p.f_ups = d->upsample; p.f_reflect = d->pad_mode == MUNIT_PAD_REFLECT;
+  p.f_Hu = d->H << d->upsample; p.f_Wu = d->W << d->upsample;
+  p.patch = pl.patch;
+  p.bf16s = pl.bf16s; p.out_bf16 = d->in_dtype == MUNIT_DTYPE_BF16;
+  return p;
+}
+bool dgrad_fold_dtypes_ok(const munit_conv_desc* d, const DgradPlan& pl) {
+  return d->in_dtype != MUNIT_DTYPE_BF16 || pl.bf16s || pl.patch;
+}
+// box-sum form: the interior source pixels as a stride-2 single gather over S ...
+IgemmParams boxsum_interior_params(const IgemmParams& p, const munit_conv_desc* d) {
+  IgemmParams q = p;
+  q.Ho = d->H - 4; q.Wo = d->W - 4;
+  q.stride = 2; q.pad = -2;
+  q.M = d->B * q.Ho * q.Wo;
+  return q;
+}
+// ... and the 2-pixel frame through the general folded gather
+void set_boxsum_frame(IgemmParams* p, const munit_conv_desc* d) {
+  p->frame = 2;
+  p->M = d->B * (4 * d->W + 4 * (d->H - 4));
+}
+// plain correlation over the padded domain, one launch phase per stride parity (fold_kernel follows unless pl.direct)
+IgemmParams dgrad_corr_params(const munit_conv_desc* d, const DgradPlan& pl) {
+  IgemmParams p{};
+  p.B = d->B; p.H = pl.Ho; p.W = pl.Wo; p.Cin = d->Cout;
+  p.ups = 0; p.Hu = pl.Ho; p.Wu = pl.Wo;
+  p.Ho = pl.Ho + pl.TH - 1; p.Wo = pl.Wo + pl.TW - 1; p.Cout = d->Cin;
+  p.KH = pl.TH; p.KW = pl.TW; p.stride = 1; p.pad = pl.TH - 1;  // TH == TW for every layer here
+  p.reflect = 0;
+  p.Ktot = pl.TH * pl.TW * d->Cout;
+  p.w_row = p.Ktot;
+  p.y_sw = pl.ps * d->Cin;
+  p.y_sh = (long long)pl.ps * pl.Wq * d->Cin;
+  p.y_sb = (long long)pl.Hq * pl.Wq * d->Cin;
+  p.M = d->B * p.Ho * p.Wo;
+  p.act = MUNIT_ACT_NONE; p.slope = 0.f;
+  p.ct = d->compute;
+  p.ps = pl.ps;
+  p.w_phase = (long long)d->Cin * p.Ktot;
+  p.y_phase_row = (long long)pl.Wq * d->Cin;
+  p.y_phase_col = d->Cin;
+  p.bf16s = pl.bf16s; p.out_bf16 = d->in_dtype == MUNIT_DTYPE_BF16;
+  return p;
+}
+bool fold_vectorised(const munit_conv_desc* d) { return d->Cin % 4 == 0; }   // fold_kernel<T>; else fold_scalar_kernel
 }  // namespace
 
 extern "C" size_t munit_conv2d_dgrad_workspace_bytes(const munit_conv_desc* d) {
@@ -1671,26 +1765,9 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
     }
   }
   if (pl.folded) {
-    IgemmParams p{};
+    IgemmParams p = dgrad_fold_params(d, pl);
     p.x = dy; p.w = wt; p.bias = nullptr; p.y = dx;
-    p.B = d->B; p.H = pl.Ho; p.W = pl.Wo; p.Cin = d->Cout;   // GEMM "input" = dy
-    p.ups = 0; p.Hu = pl.Ho; p.Wu = pl.Wo;
-    p.Ho = d->H; p.Wo = d->W; p.Cout = d->Cin;               // GEMM rows = source pixels of dx
-    p.KH = d->KH; p.KW = d->KW; p.stride = 1; p.pad = d->KH - 1; p.reflect = 0;
-    p.Ktot = d->KH * d->KW * d->Cout;
-    p.w_row = p.Ktot;
-    p.y_sw = d->Cin;
-    p.y_sh = (long long)d->W * d->Cin;
-    p.y_sb = (long long)d->H * d->W * d->Cin;
-    p.M = d->B * d->H * d->W;
-    p.act = MUNIT_ACT_NONE; p.slope = 0.f;
-    p.ct = d->compute;
-    p.ps = 1;
-    p.f_pad = d->pad; p.f_ups = d->upsample; p.f_reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-    p.f_Hu = d->H << d->upsample; p.f_Wu = d->W << d->upsample;
-    p.patch = pl.patch;
-    p.bf16s = pl.bf16s; p.out_bf16 = dx_bf16;
-    MUNIT_CHECK_ARG(!dx_bf16 || pl.bf16s || pl.patch, "conv2d_dgrad: unsupported dtype combination");
+    MUNIT_CHECK_ARG(dgrad_fold_dtypes_ok(d, pl), "conv2d_dgrad: unsupported dtype combination");
     if (pl.boxsum && pl.upwino) {
       // interior source pixels 2..H-3 x 2..W-3 as ONE Winograd launch: the four output phases of dy are 3x3-correlated with the
       // rotated merged filters and summed (K = 4 Cout); no box sum, no padding
@@ -1706,8 +1783,7 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
       wq.act = MUNIT_ACT_NONE; wq.slope = 0.f;
       rc = munit_wino_launch(wq, st);
       if (rc) return rc;
-      p.frame = 2;
-      p.M = d->B * (4 * d->W + 4 * (d->H - 4));
+      set_boxsum_frame(&p, d);
       rc = launch_igemm<2>(p, 1, st, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, pl.sk_bytes);
     } else if (pl.boxsum) {
       // interior source pixels 2..H-3 x 2..W-3: dx[i][j] = sum_taps wt[t][r] . S[2i-2+t][2j-2+r] -- one gather per element
@@ -1717,17 +1793,13 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
                            reinterpret_cast<const f32x4*>(dy), reinterpret_cast<f32x4*>(g), d->B, pl.Ho, pl.Wo, d->Cout / 4);
         MUNIT_CHECK_LAUNCH("box2x2");
       }
-      IgemmParams q = p;
+      IgemmParams q = boxsum_interior_params(p, d);
       q.x = g;
       q.y = dx + ((long long)2 * d->W + 2) * d->Cin;
-      q.Ho = d->H - 4; q.Wo = d->W - 4;
-      q.stride = 2; q.pad = -2;
-      q.M = d->B * q.Ho * q.Wo;
       rc = launch_igemm<0>(q, 1, st);
       if (rc) return rc;
       // the 2-pixel frame keeps the general folded gather (reflections add further positions there), split over K
-      p.frame = 2;
-      p.M = d->B * (4 * d->W + 4 * (d->H - 4));
+      set_boxsum_frame(&p, d);
       rc = launch_igemm<2>(p, 1, st, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, pl.sk_bytes);
     } else {
       rc = launch_igemm<2>(p, 1, st);
@@ -1742,27 +1814,9 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
     }
     return MUNIT_OK;
   }
-  IgemmParams p{};
-  p.x = dy; p.w = wt; p.bias = nullptr; p.y = direct ? (void*)dx : (void*)g;
-  p.B = d->B; p.H = pl.Ho; p.W = pl.Wo; p.Cin = d->Cout;
-  p.ups = 0; p.Hu = pl.Ho; p.Wu = pl.Wo;
-  p.Ho = pl.Ho + pl.TH - 1; p.Wo = pl.Wo + pl.TW - 1; p.Cout = d->Cin;
-  p.KH = pl.TH; p.KW = pl.TW; p.stride = 1; p.pad = pl.TH - 1;  // TH == TW for every layer here
   MUNIT_CHECK_ARG(pl.TH == pl.TW, "conv2d_dgrad: non-square kernels are not supported");
-  p.reflect = 0;
-  p.Ktot = pl.TH * pl.TW * d->Cout;
-  p.w_row = p.Ktot;
-  p.y_sw = pl.ps * d->Cin;
-  p.y_sh = (long long)pl.ps * pl.Wq * d->Cin;
-  p.y_sb = (long long)pl.Hq * pl.Wq * d->Cin;
-  p.M = d->B * p.Ho * p.Wo;
-  p.act = MUNIT_ACT_NONE; p.slope = 0.f;
-  p.ct = d->compute;
-  p.ps = pl.ps;
-  p.w_phase = (long long)d->Cin * p.Ktot;
-  p.y_phase_row = (long long)pl.Wq * d->Cin;
-  p.y_phase_col = d->Cin;
-  p.bf16s = pl.bf16s; p.out_bf16 = dx_bf16;
+  IgemmParams p = dgrad_corr_params(d, pl);
+  p.x = dy; p.w = wt; p.bias = nullptr; p.y = direct ? (void*)dx : (void*)g;
   if (pl.cin4) {
     // image head: dy has three channels -> 4-channel re-layout of dy and of the transposed weights, direct-to-LDS taps
     char* c4 = reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes;
@@ -1772,7 +1826,7 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
     if (rc) return rc;
     p.x = reinterpret_cast<const float*>(c4);
     p.w = reinterpret_cast<const float*>(c4 + c.x4_bytes);
-    p.Ktot = c.kpad; p.w_row = c.kpad; p.cin4 = 1;
+    set_cin4(&p, c);
     rc = launch_igemm<1>(p, 1, st);
   } else {
     rc = launch_igemm<1>(p, pl.ps * pl.ps, st, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, pl.sk_bytes);
@@ -1780,7 +1834,7 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
   if (rc) return rc;
   if (!direct) {
     const int reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-    if (d->Cin % 4 == 0) {
+    if (fold_vectorised(d)) {
       rc = dx_bf16 ? launch_fold<bf16_t>(d, pl, g, add_, dx_, st) : launch_fold<float>(d, pl, g, add_, dx_, st);
       if (rc) return rc;
     } else {
@@ -1860,32 +1914,122 @@ extern "C" int munit_conv2d_prepare_weights_batch(const munit_prep_item* items_d
 // 2*B*Ho*Wo*Cout*KH*KW*Cin: the sub-pixel forward runs 4 merged 3x3 phases + the 25-tap frame, the box-sum
 // backward-data one 25-tap row per interior SOURCE pixel + the frame, strided backward-data its phases over the
 // padded domain.  Valid GEMM rows only (tile padding is not counted).  bench.py reports both totals.
-// Name (as a profiler shows it) of the kernel that carries a pass of this layer; mirrors the dispatch of the entry points.
+// Name (as a profiler shows it) of the kernel that carries a pass of this layer.  It follows the entry points' own
+// decisions: the same predicates and plans, and igemm_form on the same launch parameters (fwd_params, dgrad_fold_params,
+// dgrad_corr_params).  A descriptor the entry point would refuse is named "refused: <why>".  The names of fp32 tensors with
+// fp32 arithmetic do not tell the loader variants (IG_DMA / IG_F32 / IG_UNALIGNED) apart; every other form has its own.
+namespace {
+const char* igemm_refusal(IgemmForm f) {
+  switch (f) {
+    case IG_REFUSED_BF16_CIN: return "refused: bf16 storage needs a multiple of 64 input channels";
+    case IG_REFUSED_CIN4_FOLD: return "refused: 4-channel taps are not a folded backward-data form";
+    case IG_REFUSED_BF16_FOLD: return "refused: bf16-storage folded backward-data exists for the LDS-patch form only";
+    case IG_REFUSED_FOLD_UNALIGNED: return "refused: folded backward-data needs Cout % 32 == 0";
+    default: return nullptr;
+  }
+}
+}  // namespace
+
 const char* munit_igemm_kernel_name(const munit_conv_desc* d, int pass) {
   int Ho, Wo;
   if (munit_conv2d_out_hw(d, &Ho, &Wo)) return "invalid";
   const bool refl = d->pad_mode == MUNIT_PAD_REFLECT;
+  const bool x_bf16 = d->in_dtype == MUNIT_DTYPE_BF16, y_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
   if (pass == MUNIT_PASS_FWD) {
-    if (munit_small_fwd_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_FWD")) return "conv_head_pk_kernel";
+    if (munit_small_fwd_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_FWD")) {
+      if (y_bf16) return "refused: the 3-channel image head writes fp32";
+      return x_bf16 ? "conv_head_pk_kernel<bf16_t>" : "conv_head_pk_kernel";
+    }
+    IgemmParams p = fwd_params(d, Ho, Wo);
+    const int bn = igemm_bn(p);
     if (subpixel_wino_ok(d)) return "conv_wino_kernel<1, 0> x4 sub-pixel phases + conv_igemm_kernel frame";
-    if (subpixel_ok(d)) return "conv_igemm_kernel x4 sub-pixel phases + frame";
+    if (subpixel_ok(d)) {
+      const IgemmForm ph = igemm_form(subpixel_phase_params(p, d, Wo), 0);
+      set_subpixel_frame(&p, d, Ho, Wo, 2);
+      const IgemmForm fr = igemm_form(p, 0);
+      if (igemm_refusal(ph)) return igemm_refusal(ph);
+      if (igemm_refusal(fr)) return igemm_refusal(fr);
+      if (ph != fr) return "invalid";   // (no descriptor gets here: both launches share Cin, ct and the dtypes)
+      if (ph == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 0, 4> x4 sub-pixel phases + frame"
+                                          : "conv_igemm_kernel<128, true, 0, 4> x4 sub-pixel phases + frame";
+      if (ph == IG_CT1) return "conv_igemm_kernel<.., 0, 1> x4 sub-pixel phases + frame";
+      if (ph == IG_CT2) return "conv_igemm_kernel<.., 0, 2> x4 sub-pixel phases + frame";
+      return "conv_igemm_kernel x4 sub-pixel phases + frame";
+    }
     if (wino_fwd_ok(d)) return refl ? "conv_wino_kernel<0, 0>" : "conv_wino_kernel<1, 0>";
     if (wino_s2_fwd_ok(d)) return refl ? "conv_wino_kernel<0, 1>" : "conv_wino_kernel<1, 1>";
-    if (cin4_fwd_ok(d)) return "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps)";
+    if (cin4_fwd_ok(d)) {
+      set_cin4(&p, plan_cin4(1, d->Cout, d->KH * d->KW));
+      const IgemmForm f = igemm_form(p, 0);
+      if (igemm_refusal(f)) return igemm_refusal(f);
+      return y_bf16 ? "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps, bf16 y)"
+                    : "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps)";
+    }
+    const IgemmForm f = igemm_form(p, 0);
+    if (igemm_refusal(f)) return igemm_refusal(f);
+    if (f == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 0, 4>" : "conv_igemm_kernel<128, true, 0, 4>";
+    if (f == IG_CT1) return "conv_igemm_kernel<.., 0, 1>";
+    if (f == IG_CT2) return "conv_igemm_kernel<.., 0, 2>";
     return "conv_igemm_kernel<fwd>";
   }
   DgradPlan pl;
   if (plan_dgrad(d, &pl)) return "invalid";
+  if (x_bf16 && d->Cin % 4 != 0) return "refused: bf16 dx needs Cin % 4 == 0";
   if (pl.wino) return refl ? "conv_wino_kernel<2, 0>" : "conv_wino_kernel<1, 0>";
   if (pl.wino_s2) return refl ? "conv_wino_kernel<0, 2>" : "conv_wino_kernel<1, 2>";
-  if (pl.boxsum && pl.upwino) return "conv_wino_kernel<1, 3> + conv_igemm_kernel frame";
-  if (pl.boxsum) return "box2x2_kernel + conv_igemm_kernel (box-sum backward-data)";
-  if (pl.small) return "conv_head_pk_kernel (padded-domain correlation)";
-  if (pl.patch) return "conv_igemm_kernel<.., 2, 3> (LDS-patch fold)";
-  if (pl.folded) return "conv_igemm_kernel<.., 2, 0> (folded gather)";
-  if (pl.direct) return "conv_igemm_kernel<dgrad direct>";
-  if (pl.cin4) return "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps)";
-  return "conv_igemm_kernel<.., 1, .> phases + fold_kernel";
+  if (pl.small) {
+    if (x_bf16) return "refused: the 3-channel data gradient is fp32";
+    return y_bf16 ? "conv_head_pk_kernel<bf16_t> (padded-domain correlation)" : "conv_head_pk_kernel (padded-domain correlation)";
+  }
+  if (pl.folded) {
+    if (!dgrad_fold_dtypes_ok(d, pl)) return "refused: unsupported dtype combination";
+    IgemmParams p = dgrad_fold_params(d, pl);
+    const int bn = igemm_bn(p);
+    if (pl.boxsum && pl.upwino) return "conv_wino_kernel<1, 3> + conv_igemm_kernel frame";
+    if (pl.boxsum) {
+      const IgemmForm in = igemm_form(boxsum_interior_params(p, d), 0);
+      set_boxsum_frame(&p, d);
+      const IgemmForm fr = igemm_form(p, 2);
+      if (igemm_refusal(in)) return igemm_refusal(in);
+      if (igemm_refusal(fr)) return igemm_refusal(fr);
+      if (in == IG_CT1 && fr == IG_CT1) return "box2x2_kernel + conv_igemm_kernel<.., 1> (box-sum backward-data)";
+      if (in == IG_CT2 && fr == IG_CT2) return "box2x2_kernel + conv_igemm_kernel<.., 2> (box-sum backward-data)";
+      return "box2x2_kernel + conv_igemm_kernel (box-sum backward-data)";
+    }
+    const IgemmForm f = igemm_form(p, 2);
+    if (igemm_refusal(f)) return igemm_refusal(f);
+    if (f == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 2, 4> (LDS-patch fold)" : "conv_igemm_kernel<128, true, 2, 4> (LDS-patch fold)";
+    if (f == IG_PATCH) return "conv_igemm_kernel<.., 2, 3> (LDS-patch fold)";
+    if (f == IG_CT1) return "conv_igemm_kernel<.., 2, 1> (folded gather)";
+    if (f == IG_CT2) return "conv_igemm_kernel<.., 2, 2> (folded gather)";
+    return "conv_igemm_kernel<.., 2, 0> (folded gather)";
+  }
+  if (pl.TH != pl.TW) return "refused: non-square kernels are not supported";
+  IgemmParams p = dgrad_corr_params(d, pl);
+  const int bn = igemm_bn(p);
+  if (pl.cin4) {
+    set_cin4(&p, plan_cin4(1, d->Cin, pl.TH * pl.TW));
+    const IgemmForm f = igemm_form(p, 1);
+    if (igemm_refusal(f)) return igemm_refusal(f);
+    return x_bf16 ? "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps) + fold_kernel<bf16_t>"
+                  : "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps)";
+  }
+  const IgemmForm f = igemm_form(p, 1);
+  if (igemm_refusal(f)) return igemm_refusal(f);
+  if (pl.direct) {      // (an `add` operand sends a direct layer through fold_kernel: the name is that of the call without one)
+    if (f == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 1, 4> direct" : "conv_igemm_kernel<128, true, 1, 4> direct";
+    if (f == IG_CT1) return "conv_igemm_kernel<.., 1, 1> direct";
+    if (f == IG_CT2) return "conv_igemm_kernel<.., 1, 2> direct";
+    return "conv_igemm_kernel<dgrad direct>";
+  }
+  const bool fold16 = x_bf16 && fold_vectorised(d);    // fold_kernel<bf16_t> (else fold_kernel<float> / fold_scalar_kernel)
+  if (f == IG_BF16S) {
+    if (fold16) return bn == 64 ? "conv_igemm_kernel<64, true, 1, 4> phases + fold_kernel<bf16_t>" : "conv_igemm_kernel<128, true, 1, 4> phases + fold_kernel<bf16_t>";
+    return bn == 64 ? "conv_igemm_kernel<64, true, 1, 4> phases + fold_kernel" : "conv_igemm_kernel<128, true, 1, 4> phases + fold_kernel";
+  }
+  if (f == IG_CT1) return fold16 ? "conv_igemm_kernel<.., 1, 1> phases + fold_kernel<bf16_t>" : "conv_igemm_kernel<.., 1, 1> phases + fold_kernel";
+  if (f == IG_CT2) return fold16 ? "conv_igemm_kernel<.., 1, 2> phases + fold_kernel<bf16_t>" : "conv_igemm_kernel<.., 1, 2> phases + fold_kernel";
+  return fold16 ? "conv_igemm_kernel<.., 1, .> phases + fold_kernel<bf16_t>" : "conv_igemm_kernel<.., 1, .> phases + fold_kernel";
 }
 
 double munit_igemm_executed_flops(const munit_conv_desc* d, int pass) {

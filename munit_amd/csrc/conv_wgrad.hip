@@ -1011,6 +1011,59 @@ void plan_launch(int M, int Ktot, int Cout, bool aligned, WgradPlan* pl, bool bi
   pl->bias_bytes = align_up((size_t)ns * Cout * sizeof(float), 256);
 }
 
+// Which kernel one split-K launch takes, or why it is refused.  run_wgrad acts on it and munit_conv2d_kernel_name names
+// it: the decision is written once.
+enum WgradForm {
+  WG_REFUSED_BF16,       // bf16 tensors outside the FAST loader's reach (and outside the direct-to-LDS kernel's, for a frame)
+  WG_REFUSED_BF16_X,     // bf16 x against an fp32 dy
+  WG_BF16S_128,          // conv_wgrad_bf16s_kernel<1>
+  WG_BF16S_256,          // conv_wgrad_bf16s_kernel<2>
+  WG_REG_BF16,           // conv_wgrad_kernel<bc, true, true, 1, true, true>: register loader, both tensors bf16
+  WG_REG_BF16_DY,        // conv_wgrad_kernel<bc, true, true, 0, false, true>: fp32 x against a bf16 dy
+  WG_DMA,                // conv_wgrad_kernel<128, true, true, 3>
+  WG_CT1, WG_CT2,        // conv_wgrad_kernel<bc, true, true, 1 / 2>: fp32 tensors, bf16 / split operands
+  WG_FAST, WG_ALIGNED, WG_GENERIC   // conv_wgrad_kernel<bc, true, true> / <bc, true, false> / <bc, false, false>
+};
+struct WgradChoice {
+  WgradForm form;
+  bool fast;   // FAST loader: 32-bit byte offsets and 24-bit multiplies (see the kernel)
+  long long x_bytes, dy_bytes;
+};
+WgradChoice wgrad_form(const WgradParams& p, const WgradPlan& pl, bool aligned) {
+  WgradChoice c{};
+  c.x_bytes = (long long)p.B * p.H * p.W * p.Cin * (p.x_bf16 ? 2 : 4);
+  c.dy_bytes = (long long)p.B * p.dy_sb * (p.dy_bf16 ? 2 : 4);
+  const bool any_bf16 = p.x_bf16 || p.dy_bf16;
+  const bool fast_any = aligned && (p.Cout % 4 == 0) && c.x_bytes < (1ll << 31) && c.dy_bytes < (1ll << 31) &&
+                        (long long)p.B * p.H * p.W < (1ll << 23) && (any_bf16 || !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_FAST_WGRAD"));
+  const bool fast = c.fast = fast_any && !p.frame;
+  if (any_bf16) {
+    // bf16 storage: only the FAST register loader reads bf16 tensors
+    const bool dma_ok = p.x_bf16 && p.dy_bf16 && p.Cin % 128 == 0 && p.Cout % 8 == 0 && p.Ho + p.Wo <= DMA_MAX_HW;
+    if (!fast && !(fast_any && dma_ok)) c.form = WG_REFUSED_BF16;   // (the frame enumeration exists in the direct-to-LDS kernel only)
+    else if (dma_ok && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_DMA")) c.form = pl.bc == 256 ? WG_BF16S_256 : WG_BF16S_128;
+    else if (p.x_bf16 && p.dy_bf16) c.form = WG_REG_BF16;        // trunk layers: bf16 MFMA (operands are already bf16 values)
+    else if (p.dy_bf16) c.form = WG_REG_BF16_DY;                 // first layer: fp32 image (4-channel re-layout) against a bf16 dy, fp32 MFMA
+    else c.form = WG_REFUSED_BF16_X;
+  } else if (fast && p.ct == 0 && pl.bc == 128 && p.Cin % 128 == 0 && p.Ho + p.Wo <= DMA_MAX_HW &&
+             !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_DMA")) {
+    c.form = WG_DMA;
+  } else if (fast && p.ct == 1) {
+    c.form = WG_CT1;
+  } else if (fast && p.ct == 2) {
+    c.form = WG_CT2;
+  } else {
+    c.form = fast ? WG_FAST : aligned ? WG_ALIGNED : WG_GENERIC;
+  }
+  return c;
+}
+
+#define WGRAD_LAUNCH(...)                                                                                         \
+  do {                                                                                                            \
+    if (pl.bc == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, __VA_ARGS__>), grid, dim3(WTHR), 0, st, p);        \
+    else hipLaunchKernelGGL((conv_wgrad_kernel<128, __VA_ARGS__>), grid, dim3(WTHR), 0, st, p);                   \
+  } while (0)
+
 // one split-K launch + deterministic slab reduction into dw (and db)
 int run_wgrad(WgradParams p, const WgradPlan& pl, bool aligned, float* dw, float* db, float beta, float beta_b,
               void* ws, hipStream_t st) {
@@ -1018,29 +1071,24 @@ int run_wgrad(WgradParams p, const WgradPlan& pl, bool aligned, float* dw, float
   p.bias_slab = db ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + pl.slab_bytes) : nullptr;
   p.pix_per_split = pl.pix_per_split;
   dim3 grid((unsigned)pl.k_tiles, (unsigned)pl.c_tiles, (unsigned)pl.nsplit);
-  // FAST loader: 32-bit byte offsets and 24-bit multiplies (see the kernel)
-  const long long xb = (long long)p.B * p.H * p.W * p.Cin * (p.x_bf16 ? 2 : 4), db_ = (long long)p.B * p.dy_sb * (p.dy_bf16 ? 2 : 4);
-  const bool any_bf16 = p.x_bf16 || p.dy_bf16;
-  const bool fast_any = aligned && (p.Cout % 4 == 0) && xb < (1ll << 31) && db_ < (1ll << 31) &&
-                        (long long)p.B * p.H * p.W < (1ll << 23) && (any_bf16 || !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_FAST_WGRAD"));
-  const bool fast = fast_any && !p.frame;
-  p.x_bytes = fast ? (unsigned)xb : 0u;
-  p.dy_bytes = fast ? (unsigned)db_ : 0u;
-  if (any_bf16) {
-    // bf16 storage: only the FAST register loader reads bf16 tensors
-    const bool dma_ok = p.x_bf16 && p.dy_bf16 && p.Cin % 128 == 0 && p.Cout % 8 == 0 && p.Ho + p.Wo <= DMA_MAX_HW;
-    if (!fast && !(fast_any && dma_ok)) {   // (the frame enumeration exists in the direct-to-LDS kernel only)
-      munit_set_error("conv2d_wgrad: bf16 tensors need Cin %% 4 == 0, Cout %% 4 == 0 and tensors below 2 GiB");
+  const WgradChoice ch = wgrad_form(p, pl, aligned);
+  p.x_bytes = ch.fast ? (unsigned)ch.x_bytes : 0u;
+  p.dy_bytes = ch.fast ? (unsigned)ch.dy_bytes : 0u;
+  switch (ch.form) {
+    case WG_REFUSED_BF16:
+      munit_set_error("conv2d_wgrad: bf16 tensors need Cin %% 4 == 0, Cout %% 4 == 0, tensors below 2 GiB and B*H*W < 2^23");
       return MUNIT_ERR_ARG;
-    }
-    if (p.x_bf16 && p.dy_bf16 && p.Cin % 128 == 0 && p.Cout % 8 == 0 && p.Ho + p.Wo <= DMA_MAX_HW &&
-        !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_DMA")) {
+    case WG_REFUSED_BF16_X:
+      munit_set_error("conv2d_wgrad: bf16 x with fp32 dy exists for the 3-channel image head only");
+      return MUNIT_ERR_ARG;
+    case WG_BF16S_128:
+    case WG_BF16S_256: {
       // direct-to-LDS bf16 kernel: 128 x 128 tiles (Cout padded), 64-pixel steps; never more splits than the plan's slabs hold
       // (pl.bc == 256: the plan was made for the 256 x 256 tile, see plan_launch)
       int pps = (cdiv(p.M, pl.nsplit) + BS_WP - 1) / BS_WP * BS_WP;
       p.pix_per_split = pps;
       const int ns = cdiv(p.M, pps);
-      if (pl.bc == 256) {
+      if (ch.form == WG_BF16S_256) {
         dim3 g2((unsigned)(p.Ktot / 256), (unsigned)(p.Cout / 256), (unsigned)ns);
         hipLaunchKernelGGL(conv_wgrad_bf16s_kernel<2>, g2, dim3(WTHR), 0, st, p);
       } else {
@@ -1055,33 +1103,14 @@ int run_wgrad(WgradParams p, const WgradPlan& pl, bool aligned, float* dw, float
       MUNIT_CHECK_LAUNCH("slab_reduce");
       return MUNIT_OK;
     }
-    if (p.x_bf16 && p.dy_bf16) {        // trunk layers: bf16 MFMA (operands are already bf16 values)
-      if (pl.bc == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, true, true, 1, true, true>), grid, dim3(WTHR), 0, st, p);
-      else hipLaunchKernelGGL((conv_wgrad_kernel<128, true, true, 1, true, true>), grid, dim3(WTHR), 0, st, p);
-    } else if (p.dy_bf16) {             // first layer: fp32 image (4-channel re-layout) against a bf16 dy, fp32 MFMA
-      if (pl.bc == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, true, true, 0, false, true>), grid, dim3(WTHR), 0, st, p);
-      else hipLaunchKernelGGL((conv_wgrad_kernel<128, true, true, 0, false, true>), grid, dim3(WTHR), 0, st, p);
-    } else {
-      munit_set_error("conv2d_wgrad: bf16 x with fp32 dy exists for the 3-channel image head only");
-      return MUNIT_ERR_ARG;
-    }
-  } else if (fast && p.ct == 0 && pl.bc == 128 && p.Cin % 128 == 0 && p.Ho + p.Wo <= DMA_MAX_HW &&
-      !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_DMA")) {
-    hipLaunchKernelGGL((conv_wgrad_kernel<128, true, true, 3>), grid, dim3(WTHR), 0, st, p);
-  } else if (fast && p.ct == 1) {
-    if (pl.bc == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, true, true, 1>), grid, dim3(WTHR), 0, st, p);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<128, true, true, 1>), grid, dim3(WTHR), 0, st, p);
-  } else if (fast && p.ct == 2) {
-    if (pl.bc == 64) hipLaunchKernelGGL((conv_wgrad_kernel<64, true, true, 2>), grid, dim3(WTHR), 0, st, p);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<128, true, true, 2>), grid, dim3(WTHR), 0, st, p);
-  } else if (pl.bc == 64) {
-    if (fast) hipLaunchKernelGGL((conv_wgrad_kernel<64, true, true>), grid, dim3(WTHR), 0, st, p);
-    else if (aligned) hipLaunchKernelGGL((conv_wgrad_kernel<64, true, false>), grid, dim3(WTHR), 0, st, p);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<64, false, false>), grid, dim3(WTHR), 0, st, p);
-  } else {
-    if (fast) hipLaunchKernelGGL((conv_wgrad_kernel<128, true, true>), grid, dim3(WTHR), 0, st, p);
-    else if (aligned) hipLaunchKernelGGL((conv_wgrad_kernel<128, true, false>), grid, dim3(WTHR), 0, st, p);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<128, false, false>), grid, dim3(WTHR), 0, st, p);
+    case WG_REG_BF16: WGRAD_LAUNCH(true, true, 1, true, true); break;
+    case WG_REG_BF16_DY: WGRAD_LAUNCH(true, true, 0, false, true); break;
+    case WG_DMA: hipLaunchKernelGGL((conv_wgrad_kernel<128, true, true, 3>), grid, dim3(WTHR), 0, st, p); break;
+    case WG_CT1: WGRAD_LAUNCH(true, true, 1); break;
+    case WG_CT2: WGRAD_LAUNCH(true, true, 2); break;
+    case WG_FAST: WGRAD_LAUNCH(true, true); break;
+    case WG_ALIGNED: WGRAD_LAUNCH(true, false); break;
+    case WG_GENERIC: WGRAD_LAUNCH(false, false); break;
   }
   MUNIT_CHECK_LAUNCH("conv_wgrad");
   const long long n = (long long)p.Cout * p.Ktot;
@@ -1168,7 +1197,53 @@ bool wino_s2_wgrad_layer(const munit_conv_desc* d) {
          munit_wino_wgrad_ok(d->B, d->H, d->W, d->Cin, d->Cout) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINOGRAD_S2") &&
          (long long)d->B * cdiv(d->H / 2, 3) * cdiv(d->W / 2, 3) >= (getenv("MUNIT_WINO_S2_MIN_BLOCKS") ? 1 : 512);
 }
+// Launch parameters of the backward-weight entry point (pointers left null): the entry point launches them and
+// munit_conv2d_kernel_name asks wgrad_form about the very same structs.
+WgradParams wgrad_params(const munit_conv_desc* d, int Ho, int Wo) {
+  WgradParams p{};
+  p.x_bf16 = d->in_dtype == MUNIT_DTYPE_BF16; p.dy_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
+  p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin;
+  p.ups = d->upsample; p.Hu = d->H << p.ups; p.Wu = d->W << p.ups;
+  p.Ho = Ho; p.Wo = Wo; p.Cout = d->Cout;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
+  p.reflect = d->pad_mode == MUNIT_PAD_REFLECT;
+  p.ct = d->compute;
+  p.Ktot = d->KH * d->KW * d->Cin; p.M = d->B * Ho * Wo;
+  p.dy_sw = d->Cout; p.dy_sh = (long long)Wo * d->Cout; p.dy_sb = (long long)Ho * Wo * d->Cout; p.dy_off = 0;
+  return p;
+}
+// sub-pixel form: the frame of sp.ring output pixels through the generic 25-tap gather ...
+WgradParams subpixel_frame_params(const WgradParams& p, const munit_conv_desc* d, const SubpixelPlan& sp, int Ho, int Wo) {
+  WgradParams f = p;
+  f.frame = sp.ring;
+  f.M = d->B * (2 * sp.ring * Wo + 2 * sp.ring * (Ho - 2 * sp.ring));
+  return f;
+}
+// ... and phase ph (a = ph >> 1, b = ph & 1) of the four 3x3 gradients over the interior source pixels
+WgradParams subpixel_phase_params(const WgradParams& p, const munit_conv_desc* d, int Wo, int ph) {
+  const int a = ph >> 1, b = ph & 1;
+  WgradParams q = p;
+  q.ups = 0; q.Hu = d->H; q.Wu = d->W;
+  q.Ho = d->H - 2; q.Wo = d->W - 2;          // interior source pixels i = oh+1, j = ow+1
+  q.KH = 3; q.KW = 3; q.pad = 0; q.reflect = 0;  // taps i-1..i+1 = oh..oh+2: a VALID 3x3 gather
+  q.Ktot = 9 * d->Cin; q.M = d->B * q.Ho * q.Wo;
+  q.dy_sw = 2 * d->Cout; q.dy_sh = (long long)2 * Wo * d->Cout;
+  q.dy_off = ((long long)(2 + a) * Wo + 2 + b) * d->Cout;
+  return q;
+}
+// three input channels re-laid as four
+WgradParams cin3_params(const WgradParams& p, const munit_conv_desc* d) {
+  WgradParams q = p;
+  q.Cin = 4; q.Ktot = d->KH * d->KW * 4; q.x_bf16 = 0;
+  q.ct = 0;   // 4 channels per tap: not a multiple of the bf16 K granularity, stays fp32
+  return q;
+}
 long long s2_tiles(const munit_conv_desc* d) { return (long long)d->B * cdiv(d->H / 2, 3) * cdiv(d->W / 2, 3); }
+const char* wgrad_refusal(WgradForm f) {
+  if (f == WG_REFUSED_BF16) return "refused: bf16 tensors need Cin % 4 == 0, Cout % 4 == 0, tensors below 2 GiB and B*H*W < 2^23";
+  if (f == WG_REFUSED_BF16_X) return "refused: bf16 x with fp32 dy exists for the 3-channel image head only";
+  return nullptr;
+}
 }  // namespace
 
 extern "C" size_t munit_conv2d_wgrad_workspace_bytes(const munit_conv_desc* d) {
@@ -1226,15 +1301,51 @@ extern "C" const char* munit_conv2d_kernel_name(const munit_conv_desc* d, int pa
     const bool fast = ((long long)d->B * (d->H / 2) * (d->W / 2)) % 8 == 0 && d->pad_mode == MUNIT_PAD_REFLECT;
     return fast ? "conv_wino_wgrad_kernel<false, true, false> + wino_wgrad_reduce_kernel" : "conv_wino_wgrad_kernel<false, false, false> + wino_wgrad_reduce_kernel";
   }
-  if (munit_small_wgrad_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_WGRAD"))   // mirrors munit_small_wgrad's choice
-    return MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_PK") ? "conv_lanes_wgrad_kernel" : "conv_lanes_wgrad_pk_kernel";
+  const bool x_bf16 = d->in_dtype == MUNIT_DTYPE_BF16, dy_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
+  if (munit_small_wgrad_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_WGRAD")) {   // mirrors munit_small_wgrad's choice
+    if (dy_bf16) return "refused: the 3-channel image head has an fp32 dy";
+    if (MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_PK")) return x_bf16 ? "conv_lanes_wgrad_kernel<bf16_t>" : "conv_lanes_wgrad_kernel";
+    return x_bf16 ? "conv_lanes_wgrad_pk_kernel<bf16_t>" : "conv_lanes_wgrad_pk_kernel";
+  }
+  // from here on: the launches of munit_conv2d_wgrad on the same parameters and plans, named by wgrad_form
+  const bool aligned = d->Cin % 4 == 0;
+  const WgradParams p = wgrad_params(d, Ho, Wo);
   if (subpixel_wgrad_ok(d)) {
     SubpixelPlan sp;
     plan_subpixel(d, &sp);
-    return sp.wino ? "conv_wino_wgrad_kernel<false, ., true> x4 sub-pixel phases + frame + reduce" : "conv_wgrad_kernel x4 sub-pixel phases + frame";
+    if (sp.wino) return "conv_wino_wgrad_kernel<false, ., true> x4 sub-pixel phases + frame + reduce";
+    const WgradForm fr = wgrad_form(subpixel_frame_params(p, d, sp, Ho, Wo), sp.frame, aligned).form;
+    const WgradForm ph = wgrad_form(subpixel_phase_params(p, d, Wo, 0), sp.phase, aligned).form;
+    if (wgrad_refusal(fr)) return wgrad_refusal(fr);
+    if (wgrad_refusal(ph)) return wgrad_refusal(ph);
+    if (ph == WG_BF16S_128 && fr == WG_BF16S_128) return "conv_wgrad_bf16s_kernel<1> x4 sub-pixel phases + frame";
+    if (x_bf16 || dy_bf16) return "invalid";   // (no descriptor gets here: subpixel_wgrad_ok admits bf16 only where both launches take that kernel)
+    if (ph == WG_CT1) return "conv_wgrad_kernel<.., 1> x4 sub-pixel phases + fp32 frame";
+    if (ph == WG_CT2) return "conv_wgrad_kernel<.., 2> x4 sub-pixel phases + fp32 frame";
+    return "conv_wgrad_kernel x4 sub-pixel phases + frame";
   }
-  if (cin3_padded_ok(d)) return "conv_wgrad_kernel (3 input channels padded to 4)";
-  return "conv_wgrad_kernel + slab_reduce_kernel";
+  if (cin3_padded_ok(d)) {
+    if (x_bf16) return "refused: 3-channel inputs are fp32";
+    Cin3Plan cp;
+    plan_cin3(d, Ho, Wo, &cp);
+    const WgradForm f = wgrad_form(cin3_params(p, d), cp.pl, true).form;
+    if (wgrad_refusal(f)) return wgrad_refusal(f);
+    return f == WG_REG_BF16_DY ? "conv_wgrad_kernel<.., 0, false, true> (3 input channels padded to 4, bf16 dy)"
+                               : "conv_wgrad_kernel (3 input channels padded to 4)";
+  }
+  WgradPlan pl;
+  plan_launch(p.M, p.Ktot, d->Cout, aligned, &pl, bf16s_big_tile(d, Ho, Wo));
+  const WgradForm f = wgrad_form(p, pl, aligned).form;
+  if (wgrad_refusal(f)) return wgrad_refusal(f);
+  switch (f) {
+    case WG_BF16S_128: return "conv_wgrad_bf16s_kernel<1> + slab_reduce_kernel";
+    case WG_BF16S_256: return "conv_wgrad_bf16s_kernel<2> + slab_reduce_kernel";
+    case WG_REG_BF16: return "conv_wgrad_kernel<.., 1, true, true> + slab_reduce_kernel";
+    case WG_REG_BF16_DY: return "conv_wgrad_kernel<.., 0, false, true> + slab_reduce_kernel";
+    case WG_CT1: return "conv_wgrad_kernel<.., 1> + slab_reduce_kernel";
+    case WG_CT2: return "conv_wgrad_kernel<.., 2> + slab_reduce_kernel";
+    default: return "conv_wgrad_kernel + slab_reduce_kernel";
+  }
 }
 
 extern "C" int munit_conv2d_wgrad(const munit_conv_desc* d, const void* x, const void* dy, float* dw,
@@ -1276,17 +1387,8 @@ extern "C" int munit_conv2d_wgrad(const munit_conv_desc* d, const void* x, const
     return munit_small_wgrad(d, Ho, Wo, x, reinterpret_cast<const float*>(dy), dw, db, beta, ws, st);
   }
   const bool aligned = d->Cin % 4 == 0;
-  WgradParams p{};
+  WgradParams p = wgrad_params(d, Ho, Wo);
   p.x = x; p.dy = dy;
-  p.x_bf16 = d->in_dtype == MUNIT_DTYPE_BF16; p.dy_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
-  p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin;
-  p.ups = d->upsample; p.Hu = d->H << p.ups; p.Wu = d->W << p.ups;
-  p.Ho = Ho; p.Wo = Wo; p.Cout = d->Cout;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad;
-  p.reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-  p.ct = d->compute;
-  p.Ktot = d->KH * d->KW * d->Cin; p.M = d->B * Ho * Wo;
-  p.dy_sw = d->Cout; p.dy_sh = (long long)Wo * d->Cout; p.dy_sb = (long long)Ho * Wo * d->Cout; p.dy_off = 0;
   if (subpixel_wgrad_ok(d)) {
     // dw = (frame pixels, generic 25-tap gather) + scatter of the 4 phase gradients (interior pixels, 3x3
     // VALID conv over the source against every other dy row/column): 36 instead of 100 MACs per source
@@ -1295,9 +1397,7 @@ extern "C" int munit_conv2d_wgrad(const munit_conv_desc* d, const void* x, const
     plan_subpixel(d, &sp);
     float* dwc = reinterpret_cast<float*>(ws);
     void* slabs = reinterpret_cast<char*>(ws) + sp.dwc_bytes;
-    WgradParams f = p;
-    f.frame = sp.ring;
-    f.M = d->B * (2 * sp.ring * Wo + 2 * sp.ring * (Ho - 2 * sp.ring));
+    const WgradParams f = subpixel_frame_params(p, d, sp, Ho, Wo);
     rc = run_wgrad(f, sp.frame, aligned, dw, db, beta, beta, slabs, st);
     if (rc) return rc;
     if (sp.wino) {
@@ -1316,14 +1416,7 @@ extern "C" int munit_conv2d_wgrad(const munit_conv_desc* d, const void* x, const
       if (rc) return rc;
     }
     for (int ph = 0; ph < 4 && !sp.wino; ++ph) {
-      const int a = ph >> 1, b = ph & 1;
-      WgradParams q = p;
-      q.ups = 0; q.Hu = d->H; q.Wu = d->W;
-      q.Ho = d->H - 2; q.Wo = d->W - 2;          // interior source pixels i = oh+1, j = ow+1
-      q.KH = 3; q.KW = 3; q.pad = 0; q.reflect = 0;  // taps i-1..i+1 = oh..oh+2: a VALID 3x3 gather
-      q.Ktot = 9 * d->Cin; q.M = d->B * q.Ho * q.Wo;
-      q.dy_sw = 2 * d->Cout; q.dy_sh = (long long)2 * Wo * d->Cout;
-      q.dy_off = ((long long)(2 + a) * Wo + 2 + b) * d->Cout;
+      const WgradParams q = subpixel_phase_params(p, d, Wo, ph);
       rc = run_wgrad(q, sp.phase, aligned, dwc + (long long)ph * d->Cout * 9 * d->Cin, db, 0.0f, 1.0f, slabs, st);
       if (rc) return rc;
     }
@@ -1344,9 +1437,8 @@ extern "C" int munit_conv2d_wgrad(const munit_conv_desc* d, const void* x, const
                        reinterpret_cast<const float*>(x), reinterpret_cast<f32x4*>(x4), npix);
     MUNIT_CHECK_ARG(d->in_dtype == MUNIT_DTYPE_F32, "conv2d_wgrad: 3-channel inputs are fp32");
     MUNIT_CHECK_LAUNCH("pad3to4");
-    WgradParams q = p;
-    q.x = x4; q.Cin = 4; q.Ktot = d->KH * d->KW * 4; q.x_bf16 = 0;
-    q.ct = 0;   // 4 channels per tap: not a multiple of the bf16 K granularity, stays fp32
+    WgradParams q = cin3_params(p, d);
+    q.x = x4;
     rc = run_wgrad(q, cp.pl, true, dw4, db, 0.0f, beta, slabs, st);
     if (rc) return rc;
     const long long n3 = (long long)d->Cout * d->KH * d->KW * 3;

@@ -392,6 +392,30 @@ class _Branches:
                 t.record_stream(self.main)
 
 
+BF16S_MAX_PIXELS = 1 << 23
+
+
+def bf16s_refusal(hyperparameters):
+    """Why `precision: bf16s` cannot run this configuration, or None.  Refused here, up front, rather than by a kernel
+    entry point in the middle of a backward pass."""
+    dim = hyperparameters["gen"]["dim"]
+    if dim % 64 != 0:
+        return ("munit_amd: precision 'bf16s' keeps the generator's activations as bf16 tensors, whose kernels "
+                "work on 64-channel rows: gen.dim must be a multiple of 64 (got %d)" % dim)
+    dims = (hyperparameters["input_dim_a"], hyperparameters["input_dim_b"])
+    if dims != (3, 3):
+        return ("munit_amd: precision 'bf16s' needs 3-channel images (input_dim_a = input_dim_b = 3, got %d and %d): the "
+                "backward-weight kernels pair an fp32 image with bf16 activations for three channels only" % dims)
+    # the backward-weight kernels read bf16 tensors through the 24-bit pixel arithmetic of their fast loader only
+    # (conv_wgrad.hip, wgrad_form): the layers at the crop's own resolution hold batch x height x width pixels
+    pixels = (int(hyperparameters.get("batch_size", 1)) * int(hyperparameters["crop_image_height"])
+              * int(hyperparameters["crop_image_width"]))
+    if pixels >= BF16S_MAX_PIXELS:
+        return ("munit_amd: precision 'bf16s' needs batch_size x crop_image_height x crop_image_width < 2^23 = %d pixels "
+                "(got %d): the bf16 backward-weight kernels address pixels with 24-bit multiplies" % (BF16S_MAX_PIXELS, pixels))
+    return None
+
+
 class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
     def __init__(self, hyperparameters):
         super(MUNIT_Trainer, self).__init__()
@@ -443,9 +467,9 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         else:
             raise ValueError("self.gen_state unknown value: %r" % (self.gen_state,))
         if self.precision == "bf16s":
-            if hyperparameters["gen"]["dim"] % 64 != 0:
-                raise ValueError("munit_amd: precision 'bf16s' keeps the generator's activations as bf16 tensors, whose kernels "
-                                 "work on 64-channel rows: gen.dim must be a multiple of 64 (got %d)" % hyperparameters["gen"]["dim"])
+            why = bf16s_refusal(hyperparameters)
+            if why is not None:
+                raise ValueError(why)
             for m in self.modules():
                 if isinstance(m, ContentEncoder):
                     m.store_dtype = torch.bfloat16

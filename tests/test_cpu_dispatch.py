@@ -31,9 +31,39 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PASSES = ("fwd", "dgrad", "wgrad")
 BATCHES = (1, 2, 3, 4, 8, 16, 32)
 CROPS_256 = (64, 96, 128, 192, 256, 384, 512, (256, 512), (360, 480))
-# reachable only with a MUNIT_DEBUG_* switch set (MUNIT_DEBUG_NO_WGRAD_PK): the op tests never force a debug fallback
-DEBUG_ONLY = {"conv_lanes_wgrad_kernel"}
+# reachable only with a MUNIT_DEBUG_* switch set (MUNIT_DEBUG_NO_WGRAD_PK, both): the op tests never force a debug fallback
+DEBUG_ONLY = {"conv_lanes_wgrad_kernel", "conv_lanes_wgrad_kernel<bf16_t>"}
+# backward-data of a bf16 x against an fp32 dy outside the 3-channel image head: the entry point runs it, but no caller can
+# use it (the backward-weight of the same descriptor is refused: "bf16 x with fp32 dy exists for the 3-channel image head
+# only"), so munit_amd.ops never plans one and no op test body can drive it.  Named, not covered.
+NO_CALLER = {"conv_igemm_kernel<.., 1, %s> phases + fold_kernel<bf16_t>" % ct for ct in ("1", "2", ".")}
 SEG_CROPS = tuple(range(64, 513, 32))
+# The names of the launch branches only a descriptor with compute != 0 or a bf16 tensor can take.  The dispatch must keep
+# telling them apart: a branch that went back to reporting under its fp32 name would leave the coverage tests blind to it.
+NON_F32_FORMS = {
+    "conv_head_pk_kernel<bf16_t>", "conv_head_pk_kernel<bf16_t> (padded-domain correlation)",
+    "conv_igemm_kernel<64, true, 0, 4>", "conv_igemm_kernel<128, true, 0, 4>",
+    "conv_igemm_kernel<64, true, 0, 4> x4 sub-pixel phases + frame", "conv_igemm_kernel<128, true, 0, 4> x4 sub-pixel phases + frame",
+    "conv_igemm_kernel<.., 0, 1>", "conv_igemm_kernel<.., 0, 2>",
+    "conv_igemm_kernel<.., 0, 1> x4 sub-pixel phases + frame", "conv_igemm_kernel<.., 0, 2> x4 sub-pixel phases + frame",
+    "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps, bf16 y)",
+    "box2x2_kernel + conv_igemm_kernel<.., 1> (box-sum backward-data)", "box2x2_kernel + conv_igemm_kernel<.., 2> (box-sum backward-data)",
+    "conv_igemm_kernel<64, true, 2, 4> (LDS-patch fold)", "conv_igemm_kernel<128, true, 2, 4> (LDS-patch fold)",
+    "conv_igemm_kernel<.., 2, 1> (folded gather)", "conv_igemm_kernel<.., 2, 2> (folded gather)",
+    "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps) + fold_kernel<bf16_t>",
+    "conv_igemm_kernel<64, true, 1, 4> direct", "conv_igemm_kernel<128, true, 1, 4> direct",
+    "conv_igemm_kernel<.., 1, 1> direct", "conv_igemm_kernel<.., 1, 2> direct",
+    "conv_igemm_kernel<64, true, 1, 4> phases + fold_kernel<bf16_t>", "conv_igemm_kernel<128, true, 1, 4> phases + fold_kernel<bf16_t>",
+    "conv_igemm_kernel<64, true, 1, 4> phases + fold_kernel", "conv_igemm_kernel<128, true, 1, 4> phases + fold_kernel",
+    "conv_igemm_kernel<.., 1, 1> phases + fold_kernel", "conv_igemm_kernel<.., 1, 2> phases + fold_kernel",
+    "conv_lanes_wgrad_pk_kernel<bf16_t>", "conv_lanes_wgrad_kernel<bf16_t>",
+    "conv_wgrad_bf16s_kernel<1> + slab_reduce_kernel", "conv_wgrad_bf16s_kernel<2> + slab_reduce_kernel",
+    "conv_wgrad_bf16s_kernel<1> x4 sub-pixel phases + frame",
+    "conv_wgrad_kernel<.., 1, true, true> + slab_reduce_kernel", "conv_wgrad_kernel<.., 0, false, true> + slab_reduce_kernel",
+    "conv_wgrad_kernel<.., 0, false, true> (3 input channels padded to 4, bf16 dy)",
+    "conv_wgrad_kernel<.., 1> + slab_reduce_kernel", "conv_wgrad_kernel<.., 2> + slab_reduce_kernel",
+    "conv_wgrad_kernel<.., 1> x4 sub-pixel phases + fp32 frame", "conv_wgrad_kernel<.., 2> x4 sub-pixel phases + fp32 frame",
+}
 
 
 @pytest.fixture(scope="module")
@@ -45,12 +75,20 @@ def lib():
 # ------------------------------------------------------------------------------------------------------------------
 # layer enumeration
 # ------------------------------------------------------------------------------------------------------------------
-def _trace(run):
+_SECTION = [None]      # which sub-network the traced code is in (set by bf16s_network_layers' wrappers)
+
+
+def _trace(run, sections=None):
     """Run `run()` (oracle forward code on meta tensors) and return the conv layers it calls, in call order, as
     (cin, cout, k, stride, pad, pad_type, upsample, act, H, W) at the batch of its input.  H, W are the layer's INPUT
     extent before the fused nearest x2 (what munit_conv_desc holds); act is what the device fuses into the conv (none
-    when a norm follows: the norm kernels carry the activation then)."""
+    when a norm follows: the norm kernels carry the activation then).  `sections`: a list that receives _SECTION[0] at each
+    record."""
     rec = []
+
+    def note():
+        if sections is not None:
+            sections.append(_SECTION[0])
     st = {"ups": False, "lin_out": None}
 
     def out(x, cout, k, stride, pad):
@@ -64,6 +102,7 @@ def _trace(run):
         if ups:
             h, wd = h // 2, wd // 2
         rec.append((cin, cout, k, stride, pad, pad_type, int(ups), activ if norm_fn is None else "none", h, wd))
+        note()
         return out(x, cout, k, stride, pad)
 
     def upsample2(x):
@@ -86,11 +125,13 @@ def _trace(run):
         def conv2d(self, x, w, b=None, stride=1):
             cout, cin, k, _ = w.shape
             rec.append((cin, cout, k, stride, 0, "zero", 0, "none", x.shape[2], x.shape[3]))
+            note()
             return out(x, cout, k, stride, 0)
 
         def linear(self, x, w, b=None):
             n, k = w.shape
             rec.append((k, n, 1, 1, 0, "zero", 0, "none", 1, 1))
+            note()
             y = x.new_empty(x.shape[0], n)
             st["lin_out"] = (y, len(rec) - 1)
             return y
@@ -143,17 +184,24 @@ def production_grid():
     return grid
 
 
-def _desc(case, which):
-    """munit_conv_desc of an op case (cin, cout, k, stride, pad, pad_type, ups, act, B, H, W) for pass `which`: fp32
-    tensors and arithmetic; the activation is fused into the forward only (as munit_amd.ops plans the three passes)."""
+F32_MODE = (0, 0, 0)    # (compute, in_dtype, out_dtype) = (MUNIT_COMPUTE_*, MUNIT_DTYPE_*, MUNIT_DTYPE_*): fp32 throughout
+F32, BF16 = 0, 1        # MUNIT_DTYPE_*
+
+
+def _desc(case, which, mode=F32_MODE):
+    """munit_conv_desc of an op case (cin, cout, k, stride, pad, pad_type, ups, act, B, H, W) for pass `which`, with the
+    arithmetic and tensor types of `mode` (default: fp32 tensors and arithmetic); the activation is fused into the forward
+    only (as munit_amd.ops plans the three passes)."""
     from munit_amd._lib import ACT, PAD, ConvDesc
     cin, cout, k, stride, pad, pt, ups, act, b, h, w = case
-    return ConvDesc(b, h, w, cin, cout, k, k, stride, pad, PAD[pt], int(ups), ACT[act if which == 0 else "none"], 0.2, 0, 0, 0)
+    compute, in_dt, out_dt = mode
+    return ConvDesc(b, h, w, cin, cout, k, k, stride, pad, PAD[pt], int(ups), ACT[act if which == 0 else "none"], 0.2,
+                    compute, in_dt, out_dt)
 
 
-def kernel_names(lib, case):
+def kernel_names(lib, case, mode=F32_MODE):
     import ctypes
-    return tuple(lib.munit_conv2d_kernel_name(ctypes.byref(_desc(case, p)), p).decode() for p in range(3))
+    return tuple(lib.munit_conv2d_kernel_name(ctypes.byref(_desc(case, p, mode)), p).decode() for p in range(3))
 
 
 def macs(case):
@@ -238,12 +286,21 @@ def test_every_production_conv_form_is_covered_by_an_op_test(lib):
         "  %s %s: %s  (%s, %.2f GMAC)" % (PASSES[p], n, c, lab, macs(c) / 1e9) for (p, n), (c, lab) in sorted(missing.items()))
 
 
+def F32_FORMS(lib, lits):
+    """The literals an fp32 descriptor with fp32 arithmetic can get: those the fp32 op cases and the fp32 production grid take,
+    and the fp32 debug fallback."""
+    names = {n for _, n in covered(lib)} | {"conv_lanes_wgrad_kernel"}
+    return {n for n in lits if n in names}
+
+
 def test_every_dispatch_branch_is_covered_by_an_op_test(lib):
     lits = dispatch_literals()
     assert len(lits) >= 25, lits
-    assert DEBUG_ONLY <= set(lits), DEBUG_ONLY
-    names = {n for _, n in covered(lib)}
-    missing = [n for n in lits if n not in names and n not in DEBUG_ONLY]
+    assert DEBUG_ONLY | NO_CALLER <= set(lits), DEBUG_ONLY | NO_CALLER
+    assert NON_F32_FORMS | NO_CALLER == set(lits) - F32_FORMS(lib, lits), (NON_F32_FORMS | NO_CALLER) ^ (set(lits) - F32_FORMS(lib, lits))
+    names = {n for _, n in covered(lib) | bf16_covered(lib)}
+    assert not names & (DEBUG_ONLY | NO_CALLER), names & (DEBUG_ONLY | NO_CALLER)
+    missing = [n for n in lits if n not in names and n not in DEBUG_ONLY | NO_CALLER]
     assert not missing, "kernel names the dispatch can return that no op test runs: %s" % missing
 
 
@@ -264,6 +321,21 @@ def test_added_cases_keep_their_kernels(lib):
                 assert case[2] == 4 and case[3] == 2, "only the 4x4 / stride 2 cases run under MUNIT_WINO_S2_MIN_BLOCKS=1"
             for p, (g, w) in enumerate(zip(names(case), want)):
                 assert w is None or g == w, (case, PASSES[p], g, w)
+    # the cases added for the bf16-storage / bf16-arithmetic forms
+    from tests import test_gpu_bf16 as B16, test_gpu_bf16s as B16S
+    assert B16S.BF16S_CASES_TARGETS and B16.BF16_CASES_TARGETS
+    pinned = {(c, mode): passes for c, mode, passes in bf16_op_cases()}
+    dt = {torch.float32: F32, torch.bfloat16: BF16}
+    for case, want in B16S.BF16S_CASES_TARGETS.items():
+        ci, co, k, s, p_, u, a, b, h, w = case[:10]
+        key = ((ci, co, k, s, p_, case[12] if len(case) > 12 else "reflect", u, a, b, h, w), (1, dt[case[10]], dt[case[11]]))
+        assert case in B16S.CASES and pinned[key] == (0, 1, 2), case
+        for p, (g, w_) in enumerate(zip(kernel_names(lib, *key), want)):
+            assert w_ is None or g == w_, (case, PASSES[p], g, w_)
+    for case, want in B16.BF16_CASES_TARGETS.items():
+        assert case in B16.CASES and pinned[(case, (1, F32, F32))] == (0, 1), case
+        for p, (g, w_) in enumerate(zip(kernel_names(lib, case, (1, F32, F32)), want)):
+            assert g == w_, (case, PASSES[p], g, w_)
 
 
 def test_layer_enumeration_matches_the_parameter_list():
@@ -284,6 +356,176 @@ def test_layer_enumeration_matches_the_parameter_list():
     drec = _trace(lambda: O.dis_forward(_meta_state(dshapes), "", x, hp["dis"]))
     assert len(drec) == sum(1 for k in dshapes if k.endswith("weight")) == 15
     assert [l[8] for l in drec if l[2] == 1] == [6, 3, 1]          # the heads of the three scales (96, 48, 24 pixels in)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the bf16-storage step (`precision: bf16s`)
+# ------------------------------------------------------------------------------------------------------------------
+BF16S_COMPUTE = 1       # MUNIT_COMPUTE_BF16: ops.set_compute("bf16s") is process-wide, every conv of the step carries it
+
+
+def bf16s_generator_layers(hp_gen, input_dim, double, size):
+    """[(layer at batch 1, (compute, in_dtype, out_dtype))] of one generator in a bf16s step, in call order.  The dtypes are
+    those of the trainer's tensors: the content encoder's first conv reads the fp32 image and writes
+    ContentEncoder.store_dtype = bf16; every later conv of the content encoder and of the decoder reads bf16 and writes what
+    ops.conv2d_fwd_raw gives a bf16 input (bf16 when Cout is a multiple of 64, else fp32: the image head); the style encoder
+    and the MLP (fp32 image / fp32 style code in) stay fp32."""
+    x = torch.empty(1, input_dim, *size, device="meta")
+    g = O.GenView(_meta_state(O.gen_param_shapes(hp_gen, input_dim, double)), hp_gen, double)
+    saved = O.content_encoder, O.decoder
+
+    def within(name, fn):
+        def wrapped(*a, **k):
+            _SECTION[0] = name
+            try:
+                return fn(*a, **k)
+            finally:
+                _SECTION[0] = None
+        return wrapped
+
+    O.content_encoder, O.decoder = within("content", saved[0]), within("decoder", saved[1])
+    sections = []
+    try:
+        rec = _trace(lambda: g.decode(*g.encode(x, 1 if double else None), 1 if double else None), sections)
+    finally:
+        O.content_encoder, O.decoder = saved
+    out, first = [], True
+    for l, sec in zip(rec, sections):
+        if sec is None:
+            mode = (BF16S_COMPUTE, F32, F32)
+        else:
+            in_dt = F32 if (sec == "content" and first) else BF16
+            out_dt = BF16 if (sec == "content" and first) or l[1] % 64 == 0 else F32
+            first = first and sec != "content"
+            mode = (BF16S_COMPUTE, in_dt, out_dt)
+        out.append((l, mode))
+    return out
+
+
+def bf16s_network_layers(hp):
+    """{(layer at batch 1, mode): batch multipliers} of one config in bf16 storage (see network_layers); the discriminators
+    run on fp32 images with the step's arithmetic."""
+    size = (hp["crop_image_height"], hp["crop_image_width"])
+    layers = {}
+    for input_dim in sorted({hp["input_dim_a"], hp["input_dim_b"]}):
+        for double in (True, False):
+            for lm in bf16s_generator_layers(hp["gen"], input_dim, double, size):
+                layers.setdefault(lm, set()).add(1)
+        x = torch.empty(1, input_dim, *size, device="meta")
+        sd = _meta_state(O.dis_param_shapes(hp["dis"], input_dim))
+        for l in _trace(lambda: O.dis_forward(sd, "", x, hp["dis"])):
+            layers.setdefault((l, (BF16S_COMPUTE, F32, F32)), set()).update((1, 2))
+    return layers
+
+
+def bf16s_production_cases(refused_up_front=False):
+    """{(op case, mode): first config label} over production_grid() x BATCHES in bf16 storage, restricted to what
+    MUNIT_Trainer accepts in that mode (munit_amd.trainer.bf16s_refusal; semantic_w adds no conv on these tensors).
+    refused_up_front=True returns the complement: the configurations the trainer turns away."""
+    from munit_amd.trainer import bf16s_refusal
+    cases = {}
+    for label, hp in production_grid():
+        layers = None
+        for b in BATCHES:
+            if (bf16s_refusal(dict(hp, batch_size=b)) is not None) != refused_up_front:
+                continue
+            layers = layers or bf16s_network_layers(hp)
+            for (l, mode), mult in layers.items():
+                cin, cout, k, stride, pad, pt, ups, act, h, w = l
+                for m in sorted(mult):
+                    cases.setdefault(((cin, cout, k, stride, pad, pt, ups, act, b * m, h, w), mode), "%s B=%d" % (label, b))
+    return cases
+
+
+def bf16_op_cases():
+    """[(op case, mode, passes)] of the fp64 op tests that run under ops.set_compute("bf16s") / "bf16" / "f32x3"."""
+    from tests.test_gpu_bf16 import CASES as BF16_CASES, WGRAD_CASES
+    from tests.test_gpu_bf16s import CASES as BF16S_CASES
+    from tests.test_gpu_f32x3 import F32X3_CASES
+    from tests.test_gpu_ops import LINEAR_CASES
+    from tests.test_gpu_shapes import BF16S_TRUNK_LAYER
+    dt = {torch.float32: F32, torch.bfloat16: BF16}
+    out = [(c[:5] + (c[12] if len(c) > 12 else "reflect",) + c[5:10], (1, dt[c[10]], dt[c[11]]), (0, 1, 2)) for c in BF16S_CASES]
+    ci, co, k, s, p, u, a, b, h, w = BF16S_TRUNK_LAYER
+    out.append(((ci, co, k, s, p, "reflect", u, a, b, h, w), (1, BF16, BF16), (0, 1, 2)))
+    out += [(tuple(c), (1, F32, F32), (0, 1)) for c in BF16_CASES]     # its dw is held to the mode's loose bound only
+    out += [((ci, co, k, s, p, pt, u, "none", b, h, w), (1, F32, F32), (2,)) for ci, co, k, s, p, pt, u, b, h, w in WGRAD_CASES]
+    out += [(tuple(c), (2, F32, F32), (0, 1, 2)) for c in F32X3_CASES]
+    out += [((k, n, 1, 1, 0, "zero", 0, a, b, 1, 1), (2, F32, F32), (0, 1, 2)) for b, k, n, a in LINEAR_CASES]   # test_linear_f32x3
+    return out
+
+
+def bf16_covered(lib):
+    """{(pass, kernel name)} those op tests run; a wgrad-only case covers the wgrad pass only."""
+    return {(p, kernel_names(lib, c, mode)[p]) for c, mode, passes in bf16_op_cases() for p in passes}
+
+
+def test_every_bf16s_production_conv_form_is_covered_by_an_op_test(lib):
+    cov = covered(lib) | bf16_covered(lib)
+    prod = bf16s_production_cases()
+    missing = {}
+    for (case, mode), label in prod.items():
+        for p, name in enumerate(kernel_names(lib, case, mode)):
+            if (p, name) not in cov:
+                best = missing.get((p, name))
+                if best is None or macs(case) < macs(best[0]):
+                    missing[(p, name)] = (case, mode, label)
+    assert len(prod) > 1000, len(prod)
+    assert not missing, ("kernel forms a bf16-storage step dispatches to that no op test runs (cheapest layer of each, with its "
+                         "(compute, in_dtype, out_dtype)):\n" + "\n".join(
+                             "  %s %s: %s %s  (%s, %.2f GMAC)" % (PASSES[p], n, c, m, lab, macs(c) / 1e9)
+                             for (p, n), (c, m, lab) in sorted(missing.items())))
+
+
+def test_no_bf16s_production_conv_is_refused(lib):
+    """No conv of a configuration the trainer accepts in bf16 storage is one its entry point would refuse at launch (a
+    failure inside backward); the configurations the trainer turns away do hold such layers, so the refusal is not idle."""
+    def refused(cases):
+        return sorted((PASSES[p], n, c, m, lab) for (c, m), lab in cases.items()
+                      for p, n in enumerate(kernel_names(lib, c, m)) if n.startswith("refused:") or n == "invalid")
+    bad = refused(bf16s_production_cases())
+    assert not bad, "bf16-storage layers the entry points refuse:\n" + "\n".join("  %s %s: %s %s (%s)" % r for r in bad[:20])
+    away = bf16s_production_cases(refused_up_front=True)
+    wide = {k: v for k, v in away.items() if v.startswith("config_256 512 ")}
+    assert wide and {r[:2] for r in refused(wide)} == {("wgrad", "refused: bf16 tensors need Cin % 4 == 0, Cout % 4 == 0, "
+                                                        "tensors below 2 GiB and B*H*W < 2^23")}, refused(wide)[:4]
+
+
+# (cin, cout, in_dtype, out_dtype) of default_hp(96)'s generator: the style encoder (fp32), the content encoder (fp32 image ->
+# bf16, then bf16), the MLP (fp32), the decoder (bf16 up to the fp32 image head)
+BF16S_GENERATOR_96 = ([(3, 64, F32, F32), (64, 128, F32, F32), (128, 256, F32, F32), (256, 256, F32, F32), (256, 256, F32, F32),
+                       (256, 16, F32, F32)]
+                      + [(3, 64, F32, BF16), (64, 128, BF16, BF16), (128, 256, BF16, BF16)] + [(256, 256, BF16, BF16)] * 8
+                      + [(16, 256, F32, F32), (256, 256, F32, F32), (256, 4096, F32, F32)]
+                      + [(256, 256, BF16, BF16)] * 8 + [(256, 128, BF16, BF16), (128, 64, BF16, BF16), (64, 3, BF16, F32)])
+
+
+def test_trainer_refuses_bf16s_configurations_up_front():
+    """What a bf16-storage step cannot run is a ValueError of MUNIT_Trainer.__init__ that names the bound, not an error of a
+    kernel entry point inside backward."""
+    from munit_amd import ops
+    from munit_amd.trainer import MUNIT_Trainer, bf16s_refusal
+    hp = O.default_hp(512, 32)
+    assert bf16s_refusal(dict(hp, batch_size=16)) is None and bf16s_refusal(dict(O.default_hp(256, 32))) is None
+    assert "2^23" in bf16s_refusal(hp) and "multiple of 64" in bf16s_refusal(dict(hp, gen=dict(hp["gen"], dim=96)))
+    assert "3-channel" in bf16s_refusal(dict(O.default_hp(64, 2), input_dim_a=1, input_dim_b=1))
+    small = G.merged_hp(O.default_hp, 64, dict(gen=dict(dim=64, n_res=1), dis=dict(dim=8, n_layer=1, num_scales=1)))
+    try:
+        for bad, msg in ((dict(batch_size=2048), "batch_size x crop_image_height x crop_image_width < 2\\^23"),
+                         (dict(input_dim_a=1, input_dim_b=1), "3-channel images")):
+            with pytest.raises(ValueError, match=msg):
+                MUNIT_Trainer(dict(small, precision="bf16s", **bad))
+    finally:
+        ops.set_compute("f32")
+
+
+def test_bf16s_layer_dtypes_follow_the_trainer():
+    """The dtype rule of bf16s_generator_layers, pinned on default_hp(96)'s generator (call order: style encoder, content
+    encoder, MLP, decoder)."""
+    hp = O.default_hp(96)
+    got = [(l[0], l[1], m[1], m[2]) for l, m in bf16s_generator_layers(hp["gen"], 3, False, (96, 96))]
+    assert all(m[0] == BF16S_COMPUTE for _, m in bf16s_generator_layers(hp["gen"], 3, False, (96, 96)))
+    assert got == BF16S_GENERATOR_96, got
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -48,9 +48,20 @@ CASES = [
     (32, 48, 3, 1, 1, "zero", 0, "relu", 2, 9, 11),
     (256, 256, 3, 1, 1, "reflect", 0, "relu", 3, 33, 17),    # several tiles, ragged
 ]
+# Cases added for forms tests/test_cpu_dispatch.py found no op test behind; BF16_CASES_TARGETS pins the (forward, backward-data)
+# kernel names each was added for (test_cpu_dispatch.test_added_cases_keep_their_kernels).
+BF16_CASES_TARGETS = {
+    # the MLP's linears in a bf16 / bf16s step: backward-data of a 1x1 layer written directly by the CT = 1 tile
+    (256, 256, 1, 1, 0, "zero", 0, "relu", 8, 1, 1): ("conv_igemm_kernel<.., 0, 1>", "conv_igemm_kernel<.., 1, 1> direct"),
+    # box-sum backward-data of an up-sampling conv (8x8 and up) with bf16 operands
+    (128, 64, 5, 1, 2, "reflect", 1, "none", 1, 8, 8): ("conv_igemm_kernel<.., 0, 1> x4 sub-pixel phases + frame",
+                                                        "box2x2_kernel + conv_igemm_kernel<.., 1> (box-sum backward-data)"),
+}
+CASES += list(BF16_CASES_TARGETS)
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "c%d-%d_k%ds%d_u%d" % (c[0], c[1], c[2], c[3], c[6]))
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "c%d-%d_k%ds%d_u%d" % (c[0], c[1], c[2], c[3], c[6])
+                         + ("_%dx%d" % (c[9], c[10]) if c in BF16_CASES_TARGETS else ""))
 def test_conv_bf16_forward_and_dgrad(case):
     from munit_amd import ops
     cin, cout, k, stride, pad, pt, ups, act, B, H, W = case
@@ -83,6 +94,8 @@ def test_conv_bf16_forward_and_dgrad(case):
     dy = rnd(tuple(y_exact.shape), 4)
     y_rounded.backward(dy)
     y.backward(dy.float().to(dev()))
+    print("measured:", case, "fwd %.3g / %.3g dx %.3g dw %.3g" % (nerr(y, y_rounded), nerr(y, y_exact), nerr(xd.grad, xq.grad),
+                                                                   nerr(wd.grad, wq.grad)))
     assert nerr(xd.grad, xq.grad) <= BF16_VS_ORACLE, ("dx", nerr(xd.grad, xq.grad))
     assert nerr(wd.grad, wq.grad) <= BF16_VS_ORACLE, ("dw", nerr(wd.grad, wq.grad))
 

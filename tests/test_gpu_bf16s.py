@@ -59,19 +59,43 @@ CASES = [
     (3, 64, 7, 1, 3, 0, "none", 2, 20, 24, F32, BF),       # first layer: fp32 image in, bf16 out
     (64, 3, 7, 1, 3, 0, "tanh", 2, 16, 12, BF, F32),       # image head: bf16 in, fp32 image out
 ]
+# Cases added for the forms tests/test_cpu_dispatch.py found no op test behind (the bf16-storage production grid and the
+# name literals of the dispatch), each the cheapest layer of its form shrunk as far as the form's predicate allows; a 13th
+# element is the padding mode (default reflect).  BF16S_CASES_TARGETS pins the (forward, backward-data, backward-weight)
+# kernel names each was added for (None: not pinned); test_cpu_dispatch.test_added_cases_keep_their_kernels checks them.
+_IG = "conv_igemm_kernel"
+BF16S_CASES_TARGETS = {
+    # nearest x2 + 5x5 with ZERO padding (zero_pad_full_width's decoder): no sub-pixel form, the plain bf16 tile at bn = 64
+    (128, 64, 5, 1, 2, 1, "none", 1, 10, 6, BF, BF, "zero"): (_IG + "<64, true, 0, 4>", _IG + "<128, true, 1, 4> phases + fold_kernel<bf16_t>", None),
+    # 64 input channels: the bf16 LDS-patch backward-data at bn = 64
+    (64, 128, 3, 1, 1, 0, "none", 2, 8, 8, BF, BF): (_IG + "<128, true, 0, 4>", _IG + "<64, true, 2, 4> (LDS-patch fold)", None),
+    # 1x1 on bf16 tensors: backward-data written directly (no fold), both tile widths
+    (64, 128, 1, 1, 0, 0, "none", 2, 6, 5, BF, BF, "zero"): (_IG + "<128, true, 0, 4>", _IG + "<64, true, 1, 4> direct", None),
+    (128, 128, 1, 1, 0, 0, "none", 2, 6, 5, BF, BF, "zero"): (_IG + "<128, true, 0, 4>", _IG + "<128, true, 1, 4> direct", None),
+    # fp32 in, bf16 out on 64-multiples of channels: bf16 dy through the phase form into an fp32 dx, fp32 x against a bf16 dy
+    # in the register-loader backward-weight
+    (64, 64, 4, 2, 1, 0, "none", 1, 8, 8, F32, BF): (_IG + "<.., 0, 1>", _IG + "<64, true, 1, 4> phases + fold_kernel",
+                                                     "conv_wgrad_kernel<.., 0, false, true> + slab_reduce_kernel"),
+    (128, 64, 4, 2, 1, 0, "none", 1, 8, 8, F32, BF): (_IG + "<.., 0, 1>", _IG + "<128, true, 1, 4> phases + fold_kernel",
+                                                      "conv_wgrad_kernel<.., 0, false, true> + slab_reduce_kernel"),
+}
+CASES += list(BF16S_CASES_TARGETS)
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: "c%d-%d_k%ds%d_u%d" % (c[0], c[1], c[2], c[3], c[5]))
+@pytest.mark.parametrize("case", CASES, ids=lambda c: "c%d-%d_k%ds%d_u%d%s" % (c[0], c[1], c[2], c[3], c[5], "_" + c[12] if len(c) > 12 else ""))
 def test_conv_bf16_storage(case):
     from munit_amd import ops
-    cin, cout, k, stride, pad, ups, act, B, H, W, din, dout = case
+    cin, cout, k, stride, pad, ups, act, B, H, W, din, dout = case[:12]
+    pt = case[12] if len(case) > 12 else "reflect"
     x = rnd((B, cin, H, W), 1)
     w = rnd((cout, cin, k, k), 2, (2.0 / (cin * k * k)) ** 0.5)
     b = rnd((cout,), 3, 0.1)
-    xq = r16(x) if din == BF else x.float().double()
+    # (an fp32 input of a layer on the MFMA path is rounded to bf16 when it is staged: it gets bf16-VALUED data, like a bf16
+    # input, so that only the kernel's own arithmetic is measured)
+    xq = r16(x) if din == BF or cin % 64 == 0 else x.float().double()
     wq = r16(w) if cin % 64 == 0 and cout != 3 else w.float().double()    # layers off the MFMA path multiply in fp32
     xr, wr, br = xq.clone().requires_grad_(True), wq.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    yr = O.conv_block(O.upsample2(xr) if ups else xr, wr, br, stride, pad, "reflect", None, act)
+    yr = O.conv_block(O.upsample2(xr) if ups else xr, wr, br, stride, pad, pt, None, act)
     dy = rnd(tuple(yr.shape), 4)
     dyq = r16(dy) if dout == BF else dy.float().double()
     yr.backward(dyq)
@@ -79,15 +103,27 @@ def test_conv_bf16_storage(case):
     xd = to_dev(xq, din).requires_grad_(True)
     wd = w.float().to(dev()).contiguous(memory_format=torch.channels_last).requires_grad_(True)
     bd = b.float().to(dev()).requires_grad_(True)
-    y = ops.conv2d(xd, wd, bd, stride, pad, "reflect", bool(ups), act, out_dtype=dout)
+    y = ops.conv2d(xd, wd, bd, stride, pad, pt, bool(ups), act, out_dtype=dout)
     assert y.dtype == dout and tuple(y.shape) == tuple(yr.shape)
-    loose = bool(ups)      # the sub-pixel form merges the 5x5 weights in fp32 BEFORE rounding them to bf16
+    loose = bool(ups) and pt == "reflect"    # the sub-pixel form merges the 5x5 weights in fp32 BEFORE rounding them to bf16
+    print("measured:", case, "fwd %.3g" % nerr(y, yr))
     assert nerr(y, yr) <= (MODE_TOL if loose else (BF16_OUT if dout == BF else 1e-4)), ("fwd", nerr(y, yr))
     y.backward(to_dev(dyq, dout))
-    assert xd.grad.dtype == din
+    assert xd.grad.dtype == din and wd.grad.dtype == F32 and bd.grad.dtype == F32
+    print("measured:", case, "dx %.3g dw %.3g db %.3g" % (nerr(xd.grad, xr.grad), nerr(wd.grad, wr.grad), nerr(bd.grad, br.grad)))
     assert nerr(xd.grad, xr.grad) <= (BF16_OUT if din == BF else 1e-4), ("dx", nerr(xd.grad, xr.grad))
     assert nerr(wd.grad, wr.grad) <= SHARP, ("dw", nerr(wd.grad, wr.grad))
     assert nerr(bd.grad, br.grad) <= SHARP, ("db", nerr(bd.grad, br.grad))
+
+
+@pytest.mark.parametrize("case", [c for c in BF16S_CASES_TARGETS if c[10] == BF and c[11] == BF],
+                         ids=lambda c: "c%d-%d_k%ds%d_u%d" % (c[0], c[1], c[2], c[3], c[5]))
+def test_added_bf16_tensor_cases_keep_the_entry_point_contract(case):
+    """Guard bands, NaN poison, full writes, determinism and the workspace size of the raw entry points (tests/conv_contract.py)
+    on the added cases whose tensors are bf16 on both sides."""
+    from tests.conv_contract import check_conv_case
+    cin, cout, k, stride, pad, ups, act, B, H, W = case[:10]
+    check_conv_case((cin, cout, k, stride, pad, case[12] if len(case) > 12 else "reflect", ups, act, B, H, W), bf16=True)
 
 
 def test_prepared_bf16_images_follow_the_optimizer():

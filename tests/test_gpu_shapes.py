@@ -203,6 +203,10 @@ def test_norm_at_baseline_shape(case):
         assert nerr(mine.grad, ref.grad) <= BWD_TOL, (name, nerr(mine.grad, ref.grad))
 
 
+# cin, cout, k, stride, pad, ups, act, B, H, W (reflect padding, bf16 in and out): read by tests/test_cpu_dispatch.py
+BF16S_TRUNK_LAYER = (256, 256, 3, 1, 1, 0, "none", 32, 64, 64)
+
+
 def test_bf16s_trunk_layer_at_config3_batch():
     """BASELINE.json configs[2] (256x256, batch 32, bf16 storage): the residual-trunk layer on bf16 tensors at B = 32 against
     fp64 on the same bf16-valued operands -- bf16 outputs to bf16 rounding, the fp32 weight gradient to fp32-accumulation
@@ -210,7 +214,7 @@ def test_bf16s_trunk_layer_at_config3_batch():
     from munit_amd import ops
     BF = torch.bfloat16
     r16 = lambda t: t.float().bfloat16().double()
-    B, C, H, W = 32, 256, 64, 64
+    C, _, _, _, _, _, _, B, H, W = BF16S_TRUNK_LAYER
     ops.set_compute("bf16s")
     try:
         x, w, b = r16(rnd((B, C, H, W), 1)), rnd((C, C, 3, 3), 2, (2.0 / (C * 9)) ** 0.5), rnd((C,), 3, 0.1)
