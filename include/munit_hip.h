@@ -108,7 +108,15 @@ int munit_conv2d_fwd(const munit_conv_desc* d, const void* x, const float* w, co
 /* backward-data (autograd of the sites above): dx[B][H][W][Cin] from dy[B][Ho][Wo][Cout]
  * (dy is the gradient w.r.t. the PRE-activation output; use munit_act_bwd first when an
  * activation was fused).  Handles the adjoint of reflect padding (border fold-add) and of
- * the nearest upsample (2x2 sum).  If add != NULL, dx = result + add (same shape). */
+ * the nearest upsample (2x2 sum).  If add != NULL, dx = result + add (same shape).
+ * Rounding of a bf16 dx (in_dtype = bf16).  The LDS-patch and the direct (1x1) forms round the fp32 sum once.  The
+ * strided, up-sampling and 3-output-channel layers ("... + fold_kernel<bf16_t>" in munit_conv2d_kernel_name; a direct
+ * form given `add` as well) round TWICE, by design, to halve the traffic of the padded-domain buffer: the gradient
+ * w.r.t. the padded (and up-sampled) input is stored as bf16, the fold sums n of those values in fp32 (n = 1 at an
+ * interior pixel of a strided layer, 4 under the nearest x2, up to 4 x 9 = 36 at a mirrored corner of an up-sampling
+ * layer), adds `add`, and rounds once more.  Worst case: n / 2 ulps of the largest folded value plus half an ulp of
+ * the result (|error| <= n * 2^-8 * max|g| + ulp(dx) / 2); with n = 1 the second rounding is the identity.  The folded
+ * gathers take no `add` with a bf16 dx (refused).  tests/test_gpu_exact.py pins both behaviours bit for bit. */
 size_t munit_conv2d_dgrad_workspace_bytes(const munit_conv_desc* d);
 int munit_conv2d_dgrad(const munit_conv_desc* d, const void* dy, const float* w, const void* add,
                        void* dx, void* ws, size_t ws_bytes, munit_stream_t stream);

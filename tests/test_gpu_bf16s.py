@@ -5,7 +5,11 @@ fp32.  Checks, all against the fp64 oracle evaluated on the SAME bf16-valued inp
 arithmetic is measured):
   * a bf16 output must equal the fp64 result to bf16 rounding (2^-9 relative to the element, asserted as 8e-3 of the
     tensor maximum) and fp32 outputs (weight gradients, statistics, the image head) to fp32-accumulation accuracy;
-  * the stated 2e-2 of the mode against the unrounded oracle, and the whole step against the fp32 step."""
+  * the stated 2e-2 of the mode against the unrounded oracle, and the whole step against the fp32 step.
+These bounds absorb the output rounding and are wide enough for a dropped tap to pass.  The sharp criteria live in
+tests/test_gpu_exact.py: every conv case below, the sub-pixel forms included, bit for bit on integer-lattice data (exact
+and rounding regimes, one or two roundings by kernel name), munit_l1_mean_bwd_bf16 exactly, and the norm kernels per
+element to half a bf16 ulp with an unbiased rounding error."""
 import pytest
 import torch
 
