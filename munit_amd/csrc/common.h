@@ -87,8 +87,14 @@ double munit_igemm_executed_flops(const munit_conv_desc* d, int pass);
 const char* munit_igemm_kernel_name(const munit_conv_desc* d, int pass);
 
 // conv_small.hip: channel-per-lane kernels for convolutions with 3 channels on one side
-bool munit_small_fwd_supported(const munit_conv_desc* d);
-bool munit_small_wgrad_supported(const munit_conv_desc* d);
+bool munit_small_fwd_supported(const munit_conv_desc* d);   // geometry alone
+// ... with the pass's A/B switch: the one question the pass's plan asks
+bool munit_small_fwd_ok(const munit_conv_desc* d);
+bool munit_small_wgrad_ok(const munit_conv_desc* d);
+// the kernel munit_small_fwd / munit_small_wgrad launches for a supported descriptor (Cin: its input channels)
+enum SmallFwdKernel { SMALL_FWD_PK, SMALL_FWD_MFMA, SMALL_FWD_PATCH };   // conv_head_pk / conv_head_mfma / conv_patch_fwd
+SmallFwdKernel munit_small_fwd_kernel(int Cin);
+bool munit_small_wgrad_pk();   // conv_lanes_wgrad_pk_kernel, else conv_lanes_wgrad_kernel
 // x is read as d->in_dtype (fp32 or bf16); y is always fp32 (3 channels); ws: munit_small_fwd_workspace(d) bytes
 size_t munit_small_fwd_workspace(const munit_conv_desc* d);
 int munit_small_fwd(const munit_conv_desc* d, int Ho, int Wo, const void* x, const float* w, const float* bias,

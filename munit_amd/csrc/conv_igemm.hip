@@ -1265,18 +1265,15 @@ bool wino_geometry_ok(const munit_conv_desc* d) {
          d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->upsample == 0 && d->act != MUNIT_ACT_TANH;
 }
 bool wino_fwd_ok(const munit_conv_desc* d) { return wino_geometry_ok(d) && munit_wino_ok(d->B, d->H, d->W, d->Cin, d->Cout); }
-// MUNIT_WINO_S2_MIN_BLOCKS: developer override of the threshold (tests use 1 to push small shapes through the kernel)
-long long wino_s2_min_blocks() {
-  static const long long v = getenv("MUNIT_WINO_S2_MIN_BLOCKS") ? atoll(getenv("MUNIT_WINO_S2_MIN_BLOCKS")) : 192;
-  return v;
-}
-// Backward-data takes the Winograd form further down: its alternative is four phase launches of the implicit GEMM plus the
-// fold kernel.  Measured per launch (tools/time_layers.py s2small, round 4): 144 blocks (discriminator 256->512 at 32x32, fake +
-// real) 282 -> 166 us, 128 blocks (128->256 at 64x64) 153 -> 93, 124 blocks 77 -> 58; 80 blocks 138 -> 160 and 72 blocks
-// 85 -> 90 the other way.
-long long wino_s2_dgrad_min_blocks() {
-  static const long long v = getenv("MUNIT_WINO_S2_MIN_BLOCKS") ? atoll(getenv("MUNIT_WINO_S2_MIN_BLOCKS")) : 100;
-  return v;
+// Block-count threshold of the 4x4 / stride 2 Winograd forms: 192 forward, 100 backward-data; MUNIT_WINO_S2_MIN_BLOCKS is the
+// developer override of both (tests use 1 to push small shapes through the kernel).  Backward-data takes the form further down:
+// its alternative is four phase launches of the implicit GEMM plus the fold kernel.  Measured per launch (tools/time_layers.py
+// s2small, round 4): 144 blocks (discriminator 256->512 at 32x32, fake + real) 282 -> 166 us, 128 blocks (128->256 at 64x64)
+// 153 -> 93, 124 blocks 77 -> 58; 80 blocks 138 -> 160 and 72 blocks 85 -> 90 the other way.
+long long wino_s2_min_blocks(bool dgrad) {
+  static const char* const e = getenv("MUNIT_WINO_S2_MIN_BLOCKS");   // read once per process
+  static const long long v = e ? atoll(e) : 0;
+  return e ? v : dgrad ? 100 : 192;
 }
 // 4x4 / stride 2 / pad 1 fp32 layers (encoder down-sampling, discriminators): F(3x3, 2x2) over the four input phases
 bool wino_s2_fwd_ok(const munit_conv_desc* d) {
@@ -1285,7 +1282,7 @@ bool wino_s2_fwd_ok(const munit_conv_desc* d) {
          munit_wino_ok(d->B, d->H, d->W, d->Cin, d->Cout) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINOGRAD_S2") &&
          // one block per CU and no split over K: only where the tile list fills most of the chip (the small layers of the
          // style encoder and the discriminators stay on the implicit-GEMM kernel and its split-K)
-         (long long)cdiv((long long)d->B * cdiv(d->H / 2, 3) * cdiv(d->W / 2, 3), 64) * (d->Cout / 64) >= wino_s2_min_blocks();
+         (long long)cdiv((long long)d->B * cdiv(d->H / 2, 3) * cdiv(d->W / 2, 3), 64) * (d->Cout / 64) >= wino_s2_min_blocks(false);
 }
 // backward-data of those layers: dy has extent H/2 x W/2 and Cout channels (the contraction), dx Cin channels
 bool wino_s2_dgrad_ok(const munit_conv_desc* d) {
@@ -1296,46 +1293,107 @@ bool wino_s2_dgrad_ok(const munit_conv_desc* d) {
   const int Hd = d->H / 2, Wd = d->W / 2;
   if (d->pad_mode == MUNIT_PAD_REFLECT && (Hd % 3 == 0 || Wd % 3 == 0)) return false;   // fold pairs must share a 3x3 tile
   if ((long long)d->B * d->H * d->W * std::max(d->Cin, d->Cout) >= (1ll << 29)) return false;
-  return (long long)cdiv((long long)d->B * cdiv(Hd + 1, 3) * cdiv(Wd + 1, 3), 64) * (d->Cin / 64) * 4 >= wino_s2_dgrad_min_blocks();
+  return (long long)cdiv((long long)d->B * cdiv(Hd + 1, 3) * cdiv(Wd + 1, 3), 64) * (d->Cin / 64) * 4 >= wino_s2_min_blocks(true);
 }
 // the four 3x3 phase convs of a sub-pixel up-sampling layer (over the SOURCE image) through the Winograd kernel
-bool subpixel_wino_ok(const munit_conv_desc* d) {
-  return subpixel_ok(d) && d->compute == MUNIT_COMPUTE_F32 && d->in_dtype == MUNIT_DTYPE_F32 && d->out_dtype == MUNIT_DTYPE_F32 &&
+bool subpixel_wino_ok(const munit_conv_desc* d) {   // (asked where subpixel_ok holds)
+  return d->compute == MUNIT_COMPUTE_F32 && d->in_dtype == MUNIT_DTYPE_F32 && d->out_dtype == MUNIT_DTYPE_F32 &&
          d->act != MUNIT_ACT_TANH && munit_wino_ok(d->B, d->H, d->W, d->Cin, d->Cout);
 }
 
-// forward: which re-laid-out weight image the pass multiplies by (MUNIT_PREP_NONE: w as it is) and its size
-munit_prep_item fwd_prep_item(const munit_conv_desc* d, const float* w, float* wp) {
-  munit_prep_item it{w, wp, d->Cout, d->KH, d->KW, d->Cin, MUNIT_PREP_NONE, 1, 0};
-  const bool small = munit_small_fwd_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_FWD");
-  if (small) return it;
-  it.bf16 = d->in_dtype == MUNIT_DTYPE_BF16;
-  if (subpixel_ok(d)) it.kind = subpixel_wino_ok(d) ? MUNIT_PREP_SUBPIXEL_WINOGRAD : MUNIT_PREP_SUBPIXEL;
-  else if (wino_fwd_ok(d)) it.kind = MUNIT_PREP_WINOGRAD;
-  else if (wino_s2_fwd_ok(d)) it.kind = MUNIT_PREP_WINOGRAD_S2;
-  else if (it.bf16) it.kind = MUNIT_PREP_CAST;
-  return it;
+// The route of a forward pass and what follows from it, decided HERE and nowhere else: workspace, weight image, launch, kernel
+// name and executed FLOPs all read the plan.  The tests run in the order written, and at most one of them holds:
+//   * SMALL needs a 7x7 filter, the sub-pixel routes 5x5, WINO 3x3 and WINO_S2 4x4;
+//   * the sub-pixel routes need upsample == 1, every other special route upsample == 0;
+//   * CIN4 needs Cin == 3, SMALL Cin % 16 == 0, the Winograd routes Cin % 8 == 0 and sub-pixel Cin % 32 == 0.
+enum FwdRoute { FWD_SMALL, FWD_SUBPIXEL_WINO, FWD_SUBPIXEL, FWD_WINO, FWD_WINO_S2, FWD_CIN4, FWD_IGEMM };
+struct FwdPlan {
+  int rc;                 // of munit_conv2d_out_hw: nothing else is filled in unless it is MUNIT_OK
+  FwdRoute route;
+  int Ho, Wo;
+  munit_prep_item prep;   // the weight image the pass multiplies by (MUNIT_PREP_NONE: w as it is), pointers null
+  Cin4Plan cin4;          // FWD_CIN4: workspace = [4-channel image][padded weights]
+  int ring;               // sub-pixel routes: width of the frame the generic 25-tap gather recomputes
+  size_t img_bytes, ws_bytes;   // every other route: workspace = [weight image, when the caller keeps none][split-K slabs]
+};
+FwdPlan plan_fwd(const munit_conv_desc* d) {
+  FwdPlan pl{};
+  if ((pl.rc = munit_conv2d_out_hw(d, &pl.Ho, &pl.Wo)) != MUNIT_OK) return pl;
+  const int Ho = pl.Ho, Wo = pl.Wo, Ktot = d->KH * d->KW * d->Cin;
+  const bool bf16 = d->in_dtype == MUNIT_DTYPE_BF16;
+  int kind = bf16 ? MUNIT_PREP_CAST : MUNIT_PREP_NONE;
+  if (munit_small_fwd_ok(d)) {
+    pl.route = FWD_SMALL; kind = MUNIT_PREP_NONE;
+  } else if (subpixel_ok(d)) {   // the Winograd phases replicate the source edge, which leaves a ring one pixel wide (see the launch)
+    const bool wino = subpixel_wino_ok(d);
+    pl.route = wino ? FWD_SUBPIXEL_WINO : FWD_SUBPIXEL; kind = wino ? MUNIT_PREP_SUBPIXEL_WINOGRAD : MUNIT_PREP_SUBPIXEL;
+    pl.ring = wino ? 1 : 2;
+  } else if (wino_fwd_ok(d)) {
+    pl.route = FWD_WINO; kind = MUNIT_PREP_WINOGRAD;
+  } else if (wino_s2_fwd_ok(d)) {
+    pl.route = FWD_WINO_S2; kind = MUNIT_PREP_WINOGRAD_S2;
+  } else {
+    pl.route = cin4_fwd_ok(d) ? FWD_CIN4 : FWD_IGEMM;
+  }
+  pl.prep = munit_prep_item{nullptr, nullptr, d->Cout, d->KH, d->KW, d->Cin, kind, 1, pl.route != FWD_SMALL && bf16};
+  pl.ws_bytes = pl.img_bytes = kind == MUNIT_PREP_NONE ? 0 : align_up((size_t)prep_elems(pl.prep) * (bf16 ? 2 : 4), 256);
+  if (pl.route == FWD_SMALL) pl.ws_bytes = munit_small_fwd_workspace(d);
+  if (pl.route == FWD_CIN4) pl.cin4 = plan_cin4((long long)d->B * d->H * d->W, d->Cout, d->KH * d->KW), pl.ws_bytes = pl.cin4.x4_bytes + pl.cin4.w4_bytes;
+  // bf16 inputs get no split-K slabs (launch_igemm), nor does a head layer that MUNIT_DEBUG_NO_SMALL_FWD sent to FWD_IGEMM
+  if (bf16 || munit_small_fwd_supported(d)) return pl;
+  if (pl.ring)   // the frame launch (few tiles, 25-tap K), sized for either ring width
+    pl.ws_bytes += std::max(splitk_bytes(d->B * (4 * Wo + 4 * (Ho - 4)), d->Cout, Ktot, 1), splitk_bytes(d->B * (2 * Wo + 2 * (Ho - 2)), d->Cout, Ktot, 1));
+  if (pl.route == FWD_IGEMM) pl.ws_bytes += splitk_bytes(d->B * Ho * Wo, d->Cout, Ktot, 1);
+  return pl;
 }
-size_t prep_bytes(const munit_prep_item& it) {
-  return it.kind == MUNIT_PREP_NONE ? 0 : align_up((size_t)prep_elems(it) * (it.bf16 ? 2 : 4), 256);
+
+// Launch parameters of a conv_wino_kernel launch.  Forward: the layer itself, its 4x4 / stride 2 form, the four phase convs of a
+// sub-pixel layer; backward-data (x = dy, produced channels = Cin): the same two, and the interior of an up-sampling layer as
+// one launch over the four dy phases (Ho x Wo = the extent of dy).
+enum WinoForm { WINO_FWD, WINO_FWD_S2, WINO_FWD_SUBPIXEL, WINO_DGRAD, WINO_DGRAD_S2, WINO_DGRAD_UP };
+WinoParams wino_params(const munit_conv_desc* d, int Ho, int Wo, WinoForm f, const float* x, const float* u, const float* bias, float* y) {
+  const bool fwd = f <= WINO_FWD_SUBPIXEL, refl = d->pad_mode == MUNIT_PAD_REFLECT;
+  WinoParams q{};
+  q.x = x; q.u = u; q.bias = bias; q.y = y;
+  q.B = d->B; q.H = d->H; q.W = d->W;
+  q.xc = fwd ? d->Cin : d->Cout; q.N = fwd ? d->Cout : d->Cin; q.K = q.xc;
+  const int oh = fwd ? Ho : d->H, ow = fwd ? Wo : d->W;   // extent of y
+  q.y_sw = q.N; q.y_sh = (long long)ow * q.N; q.y_sb = (long long)oh * ow * q.N;
+  q.mode = refl ? 0 : 1;
+  q.th = d->H / 2; q.tw = d->W / 2;
+  q.act = fwd ? d->act : MUNIT_ACT_NONE; q.slope = fwd ? d->slope : 0.f;
+  switch (f) {
+    case WINO_FWD: break;
+    case WINO_FWD_S2:
+      q.K = 4 * q.xc; q.s2 = 1; q.Ho = Ho; q.Wo = Wo;
+      q.th = cdiv(Ho, 3); q.tw = cdiv(Wo, 3);
+      break;
+    case WINO_FWD_SUBPIXEL:   // phase (a, b) writes every other output row / column
+      q.y_sw *= 2; q.y_sh *= 2; q.y_prow = (long long)Wo * d->Cout; q.y_pcol = d->Cout;
+      q.u_phase = wino_image_elems(d->Cin, d->Cout); q.phases = 4;
+      q.mode = 1; q.edge = 1;
+      break;
+    case WINO_DGRAD: q.mode = refl ? 2 : 1; break;
+    case WINO_DGRAD_S2:
+      q.H = d->H / 2; q.W = d->W / 2; q.s2 = 2; q.Ho = d->H; q.Wo = d->W;
+      q.th = cdiv(q.H + 1, 3); q.tw = cdiv(q.W + 1, 3);
+      q.u_phase = wino_image_elems(d->Cout, d->Cin); q.phases = 4;
+      break;
+    case WINO_DGRAD_UP:       // source pixels 2..H-3 x 2..W-3
+      q.H = Ho; q.W = Wo; q.K = 4 * q.xc; q.s2 = 3; q.mode = 1;
+      q.th = (d->H - 4) / 2; q.tw = (d->W - 4) / 2;
+      break;
+  }
+  q.cpp = q.xc / 8; q.NB = q.N / 64;
+  q.x_bytes = (unsigned)((size_t)d->B * q.H * q.W * q.xc * 4);
+  q.bth = cdiv(q.th, 8); q.btw = cdiv(q.tw, 8);
+  return q;
 }
 }  // namespace
 
 extern "C" size_t munit_conv2d_fwd_workspace_bytes(const munit_conv_desc* d) {
-  int Ho, Wo;
-  if (munit_conv2d_out_hw(d, &Ho, &Wo)) return 0;
-  // [weight image of the pass, when the caller keeps none][split-K slabs]
-  const size_t img = prep_bytes(fwd_prep_item(d, nullptr, nullptr));
-  if (munit_small_fwd_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_FWD")) return munit_small_fwd_workspace(d);
-  if (munit_small_fwd_supported(d) || d->in_dtype == MUNIT_DTYPE_BF16 || wino_fwd_ok(d) || wino_s2_fwd_ok(d)) return img;
-  if (cin4_fwd_ok(d)) {   // [4-channel image][padded weights]
-    const Cin4Plan c = plan_cin4((long long)d->B * d->H * d->W, d->Cout, d->KH * d->KW);
-    return c.x4_bytes + c.w4_bytes;
-  }
-  if (subpixel_ok(d))   // split-K slabs of the frame launch (few tiles, 25-tap K)
-    return img + std::max(splitk_bytes(d->B * (4 * Wo + 4 * (Ho - 4)), d->Cout, d->KH * d->KW * d->Cin, 1),     // 2-pixel frame
-                          splitk_bytes(d->B * (2 * Wo + 2 * (Ho - 2)), d->Cout, d->KH * d->KW * d->Cin, 1));    // 1-pixel ring (F(2x2,3x3) phases)
-  return img + splitk_bytes(d->B * Ho * Wo, d->Cout, d->KH * d->KW * d->Cin, 1);
+  const FwdPlan pl = plan_fwd(d);
+  return pl.rc ? 0 : pl.ws_bytes;
 }
 
 extern "C" int munit_conv2d_fwd(const munit_conv_desc* d, const void* x, const float* w,
@@ -1347,107 +1405,61 @@ extern "C" int munit_conv2d_fwd(const munit_conv_desc* d, const void* x, const f
 extern "C" int munit_conv2d_fwd_prepared(const munit_conv_desc* d, const void* x, const float* w, const void* wp,
                                          const float* bias, void* y, void* ws, size_t ws_bytes,
                                          munit_stream_t stream) {
-  int Ho, Wo;
-  int rc = munit_conv2d_out_hw(d, &Ho, &Wo);
+  const FwdPlan pl = plan_fwd(d);
+  int rc = pl.rc;
   if (rc) return rc;
+  const int Ho = pl.Ho, Wo = pl.Wo;
   MUNIT_CHECK_ARG(x && w && y, "conv2d_fwd: null pointer");
+  MUNIT_CHECK_ARG(pl.route != FWD_SMALL || d->out_dtype == MUNIT_DTYPE_F32, "conv2d_fwd: the 3-channel image head writes fp32");
   hipStream_t st = (hipStream_t)stream;
-  if (munit_small_fwd_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_FWD")) {
-    MUNIT_CHECK_ARG(d->out_dtype == MUNIT_DTYPE_F32, "conv2d_fwd: the 3-channel image head writes fp32");
-    const size_t sneed = munit_small_fwd_workspace(d);
-    if (sneed != 0 && (ws == nullptr || ws_bytes < sneed)) {
-      munit_set_error("conv2d_fwd: workspace %zu < %zu", ws_bytes, sneed);
-      return MUNIT_ERR_WORKSPACE;
-    }
-    return munit_small_fwd(d, Ho, Wo, x, w, bias, reinterpret_cast<float*>(y), ws, st);
-  }
-  const size_t need = munit_conv2d_fwd_workspace_bytes(d);
-  if (need != 0 && (ws == nullptr || ws_bytes < need)) {
-    munit_set_error("conv2d_fwd: workspace %zu < %zu", ws_bytes, need);
+  if (pl.ws_bytes != 0 && (ws == nullptr || ws_bytes < pl.ws_bytes)) {
+    munit_set_error("conv2d_fwd: workspace %zu < %zu", ws_bytes, pl.ws_bytes);
     return MUNIT_ERR_WORKSPACE;
   }
+  if (pl.route == FWD_SMALL) return munit_small_fwd(d, Ho, Wo, x, w, bias, reinterpret_cast<float*>(y), ws, st);
   // weight image of the pass: the caller's, or built into the head of the workspace
-  munit_prep_item it = fwd_prep_item(d, w, reinterpret_cast<float*>(ws));
-  const size_t img_bytes = prep_bytes(it);
   const float* wimg = w;
-  if (it.kind != MUNIT_PREP_NONE) {
+  if (pl.prep.kind != MUNIT_PREP_NONE) {
     wimg = reinterpret_cast<const float*>(wp);
     if (wimg == nullptr) {
+      munit_prep_item it = pl.prep;
+      it.w = w; it.wp = reinterpret_cast<float*>(ws);
       rc = launch_prep_one(it, st);
       if (rc) return rc;
       wimg = it.wp;
     }
   }
-  if (it.kind == MUNIT_PREP_WINOGRAD_S2) {
-    WinoParams q{};
-    q.x = reinterpret_cast<const float*>(x); q.u = wimg; q.bias = bias; q.y = reinterpret_cast<float*>(y);
-    q.y_sw = d->Cout; q.y_sh = (long long)Wo * d->Cout; q.y_sb = (long long)Ho * Wo * d->Cout;
-    q.B = d->B; q.H = d->H; q.W = d->W; q.K = 4 * d->Cin; q.N = d->Cout; q.xc = d->Cin; q.cpp = d->Cin / 8;
-    q.s2 = 1; q.Ho = Ho; q.Wo = Wo;
-    q.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 4);
-    q.mode = d->pad_mode == MUNIT_PAD_REFLECT ? 0 : 1;
-    q.th = cdiv(Ho, 3); q.tw = cdiv(Wo, 3); q.bth = cdiv(q.th, 8); q.btw = cdiv(q.tw, 8); q.NB = d->Cout / 64;
-    q.act = d->act; q.slope = d->slope;
-    return munit_wino_launch(q, st);
+  if (pl.route == FWD_WINO || pl.route == FWD_WINO_S2 || pl.route == FWD_SUBPIXEL_WINO) {
+    // sub-pixel: the phase convolutions REPLICATE the source edge instead of padding with zeros: with x[-1] := x[0] the merged 3x3
+    // filters reproduce reflect(2) o nearest-upsample exactly for every output row / column but the outermost one (row 1
+    // reads up[-1] = up[1] = x[0], which is what the replicated pixel holds; row 0 reads up[-2] = up[2] = x[1], which it is
+    // not), so the 25-tap frame launch below recomputes a ring one pixel wide instead of two
+    const WinoForm f = pl.route == FWD_WINO ? WINO_FWD : pl.route == FWD_WINO_S2 ? WINO_FWD_S2 : WINO_FWD_SUBPIXEL;
+    rc = munit_wino_launch(wino_params(d, Ho, Wo, f, reinterpret_cast<const float*>(x), wimg, bias, reinterpret_cast<float*>(y)), st);
+    if (rc || pl.route != FWD_SUBPIXEL_WINO) return rc;
   }
-  if (it.kind == MUNIT_PREP_WINOGRAD) {
-    WinoParams q{};
-    q.x = reinterpret_cast<const float*>(x); q.u = wimg; q.bias = bias; q.y = reinterpret_cast<float*>(y);
-    q.y_sw = d->Cout; q.y_sh = (long long)d->W * d->Cout; q.y_sb = (long long)d->H * d->W * d->Cout;
-    q.B = d->B; q.H = d->H; q.W = d->W; q.K = d->Cin; q.N = d->Cout; q.xc = d->Cin; q.cpp = d->Cin / 8;
-    q.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 4);
-    q.mode = d->pad_mode == MUNIT_PAD_REFLECT ? 0 : 1;
-    q.th = d->H / 2; q.tw = d->W / 2; q.bth = cdiv(q.th, 8); q.btw = cdiv(q.tw, 8); q.NB = d->Cout / 64;
-    q.act = d->act; q.slope = d->slope;
-    return munit_wino_launch(q, st);
-  }
-  void* slabs = ws ? reinterpret_cast<char*>(ws) + img_bytes : nullptr;
-  const size_t slab_bytes = ws ? ws_bytes - img_bytes : 0;
   IgemmParams p = fwd_params(d, Ho, Wo);
   p.x = reinterpret_cast<const float*>(x); p.w = wimg; p.bias = bias; p.y = y;
-  if (cin4_fwd_ok(d)) {
+  if (pl.route == FWD_CIN4) {
     const long long npix = (long long)d->B * d->H * d->W;
-    const Cin4Plan c = plan_cin4(npix, d->Cout, d->KH * d->KW);
-    rc = build_cin4(c, reinterpret_cast<const float*>(x), npix, w, d->Cout, d->KH * d->KW, ws, st);
+    rc = build_cin4(pl.cin4, reinterpret_cast<const float*>(x), npix, w, d->Cout, d->KH * d->KW, ws, st);
     if (rc) return rc;
     p.x = reinterpret_cast<const float*>(ws);
-    p.w = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ws) + c.x4_bytes);
-    set_cin4(&p, c);
+    p.w = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ws) + pl.cin4.x4_bytes);
+    set_cin4(&p, pl.cin4);
     return launch_igemm<0>(p, 1, st);
   }
-  if (it.kind == MUNIT_PREP_SUBPIXEL || it.kind == MUNIT_PREP_SUBPIXEL_WINOGRAD) {
-    // (1) four phase convs (3x3 over the source, merged weights) write every output pixel; the 2-pixel
-    // frame, where reflect padding breaks the merge, is then (2) recomputed by the generic 25-tap gather.
-    const IgemmParams q = subpixel_phase_params(p, d, Wo);
-    int ring = 2;                             // width of the frame the generic gather recomputes
-    if (it.kind == MUNIT_PREP_SUBPIXEL_WINOGRAD) {
-      WinoParams wq{};
-      wq.x = reinterpret_cast<const float*>(x); wq.u = wimg; wq.bias = bias; wq.y = reinterpret_cast<float*>(y);
-      wq.y_sw = q.y_sw; wq.y_sh = q.y_sh; wq.y_sb = p.y_sb;
-      wq.u_phase = wino_image_elems(d->Cin, d->Cout); wq.y_prow = q.y_phase_row; wq.y_pcol = q.y_phase_col; wq.phases = 4;
-      wq.B = d->B; wq.H = d->H; wq.W = d->W; wq.K = d->Cin; wq.N = d->Cout; wq.xc = d->Cin; wq.cpp = d->Cin / 8;
-      wq.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 4);
-      wq.mode = 1;
-      // the phase convolutions REPLICATE the source edge instead of padding with zeros: with x[-1] := x[0] the merged 3x3
-      // filters reproduce reflect(2) o nearest-upsample exactly for every output row / column but the outermost one (row 1
-      // reads up[-1] = up[1] = x[0], which is what the replicated pixel holds; row 0 reads up[-2] = up[2] = x[1], which it is
-      // not), so the 25-tap frame launch below recomputes a ring one pixel wide instead of two
-      wq.edge = 1;
-      ring = 1;
-      wq.th = d->H / 2; wq.tw = d->W / 2; wq.bth = cdiv(wq.th, 8); wq.btw = cdiv(wq.tw, 8); wq.NB = d->Cout / 64;
-      wq.act = d->act; wq.slope = d->slope;
-      rc = munit_wino_launch(wq, st);
-    } else {
-      rc = launch_igemm<0>(q, 4, st);
-    }
+  if (pl.ring) {
+    // sub-pixel: (1) four phase convs (3x3 over the source, merged weights) write every output pixel; the frame, where
+    // reflect padding breaks the merge, is then (2) recomputed by the generic 25-tap gather.
+    if (pl.route == FWD_SUBPIXEL) rc = launch_igemm<0>(subpixel_phase_params(p, d, Wo), 4, st);
     if (rc) return rc;
-    set_subpixel_frame(&p, d, Ho, Wo, ring);
+    set_subpixel_frame(&p, d, Ho, Wo, pl.ring);
     // the frame launch multiplies by the original 5x5 weights: fp32 -> w itself; bf16 storage -> their bf16 copy,
     // which the image carries behind the merged phase weights
-    p.w = it.bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const bf16_t*>(wimg) + (size_t)4 * 9 * d->Cout * d->Cin) : w;
-    return launch_igemm<0>(p, 1, st, slabs, slab_bytes);
+    p.w = pl.prep.bf16 ? reinterpret_cast<const float*>(reinterpret_cast<const bf16_t*>(wimg) + (size_t)4 * 9 * d->Cout * d->Cin) : w;
   }
-  return launch_igemm<0>(p, 1, st, slabs, slab_bytes);
+  return launch_igemm<0>(p, 1, st, ws ? reinterpret_cast<char*>(ws) + pl.img_bytes : nullptr, ws ? ws_bytes - pl.img_bytes : 0);
 }
 
 namespace {
@@ -1711,18 +1723,7 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
     wt = it.wp;
   }
   if (pl.wino_s2) {
-    WinoParams q{};
-    const int Hd = d->H / 2, Wd = d->W / 2;
-    q.x = dy; q.u = wt; q.bias = nullptr; q.y = dx;
-    q.y_sw = d->Cin; q.y_sh = (long long)d->W * d->Cin; q.y_sb = (long long)d->H * d->W * d->Cin;
-    q.B = d->B; q.H = Hd; q.W = Wd; q.K = d->Cout; q.N = d->Cin; q.xc = d->Cout; q.cpp = d->Cout / 8;
-    q.s2 = 2; q.Ho = d->H; q.Wo = d->W;
-    q.x_bytes = (unsigned)((size_t)d->B * Hd * Wd * d->Cout * 4);
-    q.mode = d->pad_mode == MUNIT_PAD_REFLECT ? 0 : 1;
-    q.th = cdiv(Hd + 1, 3); q.tw = cdiv(Wd + 1, 3); q.bth = cdiv(q.th, 8); q.btw = cdiv(q.tw, 8); q.NB = d->Cin / 64;
-    q.u_phase = wino_image_elems(d->Cout, d->Cin); q.phases = 4;
-    q.act = MUNIT_ACT_NONE; q.slope = 0.f;
-    rc = munit_wino_launch(q, st);
+    rc = munit_wino_launch(wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD_S2, dy, wt, nullptr, dx), st);
     if (rc) return rc;
     if (add != nullptr) {
       long long n = (long long)d->B * d->H * d->W * d->Cin;
@@ -1733,14 +1734,7 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
     return MUNIT_OK;
   }
   if (pl.wino) {
-    WinoParams q{};
-    q.x = dy; q.u = wt; q.bias = nullptr; q.y = dx;
-    q.y_sw = d->Cin; q.y_sh = (long long)d->W * d->Cin; q.y_sb = (long long)d->H * d->W * d->Cin;
-    q.B = d->B; q.H = d->H; q.W = d->W; q.K = d->Cout; q.N = d->Cin; q.xc = d->Cout; q.cpp = d->Cout / 8;
-    q.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cout * 4);
-    q.mode = d->pad_mode == MUNIT_PAD_REFLECT ? 2 : 1;
-    q.th = d->H / 2; q.tw = d->W / 2; q.bth = cdiv(q.th, 8); q.btw = cdiv(q.tw, 8); q.NB = d->Cin / 64;
-    q.act = MUNIT_ACT_NONE; q.slope = 0.f;
+    WinoParams q = wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD, dy, wt, nullptr, dx);
     q.add = add;    // added in the kernel's epilogue (dx and add share the layout)
     return munit_wino_launch(q, st);
   }
@@ -1771,17 +1765,8 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
     if (pl.boxsum && pl.upwino) {
       // interior source pixels 2..H-3 x 2..W-3 as ONE Winograd launch: the four output phases of dy are 3x3-correlated with the
       // rotated merged filters and summed (K = 4 Cout); no box sum, no padding
-      WinoParams wq{};
-      wq.x = dy; wq.u = wt + (size_t)d->Cout * 25 * d->Cin; wq.bias = nullptr;
-      wq.y = dx + ((long long)2 * d->W + 2) * d->Cin;
-      wq.y_sw = d->Cin; wq.y_sh = (long long)d->W * d->Cin; wq.y_sb = (long long)d->H * d->W * d->Cin;
-      wq.B = d->B; wq.H = pl.Ho; wq.W = pl.Wo; wq.K = 4 * d->Cout; wq.N = d->Cin; wq.xc = d->Cout; wq.cpp = d->Cout / 8;
-      wq.s2 = 3;
-      wq.x_bytes = (unsigned)((size_t)d->B * pl.Ho * pl.Wo * d->Cout * 4);
-      wq.mode = 1;
-      wq.th = (d->H - 4) / 2; wq.tw = (d->W - 4) / 2; wq.bth = cdiv(wq.th, 8); wq.btw = cdiv(wq.tw, 8); wq.NB = d->Cin / 64;
-      wq.act = MUNIT_ACT_NONE; wq.slope = 0.f;
-      rc = munit_wino_launch(wq, st);
+      rc = munit_wino_launch(wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD_UP, dy, wt + (size_t)d->Cout * 25 * d->Cin, nullptr,
+                                         dx + ((long long)2 * d->W + 2) * d->Cin), st);
       if (rc) return rc;
       set_boxsum_frame(&p, d);
       rc = launch_igemm<2>(p, 1, st, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, pl.sk_bytes);
@@ -1859,7 +1844,9 @@ extern "C" int munit_conv2d_prep_item(const munit_conv_desc* d, int pass, const 
   MUNIT_CHECK_ARG(pass == MUNIT_PASS_FWD || pass == MUNIT_PASS_DGRAD, "conv2d_prep_item: pass must be MUNIT_PASS_FWD or _DGRAD");
   munit_prep_item it{w, wp, d->Cout, d->KH, d->KW, d->Cin, MUNIT_PREP_NONE, 1, 0};
   if (pass == MUNIT_PASS_FWD) {
-    it = fwd_prep_item(d, w, wp);
+    const FwdPlan fp = plan_fwd(d);
+    it.kind = fp.prep.kind;
+    it.bf16 = fp.prep.bf16;
   } else {
     DgradPlan pl;
     rc = plan_dgrad(d, &pl);
@@ -1914,10 +1901,10 @@ extern "C" int munit_conv2d_prepare_weights_batch(const munit_prep_item* items_d
 // 2*B*Ho*Wo*Cout*KH*KW*Cin: the sub-pixel forward runs 4 merged 3x3 phases + the 25-tap frame, the box-sum
 // backward-data one 25-tap row per interior SOURCE pixel + the frame, strided backward-data its phases over the
 // padded domain.  Valid GEMM rows only (tile padding is not counted).  bench.py reports both totals.
-// Name (as a profiler shows it) of the kernel that carries a pass of this layer.  It follows the entry points' own
-// decisions: the same predicates and plans, and igemm_form on the same launch parameters (fwd_params, dgrad_fold_params,
-// dgrad_corr_params).  A descriptor the entry point would refuse is named "refused: <why>".  The names of fp32 tensors with
-// fp32 arithmetic do not tell the loader variants (IG_DMA / IG_F32 / IG_UNALIGNED) apart; every other form has its own.
+// Name (as a profiler shows it) of the kernel that carries a pass of this layer.  The route is the one plan_fwd / plan_dgrad
+// decided for the entry point; inside a route, igemm_form (on fwd_params, dgrad_fold_params, dgrad_corr_params) and
+// munit_small_fwd_kernel are asked as the launch asks them.  A descriptor the entry point would refuse is named "refused: <why>".
+// fp32 tensors with fp32 arithmetic: the loader variants (IG_DMA / IG_F32 / IG_UNALIGNED) share a name; every other form has its own.
 namespace {
 const char* igemm_refusal(IgemmForm f) {
   switch (f) {
@@ -1931,42 +1918,46 @@ const char* igemm_refusal(IgemmForm f) {
 }  // namespace
 
 const char* munit_igemm_kernel_name(const munit_conv_desc* d, int pass) {
-  int Ho, Wo;
-  if (munit_conv2d_out_hw(d, &Ho, &Wo)) return "invalid";
   const bool refl = d->pad_mode == MUNIT_PAD_REFLECT;
   const bool x_bf16 = d->in_dtype == MUNIT_DTYPE_BF16, y_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
+  // the 3-channel head kernels: [forward | padded-domain correlation of backward-data][SmallFwdKernel][bf16 input]
+  static const char* const head[2][3][2] = {
+      {{"conv_head_pk_kernel", "conv_head_pk_kernel<bf16_t>"}, {"conv_head_mfma_kernel", "conv_head_mfma_kernel<bf16_t>"},
+       {"conv_patch_fwd_kernel", "conv_patch_fwd_kernel<bf16_t>"}},
+      {{"conv_head_pk_kernel (padded-domain correlation)", "conv_head_pk_kernel<bf16_t> (padded-domain correlation)"},
+       {"conv_head_mfma_kernel (padded-domain correlation)", "conv_head_mfma_kernel<bf16_t> (padded-domain correlation)"},
+       {"conv_patch_fwd_kernel (padded-domain correlation)", "conv_patch_fwd_kernel<bf16_t> (padded-domain correlation)"}}};
   if (pass == MUNIT_PASS_FWD) {
-    if (munit_small_fwd_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_FWD")) {
-      if (y_bf16) return "refused: the 3-channel image head writes fp32";
-      return x_bf16 ? "conv_head_pk_kernel<bf16_t>" : "conv_head_pk_kernel";
-    }
+    const FwdPlan fp = plan_fwd(d);
+    if (fp.rc) return "invalid";
+    const int Ho = fp.Ho, Wo = fp.Wo;
     IgemmParams p = fwd_params(d, Ho, Wo);
     const int bn = igemm_bn(p);
-    if (subpixel_wino_ok(d)) return "conv_wino_kernel<1, 0> x4 sub-pixel phases + conv_igemm_kernel frame";
-    if (subpixel_ok(d)) {
-      const IgemmForm ph = igemm_form(subpixel_phase_params(p, d, Wo), 0);
-      set_subpixel_frame(&p, d, Ho, Wo, 2);
-      const IgemmForm fr = igemm_form(p, 0);
-      if (igemm_refusal(ph)) return igemm_refusal(ph);
-      if (igemm_refusal(fr)) return igemm_refusal(fr);
-      if (ph != fr) return "invalid";   // (no descriptor gets here: both launches share Cin, ct and the dtypes)
-      if (ph == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 0, 4> x4 sub-pixel phases + frame"
-                                          : "conv_igemm_kernel<128, true, 0, 4> x4 sub-pixel phases + frame";
-      if (ph == IG_CT1) return "conv_igemm_kernel<.., 0, 1> x4 sub-pixel phases + frame";
-      if (ph == IG_CT2) return "conv_igemm_kernel<.., 0, 2> x4 sub-pixel phases + frame";
-      return "conv_igemm_kernel x4 sub-pixel phases + frame";
-    }
-    if (wino_fwd_ok(d)) return refl ? "conv_wino_kernel<0, 0>" : "conv_wino_kernel<1, 0>";
-    if (wino_s2_fwd_ok(d)) return refl ? "conv_wino_kernel<0, 1>" : "conv_wino_kernel<1, 1>";
-    if (cin4_fwd_ok(d)) {
-      set_cin4(&p, plan_cin4(1, d->Cout, d->KH * d->KW));
-      const IgemmForm f = igemm_form(p, 0);
-      if (igemm_refusal(f)) return igemm_refusal(f);
-      return y_bf16 ? "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps, bf16 y)"
-                    : "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps)";
+    switch (fp.route) {
+      case FWD_SMALL: return y_bf16 ? "refused: the 3-channel image head writes fp32" : head[0][munit_small_fwd_kernel(d->Cin)][x_bf16];
+      case FWD_SUBPIXEL_WINO: return "conv_wino_kernel<1, 0> x4 sub-pixel phases + conv_igemm_kernel frame";
+      case FWD_SUBPIXEL: {
+        const IgemmForm ph = igemm_form(subpixel_phase_params(p, d, Wo), 0);
+        set_subpixel_frame(&p, d, Ho, Wo, fp.ring);
+        const IgemmForm fr = igemm_form(p, 0);
+        if (igemm_refusal(ph)) return igemm_refusal(ph);
+        if (igemm_refusal(fr)) return igemm_refusal(fr);
+        if (ph != fr) return "invalid";   // (no descriptor gets here: both launches share Cin, ct and the dtypes)
+        if (ph == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 0, 4> x4 sub-pixel phases + frame"
+                                            : "conv_igemm_kernel<128, true, 0, 4> x4 sub-pixel phases + frame";
+        if (ph == IG_CT1) return "conv_igemm_kernel<.., 0, 1> x4 sub-pixel phases + frame";
+        if (ph == IG_CT2) return "conv_igemm_kernel<.., 0, 2> x4 sub-pixel phases + frame";
+        return "conv_igemm_kernel x4 sub-pixel phases + frame";
+      }
+      case FWD_WINO: return refl ? "conv_wino_kernel<0, 0>" : "conv_wino_kernel<1, 0>";
+      case FWD_WINO_S2: return refl ? "conv_wino_kernel<0, 1>" : "conv_wino_kernel<1, 1>";
+      case FWD_CIN4: set_cin4(&p, fp.cin4); break;
+      case FWD_IGEMM: break;
     }
     const IgemmForm f = igemm_form(p, 0);
     if (igemm_refusal(f)) return igemm_refusal(f);
+    if (fp.route == FWD_CIN4) return y_bf16 ? "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps, bf16 y)"
+                                            : "conv_igemm_kernel<.., 5> (3 input channels as 4-channel taps)";
     if (f == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 0, 4>" : "conv_igemm_kernel<128, true, 0, 4>";
     if (f == IG_CT1) return "conv_igemm_kernel<.., 0, 1>";
     if (f == IG_CT2) return "conv_igemm_kernel<.., 0, 2>";
@@ -1977,10 +1968,8 @@ const char* munit_igemm_kernel_name(const munit_conv_desc* d, int pass) {
   if (x_bf16 && d->Cin % 4 != 0) return "refused: bf16 dx needs Cin % 4 == 0";
   if (pl.wino) return refl ? "conv_wino_kernel<2, 0>" : "conv_wino_kernel<1, 0>";
   if (pl.wino_s2) return refl ? "conv_wino_kernel<0, 2>" : "conv_wino_kernel<1, 2>";
-  if (pl.small) {
-    if (x_bf16) return "refused: the 3-channel data gradient is fp32";
-    return y_bf16 ? "conv_head_pk_kernel<bf16_t> (padded-domain correlation)" : "conv_head_pk_kernel (padded-domain correlation)";
-  }
+  // (the correlation reads dy: Cout input channels of d->out_dtype)
+  if (pl.small) return x_bf16 ? "refused: the 3-channel data gradient is fp32" : head[1][munit_small_fwd_kernel(d->Cout)][y_bf16];
   if (pl.folded) {
     if (!dgrad_fold_dtypes_ok(d, pl)) return "refused: unsupported dtype combination";
     IgemmParams p = dgrad_fold_params(d, pl);
@@ -2037,13 +2026,15 @@ double munit_igemm_executed_flops(const munit_conv_desc* d, int pass) {
   if (munit_conv2d_out_hw(d, &Ho, &Wo)) return 0.0;
   const double cc = 2.0 * d->Cin * d->Cout;
   if (pass == MUNIT_PASS_FWD) {
-    if (subpixel_wino_ok(d)) return cc * d->B * ((double)(d->H / 2) * (d->W / 2) * 4 * 16 + (2.0 * Wo + 2.0 * (Ho - 2)) * 25);
-    if (subpixel_ok(d)) return cc * d->B * ((double)d->H * d->W * 4 * 9 + (4.0 * Wo + 4.0 * (Ho - 4)) * 25);
-    if (wino_fwd_ok(d)) return cc * d->B * (d->H / 2) * (d->W / 2) * 16;   // 16 products per 2x2 tile instead of 36
-    if (wino_s2_fwd_ok(d)) return 4 * cc * d->B * cdiv(Ho, 3) * cdiv(Wo, 3) * 16;   // per 3x3 tile and input phase
-    if (cin4_fwd_ok(d) && !munit_small_fwd_supported(d))   // zero 4th input channel, K padded to the 32-wide tile
-      return 2.0 * d->Cout * d->B * Ho * Wo * plan_cin4(1, 1, d->KH * d->KW).kpad;
-    return cc * d->B * Ho * Wo * d->KH * d->KW;
+    const FwdPlan fp = plan_fwd(d);
+    switch (fp.route) {
+      case FWD_SUBPIXEL_WINO: return cc * d->B * ((double)(d->H / 2) * (d->W / 2) * 4 * 16 + (2.0 * Wo + 2.0 * (Ho - 2)) * 25);
+      case FWD_SUBPIXEL: return cc * d->B * ((double)d->H * d->W * 4 * 9 + (4.0 * Wo + 4.0 * (Ho - 4)) * 25);
+      case FWD_WINO: return cc * d->B * (d->H / 2) * (d->W / 2) * 16;   // 16 products per 2x2 tile instead of 36
+      case FWD_WINO_S2: return 4 * cc * d->B * cdiv(Ho, 3) * cdiv(Wo, 3) * 16;   // per 3x3 tile and input phase
+      case FWD_CIN4: return 2.0 * d->Cout * d->B * Ho * Wo * fp.cin4.kpad;   // zero 4th input channel, K padded to the 32-wide tile
+      default: return cc * d->B * Ho * Wo * d->KH * d->KW;
+    }
   }
   DgradPlan pl;
   if (plan_dgrad(d, &pl)) return 0.0;

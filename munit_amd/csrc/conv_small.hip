@@ -600,14 +600,22 @@ __global__ __launch_bounds__(256) void conv_lanes_wgrad_pk_kernel(SmallParams p)
 bool munit_small_fwd_supported(const munit_conv_desc* d) {
   return d->Cout == 3 && d->KH == 7 && d->KW == 7 && d->stride == 1 && d->upsample == 0 && d->Cin % 16 == 0;
 }
-
-bool munit_small_wgrad_supported(const munit_conv_desc* d) {
-  return d->Cout == 3 && d->KH == 7 && d->KW == 7 && d->stride == 1 && d->upsample == 0 && d->Cin % 64 == 0;
+// one predicate per pass: the geometry and the pass's own A/B switch
+bool munit_small_fwd_ok(const munit_conv_desc* d) { return munit_small_fwd_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_FWD"); }
+bool munit_small_wgrad_ok(const munit_conv_desc* d) {
+  return munit_small_fwd_supported(d) && d->Cin % 64 == 0 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_WGRAD");
 }
+
+// Which kernel a supported descriptor takes.  The workspace, the launch and the kernel names all ask here.
+SmallFwdKernel munit_small_fwd_kernel(int Cin) {
+  if (!MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_HEAD_PK")) return SMALL_FWD_PK;
+  return Cin % 64 == 0 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_HEAD_MFMA") ? SMALL_FWD_MFMA : SMALL_FWD_PATCH;
+}
+bool munit_small_wgrad_pk() { return !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_PK"); }
 
 size_t munit_small_fwd_workspace(const munit_conv_desc* d) {
   // packed-FMA head kernel: the re-laid weights [Cin/8][7][2][7][4][4]
-  if (d->Cin % 8 != 0 || MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_HEAD_PK")) return 0;
+  if (munit_small_fwd_kernel(d->Cin) != SMALL_FWD_PK) return 0;
   return align_up((size_t)(d->Cin / HP_CP) * HP_K * 2 * HP_K * 12 * sizeof(float), 256);
 }
 
@@ -617,31 +625,27 @@ int munit_small_fwd(const munit_conv_desc* d, int Ho, int Wo, const void* x, con
   p.x = x; p.w = w; p.bias = bias; p.y = y;
   p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Ho = Ho; p.Wo = Wo;
   p.pad = d->pad; p.reflect = d->pad_mode == MUNIT_PAD_REFLECT; p.act = d->act; p.slope = d->slope;
-  if (munit_small_fwd_workspace(d) != 0 && ws != nullptr) {
+  const SmallFwdKernel k = munit_small_fwd_kernel(d->Cin);
+  const bool b16 = d->in_dtype == MUNIT_DTYPE_BF16;
+  p.tiles_x = cdiv(Wo, k == SMALL_FWD_PK ? HP_TW : k == SMALL_FWD_MFMA ? 16 : 64);
+  p.tiles_y = cdiv(Ho, k == SMALL_FWD_PK ? HP_TH : k == SMALL_FWD_MFMA ? 8 : 4);
+  const dim3 grid((unsigned)((long long)d->B * p.tiles_x * p.tiles_y));
+  if (k == SMALL_FWD_PK) {
+    MUNIT_CHECK_ARG(ws != nullptr, "conv_head_pk: null workspace");
     float* wp = reinterpret_cast<float*>(ws);
     const int total = (d->Cin / HP_CP) * HP_K * 2 * HP_K * 12;
     hipLaunchKernelGGL(head_pk_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, st, w, wp, d->Cin);
     MUNIT_CHECK_LAUNCH("head_pk_weights");
-    p.tiles_x = cdiv(Wo, HP_TW); p.tiles_y = cdiv(Ho, HP_TH);
-    const long long nb = (long long)d->B * p.tiles_x * p.tiles_y;
-    if (d->in_dtype == MUNIT_DTYPE_BF16) hipLaunchKernelGGL((conv_head_pk_kernel<bf16_t>), dim3((unsigned)nb), dim3(256), 0, st, p, wp);
-    else hipLaunchKernelGGL((conv_head_pk_kernel<float>), dim3((unsigned)nb), dim3(256), 0, st, p, wp);
-    MUNIT_CHECK_LAUNCH("conv_head_pk");
-    return MUNIT_OK;
+    if (b16) hipLaunchKernelGGL((conv_head_pk_kernel<bf16_t>), grid, dim3(256), 0, st, p, wp);
+    else hipLaunchKernelGGL((conv_head_pk_kernel<float>), grid, dim3(256), 0, st, p, wp);
+  } else if (k == SMALL_FWD_MFMA) {
+    if (b16) hipLaunchKernelGGL((conv_head_mfma_kernel<bf16_t>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv_head_mfma_kernel<float>), grid, dim3(256), 0, st, p);
+  } else {
+    if (b16) hipLaunchKernelGGL((conv_patch_fwd_kernel<3, 7, bf16_t>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((conv_patch_fwd_kernel<3, 7, float>), grid, dim3(256), 0, st, p);
   }
-  if (d->Cin % 64 == 0 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_HEAD_MFMA")) {
-    p.tiles_x = cdiv(Wo, 16); p.tiles_y = cdiv(Ho, 8);
-    const long long nb = (long long)d->B * p.tiles_x * p.tiles_y;
-    if (d->in_dtype == MUNIT_DTYPE_BF16) hipLaunchKernelGGL((conv_head_mfma_kernel<bf16_t>), dim3((unsigned)nb), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((conv_head_mfma_kernel<float>), dim3((unsigned)nb), dim3(256), 0, st, p);
-    MUNIT_CHECK_LAUNCH("conv_head_mfma");
-    return MUNIT_OK;
-  }
-  p.tiles_x = cdiv(Wo, 64); p.tiles_y = cdiv(Ho, 4);
-  const long long blocks = (long long)d->B * p.tiles_x * p.tiles_y;
-  if (d->in_dtype == MUNIT_DTYPE_BF16) hipLaunchKernelGGL((conv_patch_fwd_kernel<3, 7, bf16_t>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((conv_patch_fwd_kernel<3, 7, float>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-  MUNIT_CHECK_LAUNCH("conv_patch_fwd");
+  MUNIT_CHECK_LAUNCH(k == SMALL_FWD_PK ? "conv_head_pk" : k == SMALL_FWD_MFMA ? "conv_head_mfma" : "conv_patch_fwd");
   return MUNIT_OK;
 }
 
@@ -664,8 +668,7 @@ int munit_small_wgrad(const munit_conv_desc* d, int Ho, int Wo, const void* x, c
   const int G = d->Cin / 64;
   const long long bands = (long long)d->B * p.units_per_img;
   const long long units = bands * 7 * G;
-  const bool pk = !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_PK");
-  if (pk) {
+  if (munit_small_wgrad_pk()) {
     if (d->in_dtype == MUNIT_DTYPE_BF16) hipLaunchKernelGGL((conv_lanes_wgrad_pk_kernel<3, 7, bf16_t>), dim3((unsigned)cdiv(units, 4)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((conv_lanes_wgrad_pk_kernel<3, 7, float>), dim3((unsigned)cdiv(units, 4)), dim3(256), 0, st, p);
   } else {

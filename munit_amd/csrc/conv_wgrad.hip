@@ -1130,15 +1130,6 @@ int run_wgrad(WgradParams p, const WgradPlan& pl, bool aligned, float* dw, float
 bool cin3_padded_ok(const munit_conv_desc* d) {
   return d->Cin == 3 && d->Cout % 4 == 0 && d->upsample == 0 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_CIN3_PAD");
 }
-struct Cin3Plan {
-  WgradPlan pl;
-  size_t x4_bytes, dw4_bytes;
-};
-void plan_cin3(const munit_conv_desc* d, int Ho, int Wo, Cin3Plan* cp) {
-  plan_launch(d->B * Ho * Wo, d->KH * d->KW * 4, d->Cout, true, &cp->pl);
-  cp->x4_bytes = align_up((size_t)d->B * d->H * d->W * 4 * sizeof(float), 256);
-  cp->dw4_bytes = align_up((size_t)d->Cout * d->KH * d->KW * 4 * sizeof(float), 256);
-}
 
 // bf16-storage layers whose backward-weight takes the 256 x 256 tile: both tensors bf16, whole 256-channel tiles on both sides
 // (one filter tap per block), the direct-to-LDS conditions of run_wgrad, and enough pixels that 256 / tiles splits keep >= 16 steps
@@ -1190,15 +1181,61 @@ bool wino_wgrad_layer(const munit_conv_desc* d) {
   return d->compute == MUNIT_COMPUTE_F32 && d->in_dtype == MUNIT_DTYPE_F32 && d->out_dtype == MUNIT_DTYPE_F32 && d->KH == 3 &&
          d->KW == 3 && d->stride == 1 && d->pad == 1 && d->upsample == 0 && munit_wino_wgrad_ok(d->B, d->H, d->W, d->Cin, d->Cout);
 }
+long long s2_tiles(const munit_conv_desc* d) { return (long long)d->B * cdiv(d->H / 2, 3) * cdiv(d->W / 2, 3); }
 // 4x4 / stride 2 / pad 1 fp32 layers: F(3x3, 2x2) backward-weight, one launch phase per filter-tap parity
 bool wino_s2_wgrad_layer(const munit_conv_desc* d) {
   return d->compute == MUNIT_COMPUTE_F32 && d->in_dtype == MUNIT_DTYPE_F32 && d->out_dtype == MUNIT_DTYPE_F32 && d->KH == 4 &&
          d->KW == 4 && d->stride == 2 && d->pad == 1 && d->upsample == 0 && d->H >= 4 && d->W >= 4 &&
          munit_wino_wgrad_ok(d->B, d->H, d->W, d->Cin, d->Cout) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINOGRAD_S2") &&
-         (long long)d->B * cdiv(d->H / 2, 3) * cdiv(d->W / 2, 3) >= (getenv("MUNIT_WINO_S2_MIN_BLOCKS") ? 1 : 512);
+         s2_tiles(d) >= (getenv("MUNIT_WINO_S2_MIN_BLOCKS") ? 1 : 512);
 }
+
+// The route of a backward-weight pass and its sub-plan, decided HERE and nowhere else: workspace, launch, kernel name and
+// executed FLOPs all read the plan.  The tests below run in the order written, and at most one of them holds:
+//   * the filter tells WINO_S2 (4x4 / stride 2), WINO (3x3), SMALL (7x7) and SUBPIXEL (5x5, upsample == 1) apart;
+//   * CIN3 needs Cin == 3, the first three Cin % 64 == 0 and SUBPIXEL Cin % 4 == 0.
+enum WgradRoute { WGR_WINO_S2, WGR_WINO, WGR_SMALL, WGR_SUBPIXEL, WGR_CIN3, WGR_GENERIC };
+struct WgradRoutePlan {
+  int rc;              // of munit_conv2d_out_hw: nothing else is filled in when it is not MUNIT_OK
+  WgradRoute route;
+  int Ho, Wo;
+  bool aligned;        // Cin % 4 == 0, or CIN3's four channels
+  SubpixelPlan sp;     // SUBPIXEL
+  WgradPlan gen;       // GENERIC (with the bf16s_big_tile choice), CIN3
+  size_t x4_bytes, dw4_bytes;   // CIN3: workspace = [4-channel x][4-channel dw][slabs]
+  size_t ws_bytes;
+};
+WgradRoutePlan plan_wgrad(const munit_conv_desc* d) {
+  WgradRoutePlan pl{};
+  pl.rc = munit_conv2d_out_hw(d, &pl.Ho, &pl.Wo);
+  if (pl.rc) return pl;
+  pl.route = wino_s2_wgrad_layer(d) ? WGR_WINO_S2 : wino_wgrad_layer(d) ? WGR_WINO : munit_small_wgrad_ok(d) ? WGR_SMALL
+             : subpixel_wgrad_ok(d) ? WGR_SUBPIXEL : cin3_padded_ok(d) ? WGR_CIN3 : WGR_GENERIC;
+  pl.aligned = pl.route == WGR_CIN3 || d->Cin % 4 == 0;
+  switch (pl.route) {
+    case WGR_WINO_S2: pl.ws_bytes = munit_wino_wgrad_workspace(s2_tiles(d), d->Cin, d->Cout, 4); break;
+    case WGR_WINO: pl.ws_bytes = munit_wino_wgrad_workspace((long long)d->B * (d->H / 2) * (d->W / 2), d->Cin, d->Cout, 1); break;
+    case WGR_SMALL: pl.ws_bytes = munit_small_wgrad_workspace(d, pl.Ho); break;
+    case WGR_SUBPIXEL:
+      plan_subpixel(d, &pl.sp);
+      pl.ws_bytes = pl.sp.dwc_bytes + pl.sp.slab_bytes;
+      break;
+    case WGR_CIN3:
+      plan_launch(d->B * pl.Ho * pl.Wo, d->KH * d->KW * 4, d->Cout, true, &pl.gen);
+      pl.x4_bytes = align_up((size_t)d->B * d->H * d->W * 4 * sizeof(float), 256);
+      pl.dw4_bytes = align_up((size_t)d->Cout * d->KH * d->KW * 4 * sizeof(float), 256);
+      pl.ws_bytes = pl.x4_bytes + pl.dw4_bytes + pl.gen.slab_bytes + pl.gen.bias_bytes;
+      break;
+    case WGR_GENERIC:
+      plan_launch(d->B * pl.Ho * pl.Wo, d->KH * d->KW * d->Cin, d->Cout, pl.aligned, &pl.gen, bf16s_big_tile(d, pl.Ho, pl.Wo));
+      pl.ws_bytes = pl.gen.slab_bytes + pl.gen.bias_bytes;
+      break;
+  }
+  return pl;
+}
+
 // Launch parameters of the backward-weight entry point (pointers left null): the entry point launches them and
-// munit_conv2d_kernel_name asks wgrad_form about the very same structs.
+// munit_conv2d_kernel_name asks wgrad_form / munit_wino_wgrad_variant about the very same structs.
 WgradParams wgrad_params(const munit_conv_desc* d, int Ho, int Wo) {
   WgradParams p{};
   p.x_bf16 = d->in_dtype == MUNIT_DTYPE_BF16; p.dy_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
@@ -1211,6 +1248,29 @@ WgradParams wgrad_params(const munit_conv_desc* d, int Ho, int Wo) {
   p.Ktot = d->KH * d->KW * d->Cin; p.M = d->B * Ho * Wo;
   p.dy_sw = d->Cout; p.dy_sh = (long long)Wo * d->Cout; p.dy_sb = (long long)Ho * Wo * d->Cout; p.dy_off = 0;
   return p;
+}
+// the Winograd launch of route WGR_WINO_S2, WGR_WINO or WGR_SUBPIXEL (its four phase gradients)
+WinoWgradParams wino_wgrad_params(const munit_conv_desc* d, int Ho, int Wo, WgradRoute route, const void* x, const void* dy) {
+  WinoWgradParams q{};
+  q.x = reinterpret_cast<const float*>(x); q.dy = reinterpret_cast<const float*>(dy);
+  q.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 4); q.dy_bytes = (unsigned)((size_t)d->B * Ho * Wo * d->Cout * 4);
+  q.dy_sw = d->Cout; q.dy_sh = (long long)Wo * d->Cout; q.dy_sb = (long long)Ho * Wo * d->Cout;
+  q.B = d->B; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout;
+  q.reflect = d->pad_mode == MUNIT_PAD_REFLECT;
+  q.th = d->H / 2; q.tw = d->W / 2; q.phases = 4;
+  if (route == WGR_WINO_S2) {
+    q.th = cdiv(Ho, 3); q.tw = cdiv(Wo, 3);
+    q.s2 = 1; q.Ho = Ho; q.Wo = Wo;
+  } else if (route == WGR_WINO) {
+    q.xo = -1; q.phases = 1;
+  } else {
+    // every source pixel i: output (2i + a, 2j + b) of phase (a, b) against taps i - 1 .. i + 1 of the source with its edge
+    // REPLICATED -- exact for all outputs but the outermost ring (conv_igemm.hip, forward), whose dy the kernel reads as 0
+    // and whose contribution the 25-tap frame launch adds
+    q.dy_sw *= 2; q.dy_sh *= 2; q.dy_prow = (long long)Wo * d->Cout; q.dy_pcol = d->Cout;
+    q.reflect = 2; q.xo = -1; q.ring_mask = 1;
+  }
+  return q;
 }
 // sub-pixel form: the frame of sp.ring output pixels through the generic 25-tap gather ...
 WgradParams subpixel_frame_params(const WgradParams& p, const munit_conv_desc* d, const SubpixelPlan& sp, int Ho, int Wo) {
@@ -1238,7 +1298,6 @@ WgradParams cin3_params(const WgradParams& p, const munit_conv_desc* d) {
   q.ct = 0;   // 4 channels per tap: not a multiple of the bf16 K granularity, stays fp32
   return q;
 }
-long long s2_tiles(const munit_conv_desc* d) { return (long long)d->B * cdiv(d->H / 2, 3) * cdiv(d->W / 2, 3); }
 const char* wgrad_refusal(WgradForm f) {
   if (f == WG_REFUSED_BF16) return "refused: bf16 tensors need Cin % 4 == 0, Cout % 4 == 0, tensors below 2 GiB and B*H*W < 2^23";
   if (f == WG_REFUSED_BF16_X) return "refused: bf16 x with fp32 dy exists for the 3-channel image head only";
@@ -1247,96 +1306,74 @@ const char* wgrad_refusal(WgradForm f) {
 }  // namespace
 
 extern "C" size_t munit_conv2d_wgrad_workspace_bytes(const munit_conv_desc* d) {
-  int Ho, Wo;
-  if (munit_conv2d_out_hw(d, &Ho, &Wo)) return 0;
-  if (wino_s2_wgrad_layer(d)) return munit_wino_wgrad_workspace(s2_tiles(d), d->Cin, d->Cout, 4);
-  if (wino_wgrad_layer(d)) return munit_wino_wgrad_workspace((long long)d->B * (d->H / 2) * (d->W / 2), d->Cin, d->Cout, 1);
-  if (munit_small_wgrad_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_WGRAD")) return munit_small_wgrad_workspace(d, Ho);
-  if (subpixel_wgrad_ok(d)) {
-    SubpixelPlan sp;
-    plan_subpixel(d, &sp);
-    return sp.dwc_bytes + sp.slab_bytes;
-  }
-  if (cin3_padded_ok(d)) {
-    Cin3Plan cp;
-    plan_cin3(d, Ho, Wo, &cp);
-    return cp.x4_bytes + cp.dw4_bytes + cp.pl.slab_bytes + cp.pl.bias_bytes;
-  }
-  WgradPlan pl;
-  plan_launch(d->B * Ho * Wo, d->KH * d->KW * d->Cin, d->Cout, d->Cin % 4 == 0, &pl, bf16s_big_tile(d, Ho, Wo));
-  return pl.slab_bytes + pl.bias_bytes;
+  const WgradRoutePlan pl = plan_wgrad(d);
+  return pl.rc ? 0 : pl.ws_bytes;
 }
 
 extern "C" double munit_conv2d_executed_flops(const munit_conv_desc* d, int pass) {
   if (pass == MUNIT_PASS_FWD || pass == MUNIT_PASS_DGRAD) return munit_igemm_executed_flops(d, pass);
-  int Ho, Wo;
-  if (pass != MUNIT_PASS_WGRAD || munit_conv2d_out_hw(d, &Ho, &Wo)) return 0.0;
+  if (pass != MUNIT_PASS_WGRAD) return 0.0;
+  const WgradRoutePlan pl = plan_wgrad(d);
+  if (pl.rc) return 0.0;
+  const int Ho = pl.Ho, Wo = pl.Wo;
   const double cc = 2.0 * d->Cin * d->Cout;
-  if (wino_wgrad_layer(d)) return cc * d->B * (d->H / 2) * (d->W / 2) * 16;
-  if (wino_s2_wgrad_layer(d)) return 4 * cc * (double)s2_tiles(d) * 16;
-  if (munit_small_wgrad_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_WGRAD")) return cc * d->B * Ho * Wo * d->KH * d->KW;
-  if (subpixel_wgrad_ok(d)) {  // 4 phase gradients over the interior source pixels + the 25-tap frame
-    SubpixelPlan sp;
-    plan_subpixel(d, &sp);
-    if (sp.wino) return cc * d->B * ((double)d->H * d->W * 4 * 4 + (2.0 * Wo + 2.0 * (Ho - 2)) * 25);
-    return cc * d->B * ((double)(d->H - 2) * (d->W - 2) * 4 * 9 + (4.0 * Wo + 4.0 * (Ho - 4)) * 25);
+  switch (pl.route) {
+    case WGR_WINO: return cc * d->B * (d->H / 2) * (d->W / 2) * 16;
+    case WGR_WINO_S2: return 4 * cc * (double)s2_tiles(d) * 16;
+    case WGR_SUBPIXEL:   // 4 phase gradients over the interior source pixels + the 25-tap frame
+      if (pl.sp.wino) return cc * d->B * ((double)d->H * d->W * 4 * 4 + (2.0 * Wo + 2.0 * (Ho - 2)) * 25);
+      return cc * d->B * ((double)(d->H - 2) * (d->W - 2) * 4 * 9 + (4.0 * Wo + 4.0 * (Ho - 4)) * 25);
+    case WGR_CIN3: return 2.0 * 4 * d->Cout * d->B * Ho * Wo * d->KH * d->KW;   // zero 4th input channel
+    default: return cc * d->B * Ho * Wo * d->KH * d->KW;
   }
-  if (cin3_padded_ok(d)) return 2.0 * 4 * d->Cout * d->B * Ho * Wo * d->KH * d->KW;   // zero 4th input channel
-  return cc * d->B * Ho * Wo * d->KH * d->KW;
 }
 
+// Name (as a profiler shows it) of the kernel that carries a pass of this layer.  The route comes from the pass's plan
+// (plan_fwd / plan_dgrad in conv_igemm.hip, plan_wgrad here), the kernel inside a route from the function its launch asks
+// (wgrad_form, munit_wino_wgrad_variant, munit_small_wgrad_pk) -- but for the sub-pixel Winograd phases, whose FAST is left open.
 extern "C" const char* munit_conv2d_kernel_name(const munit_conv_desc* d, int pass) {
   if (pass == MUNIT_PASS_FWD || pass == MUNIT_PASS_DGRAD) return munit_igemm_kernel_name(d, pass);
-  int Ho, Wo;
-  if (pass != MUNIT_PASS_WGRAD || munit_conv2d_out_hw(d, &Ho, &Wo)) return "invalid";
-  // (the second template argument mirrors the FAST decision of munit_wino_wgrad_launch)
-  if (wino_s2_wgrad_layer(d)) {
-    const bool fast = s2_tiles(d) % 8 == 0 && d->pad_mode == MUNIT_PAD_REFLECT && d->H % 6 == 0 && d->W % 6 == 0 && Ho % 3 == 0 && Wo % 3 == 0;
-    const bool xclamp = !fast && s2_tiles(d) % 8 == 0 && d->pad_mode == MUNIT_PAD_REFLECT;   // mirrors munit_wino_wgrad_launch
-    return fast ? "conv_wino_wgrad_kernel<true, true, false> + wino_wgrad_reduce_kernel"
-                : xclamp ? "conv_wino_wgrad_kernel<true, false, true> + wino_wgrad_reduce_kernel"
-                         : "conv_wino_wgrad_kernel<true, false, false> + wino_wgrad_reduce_kernel";
-  }
-  if (wino_wgrad_layer(d)) {
-    const bool fast = ((long long)d->B * (d->H / 2) * (d->W / 2)) % 8 == 0 && d->pad_mode == MUNIT_PAD_REFLECT;
-    return fast ? "conv_wino_wgrad_kernel<false, true, false> + wino_wgrad_reduce_kernel" : "conv_wino_wgrad_kernel<false, false, false> + wino_wgrad_reduce_kernel";
-  }
+  if (pass != MUNIT_PASS_WGRAD) return "invalid";
+  const WgradRoutePlan pl = plan_wgrad(d);
+  if (pl.rc) return "invalid";
+  const int Ho = pl.Ho, Wo = pl.Wo;
   const bool x_bf16 = d->in_dtype == MUNIT_DTYPE_BF16, dy_bf16 = d->out_dtype == MUNIT_DTYPE_BF16;
-  if (munit_small_wgrad_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_WGRAD")) {   // mirrors munit_small_wgrad's choice
-    if (dy_bf16) return "refused: the 3-channel image head has an fp32 dy";
-    if (MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WGRAD_PK")) return x_bf16 ? "conv_lanes_wgrad_kernel<bf16_t>" : "conv_lanes_wgrad_kernel";
-    return x_bf16 ? "conv_lanes_wgrad_pk_kernel<bf16_t>" : "conv_lanes_wgrad_pk_kernel";
-  }
-  // from here on: the launches of munit_conv2d_wgrad on the same parameters and plans, named by wgrad_form
-  const bool aligned = d->Cin % 4 == 0;
   const WgradParams p = wgrad_params(d, Ho, Wo);
-  if (subpixel_wgrad_ok(d)) {
-    SubpixelPlan sp;
-    plan_subpixel(d, &sp);
-    if (sp.wino) return "conv_wino_wgrad_kernel<false, ., true> x4 sub-pixel phases + frame + reduce";
-    const WgradForm fr = wgrad_form(subpixel_frame_params(p, d, sp, Ho, Wo), sp.frame, aligned).form;
-    const WgradForm ph = wgrad_form(subpixel_phase_params(p, d, Wo, 0), sp.phase, aligned).form;
-    if (wgrad_refusal(fr)) return wgrad_refusal(fr);
-    if (wgrad_refusal(ph)) return wgrad_refusal(ph);
-    if (ph == WG_BF16S_128 && fr == WG_BF16S_128) return "conv_wgrad_bf16s_kernel<1> x4 sub-pixel phases + frame";
-    if (x_bf16 || dy_bf16) return "invalid";   // (no descriptor gets here: subpixel_wgrad_ok admits bf16 only where both launches take that kernel)
-    if (ph == WG_CT1) return "conv_wgrad_kernel<.., 1> x4 sub-pixel phases + fp32 frame";
-    if (ph == WG_CT2) return "conv_wgrad_kernel<.., 2> x4 sub-pixel phases + fp32 frame";
-    return "conv_wgrad_kernel x4 sub-pixel phases + frame";
+  switch (pl.route) {
+    case WGR_WINO_S2:
+    case WGR_WINO: {
+      const WinoWgradVariant v = munit_wino_wgrad_variant(wino_wgrad_params(d, Ho, Wo, pl.route, nullptr, nullptr));
+      if (!v.s2) return v.fast ? "conv_wino_wgrad_kernel<false, true, false> + wino_wgrad_reduce_kernel"
+                               : "conv_wino_wgrad_kernel<false, false, false> + wino_wgrad_reduce_kernel";
+      return v.fast ? "conv_wino_wgrad_kernel<true, true, false> + wino_wgrad_reduce_kernel"
+                    : v.ring ? "conv_wino_wgrad_kernel<true, false, true> + wino_wgrad_reduce_kernel"
+                             : "conv_wino_wgrad_kernel<true, false, false> + wino_wgrad_reduce_kernel";
+    }
+    case WGR_SMALL:
+      if (dy_bf16) return "refused: the 3-channel image head has an fp32 dy";
+      if (!munit_small_wgrad_pk()) return x_bf16 ? "conv_lanes_wgrad_kernel<bf16_t>" : "conv_lanes_wgrad_kernel";
+      return x_bf16 ? "conv_lanes_wgrad_pk_kernel<bf16_t>" : "conv_lanes_wgrad_pk_kernel";
+    case WGR_SUBPIXEL: {
+      if (pl.sp.wino) return "conv_wino_wgrad_kernel<false, ., true> x4 sub-pixel phases + frame + reduce";
+      const WgradForm fr = wgrad_form(subpixel_frame_params(p, d, pl.sp, Ho, Wo), pl.sp.frame, pl.aligned).form;
+      const WgradForm ph = wgrad_form(subpixel_phase_params(p, d, Wo, 0), pl.sp.phase, pl.aligned).form;
+      if (wgrad_refusal(fr)) return wgrad_refusal(fr);
+      if (wgrad_refusal(ph)) return wgrad_refusal(ph);
+      if (ph == WG_BF16S_128 && fr == WG_BF16S_128) return "conv_wgrad_bf16s_kernel<1> x4 sub-pixel phases + frame";
+      if (x_bf16 || dy_bf16) return "invalid";   // (no descriptor gets here: subpixel_wgrad_ok admits bf16 only where both launches take that kernel)
+      if (ph == WG_CT1) return "conv_wgrad_kernel<.., 1> x4 sub-pixel phases + fp32 frame";
+      if (ph == WG_CT2) return "conv_wgrad_kernel<.., 2> x4 sub-pixel phases + fp32 frame";
+      return "conv_wgrad_kernel x4 sub-pixel phases + frame";
+    }
+    case WGR_CIN3:
+      if (x_bf16) return "refused: 3-channel inputs are fp32";
+      break;
+    case WGR_GENERIC: break;
   }
-  if (cin3_padded_ok(d)) {
-    if (x_bf16) return "refused: 3-channel inputs are fp32";
-    Cin3Plan cp;
-    plan_cin3(d, Ho, Wo, &cp);
-    const WgradForm f = wgrad_form(cin3_params(p, d), cp.pl, true).form;
-    if (wgrad_refusal(f)) return wgrad_refusal(f);
-    return f == WG_REG_BF16_DY ? "conv_wgrad_kernel<.., 0, false, true> (3 input channels padded to 4, bf16 dy)"
-                               : "conv_wgrad_kernel (3 input channels padded to 4)";
-  }
-  WgradPlan pl;
-  plan_launch(p.M, p.Ktot, d->Cout, aligned, &pl, bf16s_big_tile(d, Ho, Wo));
-  const WgradForm f = wgrad_form(p, pl, aligned).form;
+  const WgradForm f = wgrad_form(pl.route == WGR_CIN3 ? cin3_params(p, d) : p, pl.gen, pl.aligned).form;
   if (wgrad_refusal(f)) return wgrad_refusal(f);
+  if (pl.route == WGR_CIN3) return f == WG_REG_BF16_DY ? "conv_wgrad_kernel<.., 0, false, true> (3 input channels padded to 4, bf16 dy)"
+                                                       : "conv_wgrad_kernel (3 input channels padded to 4)";
   switch (f) {
     case WG_BF16S_128: return "conv_wgrad_bf16s_kernel<1> + slab_reduce_kernel";
     case WG_BF16S_256: return "conv_wgrad_bf16s_kernel<2> + slab_reduce_kernel";
@@ -1351,105 +1388,65 @@ extern "C" const char* munit_conv2d_kernel_name(const munit_conv_desc* d, int pa
 extern "C" int munit_conv2d_wgrad(const munit_conv_desc* d, const void* x, const void* dy, float* dw,
                                   float* db, float beta, void* ws, size_t ws_bytes,
                                   munit_stream_t stream) {
-  int Ho, Wo;
-  int rc = munit_conv2d_out_hw(d, &Ho, &Wo);
-  if (rc) return rc;
+  const WgradRoutePlan pl = plan_wgrad(d);
+  if (pl.rc) return pl.rc;
+  const int Ho = pl.Ho, Wo = pl.Wo;
   MUNIT_CHECK_ARG(x && dy && dw && ws, "conv2d_wgrad: null pointer");
-  if (ws_bytes < munit_conv2d_wgrad_workspace_bytes(d)) {
-    munit_set_error("conv2d_wgrad: workspace %zu < %zu", ws_bytes, munit_conv2d_wgrad_workspace_bytes(d));
+  if (ws_bytes < pl.ws_bytes) {
+    munit_set_error("conv2d_wgrad: workspace %zu < %zu", ws_bytes, pl.ws_bytes);
     return MUNIT_ERR_WORKSPACE;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (wino_s2_wgrad_layer(d)) {
-    WinoWgradParams q{};
-    q.x = reinterpret_cast<const float*>(x); q.dy = reinterpret_cast<const float*>(dy);
-    q.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 4); q.dy_bytes = (unsigned)((size_t)d->B * Ho * Wo * d->Cout * 4);
-    q.dy_sw = d->Cout; q.dy_sh = (long long)Wo * d->Cout; q.dy_sb = (long long)Ho * Wo * d->Cout;
-    q.B = d->B; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout;
-    q.reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-    q.th = cdiv(Ho, 3); q.tw = cdiv(Wo, 3); q.phases = 4;
-    q.s2 = 1; q.Ho = Ho; q.Wo = Wo;
-    return munit_wino_wgrad_launch(q, dw, 0, db, beta, beta, ws, st);
-  }
-  if (wino_wgrad_layer(d)) {
-    WinoWgradParams q{};
-    q.x = reinterpret_cast<const float*>(x); q.dy = reinterpret_cast<const float*>(dy);
-    q.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 4); q.dy_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cout * 4);
-    q.dy_sw = d->Cout; q.dy_sh = (long long)d->W * d->Cout; q.dy_sb = (long long)d->H * d->W * d->Cout;
-    q.B = d->B; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout;
-    q.reflect = d->pad_mode == MUNIT_PAD_REFLECT; q.xo = -1;
-    q.th = d->H / 2; q.tw = d->W / 2; q.phases = 1;
-    return munit_wino_wgrad_launch(q, dw, 0, db, beta, beta, ws, st);
-  }
-  if (munit_small_wgrad_supported(d) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_WGRAD"))
-  {
-    MUNIT_CHECK_ARG(d->out_dtype == MUNIT_DTYPE_F32, "conv2d_wgrad: the 3-channel image head has an fp32 dy");
-    return munit_small_wgrad(d, Ho, Wo, x, reinterpret_cast<const float*>(dy), dw, db, beta, ws, st);
-  }
-  const bool aligned = d->Cin % 4 == 0;
   WgradParams p = wgrad_params(d, Ho, Wo);
   p.x = x; p.dy = dy;
-  if (subpixel_wgrad_ok(d)) {
-    // dw = (frame pixels, generic 25-tap gather) + scatter of the 4 phase gradients (interior pixels, 3x3
-    // VALID conv over the source against every other dy row/column): 36 instead of 100 MACs per source
-    // pixel and channel pair.
-    SubpixelPlan sp;
-    plan_subpixel(d, &sp);
-    float* dwc = reinterpret_cast<float*>(ws);
-    void* slabs = reinterpret_cast<char*>(ws) + sp.dwc_bytes;
-    const WgradParams f = subpixel_frame_params(p, d, sp, Ho, Wo);
-    rc = run_wgrad(f, sp.frame, aligned, dw, db, beta, beta, slabs, st);
-    if (rc) return rc;
-    if (sp.wino) {
-      WinoWgradParams q{};
-      q.x = reinterpret_cast<const float*>(x); q.dy = reinterpret_cast<const float*>(dy);
-      q.x_bytes = (unsigned)((size_t)d->B * d->H * d->W * d->Cin * 4); q.dy_bytes = (unsigned)((size_t)d->B * Ho * Wo * d->Cout * 4);
-      q.dy_sw = 2 * d->Cout; q.dy_sh = (long long)2 * Wo * d->Cout; q.dy_sb = (long long)Ho * Wo * d->Cout;
-      q.dy_off = 0; q.dy_prow = (long long)Wo * d->Cout; q.dy_pcol = d->Cout;
-      q.B = d->B; q.H = d->H; q.W = d->W; q.Cin = d->Cin; q.Cout = d->Cout;
-      // every source pixel i: output (2i + a, 2j + b) of phase (a, b) against taps i - 1 .. i + 1 of the source with its edge
-      // REPLICATED -- exact for all outputs but the outermost ring (conv_igemm.hip, forward), whose dy the kernel reads as 0
-      // and whose contribution the 25-tap frame launch above has added
-      q.reflect = 2; q.xo = -1; q.ring_mask = 1;
-      q.th = d->H / 2; q.tw = d->W / 2; q.phases = 4;
-      rc = munit_wino_wgrad_launch(q, dwc, (long long)d->Cout * 9 * d->Cin, db, 0.0f, 1.0f, slabs, st);
+  switch (pl.route) {
+    case WGR_WINO_S2:
+    case WGR_WINO: return munit_wino_wgrad_launch(wino_wgrad_params(d, Ho, Wo, pl.route, x, dy), dw, 0, db, beta, beta, ws, st);
+    case WGR_SMALL:
+      MUNIT_CHECK_ARG(d->out_dtype == MUNIT_DTYPE_F32, "conv2d_wgrad: the 3-channel image head has an fp32 dy");
+      return munit_small_wgrad(d, Ho, Wo, x, reinterpret_cast<const float*>(dy), dw, db, beta, ws, st);
+    case WGR_SUBPIXEL: {
+      // dw = (frame pixels, generic 25-tap gather) + scatter of the 4 phase gradients (interior pixels, 3x3
+      // VALID conv over the source against every other dy row/column): 36 instead of 100 MACs per source
+      // pixel and channel pair.
+      const SubpixelPlan& sp = pl.sp;
+      float* dwc = reinterpret_cast<float*>(ws);
+      void* slabs = reinterpret_cast<char*>(ws) + sp.dwc_bytes;
+      const WgradParams f = subpixel_frame_params(p, d, sp, Ho, Wo);
+      int rc = run_wgrad(f, sp.frame, pl.aligned, dw, db, beta, beta, slabs, st);
       if (rc) return rc;
-    }
-    for (int ph = 0; ph < 4 && !sp.wino; ++ph) {
-      const WgradParams q = subpixel_phase_params(p, d, Wo, ph);
-      rc = run_wgrad(q, sp.phase, aligned, dwc + (long long)ph * d->Cout * 9 * d->Cin, db, 0.0f, 1.0f, slabs, st);
+      if (sp.wino) rc = munit_wino_wgrad_launch(wino_wgrad_params(d, Ho, Wo, pl.route, x, dy), dwc, (long long)d->Cout * 9 * d->Cin, db, 0.0f, 1.0f, slabs, st);
+      for (int ph = 0; ph < 4 && !sp.wino && !rc; ++ph)
+        rc = run_wgrad(subpixel_phase_params(p, d, Wo, ph), sp.phase, pl.aligned, dwc + (long long)ph * d->Cout * 9 * d->Cin, db, 0.0f, 1.0f, slabs, st);
       if (rc) return rc;
+      const long long total = (long long)d->Cout * 25 * d->Cin;
+      const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
+      hipLaunchKernelGGL(upw_scatter_kernel, dim3(blocks), dim3(256), 0, st, dwc, dw, d->Cout, d->Cin);
+      MUNIT_CHECK_LAUNCH("upw_scatter");
+      return MUNIT_OK;
     }
-    const long long total = (long long)d->Cout * 25 * d->Cin;
-    const int blocks = (int)std::min<long long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(upw_scatter_kernel, dim3(blocks), dim3(256), 0, st, dwc, dw, d->Cout, d->Cin);
-    MUNIT_CHECK_LAUNCH("upw_scatter");
-    return MUNIT_OK;
+    case WGR_CIN3: {
+      float* x4 = reinterpret_cast<float*>(ws);
+      float* dw4 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + pl.x4_bytes);
+      void* slabs = reinterpret_cast<char*>(ws) + pl.x4_bytes + pl.dw4_bytes;
+      const long long npix = (long long)d->B * d->H * d->W;
+      hipLaunchKernelGGL(pad3to4_kernel, dim3((unsigned)std::min<long long>((npix + 255) / 256, 8192)), dim3(256), 0, st,
+                         reinterpret_cast<const float*>(x), reinterpret_cast<f32x4*>(x4), npix);
+      MUNIT_CHECK_ARG(d->in_dtype == MUNIT_DTYPE_F32, "conv2d_wgrad: 3-channel inputs are fp32");
+      MUNIT_CHECK_LAUNCH("pad3to4");
+      WgradParams c = cin3_params(p, d);
+      c.x = x4;
+      const int rc = run_wgrad(c, pl.gen, pl.aligned, dw4, db, 0.0f, beta, slabs, st);
+      if (rc) return rc;
+      const long long n3 = (long long)d->Cout * d->KH * d->KW * 3;
+      hipLaunchKernelGGL(compact4to3_kernel, dim3((unsigned)std::min<long long>((n3 + 255) / 256, 4096)), dim3(256), 0, st, dw4, dw,
+                         n3, beta);
+      MUNIT_CHECK_LAUNCH("compact4to3");
+      return MUNIT_OK;
+    }
+    case WGR_GENERIC: break;
   }
-  if (cin3_padded_ok(d)) {
-    Cin3Plan cp;
-    plan_cin3(d, Ho, Wo, &cp);
-    float* x4 = reinterpret_cast<float*>(ws);
-    float* dw4 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + cp.x4_bytes);
-    void* slabs = reinterpret_cast<char*>(ws) + cp.x4_bytes + cp.dw4_bytes;
-    const long long npix = (long long)d->B * d->H * d->W;
-    hipLaunchKernelGGL(pad3to4_kernel, dim3((unsigned)std::min<long long>((npix + 255) / 256, 8192)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(x), reinterpret_cast<f32x4*>(x4), npix);
-    MUNIT_CHECK_ARG(d->in_dtype == MUNIT_DTYPE_F32, "conv2d_wgrad: 3-channel inputs are fp32");
-    MUNIT_CHECK_LAUNCH("pad3to4");
-    WgradParams q = cin3_params(p, d);
-    q.x = x4;
-    rc = run_wgrad(q, cp.pl, true, dw4, db, 0.0f, beta, slabs, st);
-    if (rc) return rc;
-    const long long n3 = (long long)d->Cout * d->KH * d->KW * 3;
-    hipLaunchKernelGGL(compact4to3_kernel, dim3((unsigned)std::min<long long>((n3 + 255) / 256, 4096)), dim3(256), 0, st, dw4, dw,
-                       n3, beta);
-    MUNIT_CHECK_LAUNCH("compact4to3");
-    return MUNIT_OK;
-  }
-  WgradPlan pl;
-  plan_launch(p.M, p.Ktot, d->Cout, aligned, &pl, bf16s_big_tile(d, Ho, Wo));
-  return run_wgrad(p, pl, aligned, dw, db, beta, beta, ws, st);
+  return run_wgrad(p, pl.gen, pl.aligned, dw, db, beta, beta, ws, st);
 }
 
 #ifdef WGB_STAMP

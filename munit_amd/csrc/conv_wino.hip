@@ -911,6 +911,23 @@ size_t munit_wino_wgrad_workspace(long long tiles, int Cin, int Cout, int phases
   return align_up(k * 16 * Cin * Cout * sizeof(float), 256) + align_up(k * Cout * sizeof(float), 256);
 }
 
+// FAST: every tile of every chunk exists and every patch / dy position lies inside its tensor (after reflection).
+// XCLAMP (<true, false, true>): a reflect-padded 4x4 / stride 2 layer whose 3x3 tiles overhang the output (Ho % 3 != 0 -- every
+// power-of-two extent) with every tile of every chunk present.  The overhanging dy positions are read as 0 (guarded, 9 loads per
+// tile), so the input positions that meet ONLY them may hold any finite value: the x side -- 32 loads per wave and chunk -- clamps
+// them into the image and drops its per-load validity selects.  Exact in the sense of the transform (linear; the products with a
+// zero gradient cancel), and the op tests hold it to the same bound as the guarded form.
+WinoWgradVariant munit_wino_wgrad_variant(const WinoWgradParams& p) {
+  const bool whole = (p.B * p.th * p.tw) % 8 == 0 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINO_WGRAD_FAST");
+  if (p.s2) {
+    const bool fast = whole && p.reflect && p.H % 6 == 0 && p.W % 6 == 0 && p.Ho % 3 == 0 && p.Wo % 3 == 0;
+    return {true, fast, !fast && whole && p.reflect == 1 && p.H >= 2 && p.W >= 2};
+  }
+  const bool fast = whole && (p.xo == -1 ? (p.reflect && p.H >= 2 && p.W >= 2 && 2 * p.th <= p.H && 2 * p.tw <= p.W)
+                                         : (p.xo >= 0 && 2 * (p.th - 1) + p.xo + 3 < p.H && 2 * (p.tw - 1) + p.xo + 3 < p.W));
+  return {false, fast, p.ring_mask != 0};
+}
+
 int munit_wino_wgrad_launch(WinoWgradParams p, float* dw, long long dw_phase, float* db, float beta, float beta_b, void* ws,
                             hipStream_t st) {
   p.phases = std::max(1, p.phases);
@@ -923,28 +940,18 @@ int munit_wino_wgrad_launch(WinoWgradParams p, float* dw, long long dw_phase, fl
                                             align_up((size_t)p.ksplit * p.phases * 16 * p.Cin * p.Cout * sizeof(float), 256));
   p.db_part = db != nullptr ? db_part : nullptr;
   const dim3 grid((unsigned)(p.CB * p.NB * p.ksplit), (unsigned)p.phases);
-  // FAST: every tile of every chunk exists and every patch / dy position lies inside its tensor (after reflection)
-  bool fast = p.tiles % 8 == 0 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINO_WGRAD_FAST");
-  if (p.s2) fast = fast && p.reflect && p.H % 6 == 0 && p.W % 6 == 0 && p.Ho % 3 == 0 && p.Wo % 3 == 0;
-  else fast = fast && (p.xo == -1 ? (p.reflect && p.H >= 2 && p.W >= 2 && 2 * p.th <= p.H && 2 * p.tw <= p.W)
-                                  : (p.xo >= 0 && 2 * (p.th - 1) + p.xo + 3 < p.H && 2 * (p.tw - 1) + p.xo + 3 < p.W));
-  if (p.s2) {
-    // XCLAMP (<true, false, true>): a reflect-padded layer whose 3x3 tiles overhang the output (Ho % 3 != 0 -- every power-of-two
-    // extent) with every tile of every chunk present.  The overhanging dy positions are read as 0 (guarded, 9 loads per tile), so
-    // the input positions that meet ONLY them may hold any finite value: the x side -- 32 loads per wave and chunk -- clamps them
-    // into the image and drops its per-load validity selects.  Exact in the sense of the transform (linear; the products with a
-    // zero gradient cancel), and the op tests hold it to the same bound as the guarded form.
-    const bool xclamp = !fast && p.reflect == 1 && p.tiles % 8 == 0 && p.H >= 2 && p.W >= 2 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINO_WGRAD_FAST");
-    if (fast) hipLaunchKernelGGL((conv_wino_wgrad_kernel<true, true>), grid, dim3(512), 0, st, p);
-    else if (xclamp) hipLaunchKernelGGL((conv_wino_wgrad_kernel<true, false, true>), grid, dim3(512), 0, st, p);
+  const WinoWgradVariant v = munit_wino_wgrad_variant(p);
+  if (v.s2) {
+    if (v.fast) hipLaunchKernelGGL((conv_wino_wgrad_kernel<true, true>), grid, dim3(512), 0, st, p);
+    else if (v.ring) hipLaunchKernelGGL((conv_wino_wgrad_kernel<true, false, true>), grid, dim3(512), 0, st, p);
     else hipLaunchKernelGGL((conv_wino_wgrad_kernel<true, false>), grid, dim3(512), 0, st, p);
-  } else if (p.ring_mask) {
+  } else if (v.ring) {
     MUNIT_CHECK_ARG(p.reflect == 2 && p.xo == -1 && p.phases == 4, "conv_wino_wgrad: ring_mask goes with the replicated edge and 4 phases");
-    if (fast) hipLaunchKernelGGL((conv_wino_wgrad_kernel<false, true, true>), grid, dim3(512), 0, st, p);
+    if (v.fast) hipLaunchKernelGGL((conv_wino_wgrad_kernel<false, true, true>), grid, dim3(512), 0, st, p);
     else hipLaunchKernelGGL((conv_wino_wgrad_kernel<false, false, true>), grid, dim3(512), 0, st, p);
   } else {
     MUNIT_CHECK_ARG(p.reflect != 2, "conv_wino_wgrad: the replicated edge goes with ring_mask");
-    if (fast) hipLaunchKernelGGL((conv_wino_wgrad_kernel<false, true>), grid, dim3(512), 0, st, p);
+    if (v.fast) hipLaunchKernelGGL((conv_wino_wgrad_kernel<false, true>), grid, dim3(512), 0, st, p);
     else hipLaunchKernelGGL((conv_wino_wgrad_kernel<false, false>), grid, dim3(512), 0, st, p);
   }
   MUNIT_CHECK_LAUNCH("conv_wino_wgrad");

@@ -216,6 +216,10 @@ bool munit_wino_wgrad_ok(int B, int H, int W, int Cin, int Cout);
 // splits of the tile range, and the workspace (slabs + bias partials) for `phases` launch phases over `tiles` tiles
 int munit_wino_wgrad_splits(long long tiles, int Cin, int Cout, int phases);
 size_t munit_wino_wgrad_workspace(long long tiles, int Cin, int Cout, int phases);
+// the <S2, FAST, RING> instantiation of conv_wino_wgrad_kernel a launch takes (s2: ring = the XCLAMP loader); the launch acts on
+// it and munit_conv2d_kernel_name names it
+struct WinoWgradVariant { bool s2, fast, ring; };
+WinoWgradVariant munit_wino_wgrad_variant(const WinoWgradParams& p);
 // p: tensors, strides and geometry filled in (x, dy, *_bytes, dy_*, B..Cout, reflect, xo, th, tw, phases); writes
 // dw + ph * dw_phase = beta * (.) + gradient of phase ph ([Cout][3][3][Cin]) and db = beta_b * db + sum over phases
 int munit_wino_wgrad_launch(WinoWgradParams p, float* dw, long long dw_phase, float* db, float beta, float beta_b, void* ws,

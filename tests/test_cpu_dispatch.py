@@ -31,8 +31,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PASSES = ("fwd", "dgrad", "wgrad")
 BATCHES = (1, 2, 3, 4, 8, 16, 32)
 CROPS_256 = (64, 96, 128, 192, 256, 384, 512, (256, 512), (360, 480))
-# reachable only with a MUNIT_DEBUG_* switch set (MUNIT_DEBUG_NO_WGRAD_PK, both): the op tests never force a debug fallback
-DEBUG_ONLY = {"conv_lanes_wgrad_kernel", "conv_lanes_wgrad_kernel<bf16_t>"}
+# reachable only with a MUNIT_DEBUG_* switch set (MUNIT_DEBUG_NO_WGRAD_PK; MUNIT_DEBUG_NO_HEAD_PK, alone and with
+# MUNIT_DEBUG_NO_HEAD_MFMA, for the head kernels of the forward and of the 3-channel backward-data): the op tests never force a
+# debug fallback
+_HEAD_FALLBACKS = {k + x + s for k in ("conv_head_mfma_kernel", "conv_patch_fwd_kernel") for x in ("", "<bf16_t>")
+                   for s in ("", " (padded-domain correlation)")}
+DEBUG_ONLY = {"conv_lanes_wgrad_kernel", "conv_lanes_wgrad_kernel<bf16_t>"} | _HEAD_FALLBACKS
 # backward-data of a bf16 x against an fp32 dy outside the 3-channel image head: the entry point runs it, but no caller can
 # use it (the backward-weight of the same descriptor is refused: "bf16 x with fp32 dy exists for the 3-channel image head
 # only"), so munit_amd.ops never plans one and no op test body can drive it.  Named, not covered.
@@ -63,7 +67,7 @@ NON_F32_FORMS = {
     "conv_wgrad_kernel<.., 0, false, true> (3 input channels padded to 4, bf16 dy)",
     "conv_wgrad_kernel<.., 1> + slab_reduce_kernel", "conv_wgrad_kernel<.., 2> + slab_reduce_kernel",
     "conv_wgrad_kernel<.., 1> x4 sub-pixel phases + fp32 frame", "conv_wgrad_kernel<.., 2> x4 sub-pixel phases + fp32 frame",
-}
+} | {n for n in _HEAD_FALLBACKS if "<bf16_t>" in n}
 
 
 @pytest.fixture(scope="module")
@@ -288,8 +292,8 @@ def test_every_production_conv_form_is_covered_by_an_op_test(lib):
 
 def F32_FORMS(lib, lits):
     """The literals an fp32 descriptor with fp32 arithmetic can get: those the fp32 op cases and the fp32 production grid take,
-    and the fp32 debug fallback."""
-    names = {n for _, n in covered(lib)} | {"conv_lanes_wgrad_kernel"}
+    and the fp32 debug fallbacks."""
+    names = {n for _, n in covered(lib)} | (DEBUG_ONLY - NON_F32_FORMS)
     return {n for n in lits if n in names}
 
 
