@@ -4,6 +4,10 @@ update_learning_rate first, periodic save).  Control plane only -- no comet, FID
 
   python examples/train_loop.py --config configs.yaml --data-root /path/with/trainA,trainB,testA,testB [--iters N]
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_loop.py ...      (data parallel, RCCL)
+
+The synthetic-pair iteration of scripts/train.py:229-260 runs when main() is called from Python with `synth_pairs`, an
+iterator of (x_as, x_bs, mask_s, sem_a, sem_b) batches: this package has no synthetic data loader, so the caller supplies
+the tensors (sem_a / sem_b may be None, the reference's `synthetic_seg_gt: 0`).
 """
 import argparse
 import os
@@ -15,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main(argv=None):
+def main(argv=None, synth_pairs=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
     ap.add_argument("--data-root", default=None, help="folder with trainA/ trainB/ testA/ testB (overrides the YAML lists)")
@@ -68,6 +72,13 @@ def main(argv=None):
             trainer.dis_update(x_a, x_b, config)                        # scripts/train.py:182
             if (it + 1) % ratio == 0:
                 trainer.gen_update(x_a, x_b, config, m_a, m_b)          # scripts/train.py:185-187
+            freq = int(config.get("synthetic_frequency", 0))
+            if synth_pairs is not None and freq > 0 and it % freq == 0:  # scripts/train.py:229-260
+                x_as, x_bs, mask_s, sem_a, sem_b = next(synth_pairs)
+                if config.get("synthetic_seg_gt", 0) == 0:
+                    sem_a = sem_b = None
+                trainer.dis_update(x_as, x_bs, config)
+                trainer.gen_update(x_as, x_bs, config, mask_s, mask_s, None, True, sem_a, sem_b)
             it += 1
             if args.output and args.save_every and it % args.save_every == 0 and local_rank == 0:
                 trainer.save(args.output, it - 1)      # file names carry iterations + 1 (trainer.py:1337-1344)

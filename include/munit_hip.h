@@ -270,6 +270,15 @@ int munit_l1_mean_fwd_bf16(const void* a, const void* b, const float* mask, size
                            void* ws, size_t ws_bytes, munit_stream_t stream);
 int munit_l1_mean_bwd_bf16(const void* a, const void* b, const float* mask, size_t npix, int C,
                            const float* gout, void* da, void* db, munit_stream_t stream);
+/* Synthetic-pair reconstruction loss (trainer.py:452-464): x_a, x_b, x_ab, x_ba NHWC fp32, npix pixels of C channels
+ * (C in 1..4).  A pixel is aligned when sum_c |x_a - x_b| == 0 (formed on the fly; no mask tensor exists).
+ * out = sum over aligned pixels of sum_c (|x_ab - x_b| + |x_ba - x_a|) / (npix * C): the sum of the reference's two
+ * recon_criterion_mask(., ., 1 - mask_alignment) means.  ws: munit_loss_workspace_bytes.  bwd writes dx_ab and dx_ba (either
+ * may be NULL) = gout[0] / (npix * C) * aligned * sign(.), sign(0) = 0; x_a and x_b get no gradient. */
+int munit_pair_l1_fwd(const float* x_a, const float* x_b, const float* x_ab, const float* x_ba, size_t npix, int C,
+                      float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
+int munit_pair_l1_bwd(const float* x_a, const float* x_b, const float* x_ab, const float* x_ba, size_t npix, int C,
+                      const float* gout, float* dx_ab, float* dx_ba, munit_stream_t stream);
 int munit_mse_const_fwd(const float* x, float target, size_t n, float* out, void* ws, size_t ws_bytes,
                         munit_stream_t stream);
 int munit_mse_const_bwd(const float* x, float target, size_t n, const float* gout, float* dx,
@@ -366,6 +375,20 @@ int munit_seg_ce_fwd(const float* logits, const int* labels, const float* mask, 
                      float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
 int munit_seg_ce_bwd(const float* logits, const int* labels, const float* mask, int B, int h, int w, int S, float norm,
                      const float* gout, float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream);
+/* The head against a ground-truth map of the simulator's 10 classes (trainer.py:732-737, merge_classes of
+ * utils.py:1330-1353).  The 19 up-sampled logits are merged into 10: merged class 0 is the constant 0, 1 = {0, 1},
+ * 2 = {2, 3, 4}, 3 = {5, 6, 7}, 4 = {8}, 5 = {9}, 6 = {10}, 7 = {11, 12}, 8 = {13, 17, 18}, 9 = {14, 15, 16} (sums of the
+ * member logits).  gt [B][h*S][w*S] FLOAT32 as the loader delivers it, truncated toward zero like .type(torch.long);
+ * valid values 0..9.  mask NULL: the 10-class cross-entropy; otherwise the masked form with new_class = 10 (logits
+ * (1 - m) * merged, m appended as the 11th logit, target (1 - m) * gt + 10 m).  out, norm, ws and the refusals as
+ * munit_seg_ce_*.  bwd: the pixel gradient of a merged class goes to each of its members (class 0's is dropped), then
+ * through the same up-sample adjoint; deterministic.
+ * A label outside 0..9, NaN or infinite is never used as an index: that pixel's loss is NaN (so `out` is NaN and the
+ * step's loss_sem_seg shows it) and its gradient 0; both calls still return MUNIT_OK. */
+int munit_seg_ce_gt_fwd(const float* logits, const float* gt, const float* mask, int B, int h, int w, int S, float norm,
+                        float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
+int munit_seg_ce_gt_bwd(const float* logits, const float* gt, const float* mask, int B, int h, int w, int S, float norm,
+                        const float* gout, float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream);
 /* labels = argmax over the 19 up-sampled logits (first maximal class on ties: torch's max(1)[1]). */
 int munit_seg_labels(const float* logits, int B, int h, int w, int S, int* labels, munit_stream_t stream);
 

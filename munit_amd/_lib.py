@@ -96,6 +96,8 @@ SIGNATURES = {
     "munit_l1_mean_bwd": (c_int, [_P, _P, _P, c_size_t, c_int, _P, _P, _P, _P]),
     "munit_l1_mean_fwd_bf16": (c_int, [_P, _P, _P, c_size_t, c_int, _P, _P, c_size_t, _P]),
     "munit_l1_mean_bwd_bf16": (c_int, [_P, _P, _P, c_size_t, c_int, _P, _P, _P, _P]),
+    "munit_pair_l1_fwd": (c_int, [_P, _P, _P, _P, c_size_t, c_int, _P, _P, c_size_t, _P]),
+    "munit_pair_l1_bwd": (c_int, [_P, _P, _P, _P, c_size_t, c_int, _P, _P, _P, _P]),
     "munit_mse_const_fwd": (c_int, [_P, c_float, c_size_t, _P, _P, c_size_t, _P]),
     "munit_mse_const_bwd": (c_int, [_P, c_float, c_size_t, _P, _P, _P]),
     "munit_weighted_sum": (c_int, [POINTER(c_void_p), POINTER(c_float), c_int, _P, _P]),
@@ -118,6 +120,8 @@ SIGNATURES = {
     "munit_seg_ce_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "munit_seg_ce_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
     "munit_seg_ce_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
+    "munit_seg_ce_gt_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
+    "munit_seg_ce_gt_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
     "munit_seg_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
 }
 

@@ -170,6 +170,49 @@ __global__ void l1_bwd_kernel(const T* __restrict__ a, const T* __restrict__ b, 
   }
 }
 
+// Synthetic-pair reconstruction loss (trainer.py:452-464): a pixel of the pair is aligned when x_a and x_b agree in every
+// channel, and only there x_ab is held to x_b and x_ba to x_a.  The alignment is formed per pixel, in registers.
+template <int C>
+__device__ inline bool pair_aligned(const float* __restrict__ xa, const float* __restrict__ xb, long long base) {
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) s += fabsf(xa[base + c] - xb[base + c]);
+  return s == 0.f;
+}
+
+template <int C>
+__global__ __launch_bounds__(NT) void pair_l1_partial_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
+                                                             const float* __restrict__ xab, const float* __restrict__ xba,
+                                                             long long npix, float* __restrict__ partial) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (long long p = (long long)blockIdx.x * NT + threadIdx.x; p < npix; p += (long long)gridDim.x * NT) {
+    const long long base = p * C;
+    if (!pair_aligned<C>(xa, xb, base)) continue;
+#pragma unroll
+    for (int c = 0; c < C; ++c) s += fabsf(xab[base + c] - xb[base + c]) + fabsf(xba[base + c] - xa[base + c]);
+  }
+  s = block_sum256(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+template <int C>
+__global__ void pair_l1_bwd_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
+                                   const float* __restrict__ xab, const float* __restrict__ xba, long long npix,
+                                   const float* __restrict__ gout, float* __restrict__ dab, float* __restrict__ dba) {
+  const float g = gout[0] / (float)(npix * C);
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+    const long long base = p * C;
+    const bool al = pair_aligned<C>(xa, xb, base);
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float d1 = xab[base + c] - xb[base + c], d2 = xba[base + c] - xa[base + c];
+      if (dab != nullptr) dab[base + c] = al ? (d1 > 0.f ? g : (d1 < 0.f ? -g : 0.f)) : 0.f;
+      if (dba != nullptr) dba[base + c] = al ? (d2 > 0.f ? g : (d2 < 0.f ? -g : 0.f)) : 0.f;
+    }
+  }
+}
+
 __global__ void mse_bwd_kernel(const float* __restrict__ x, float target, long long n, const float* __restrict__ gout,
                                float* __restrict__ dx) {
   const float g = 2.f * gout[0] / (float)n;
@@ -346,6 +389,46 @@ extern "C" int munit_l1_mean_bwd_bf16(const void* a, const void* b, const float*
                                       const float* gout, void* da, void* db, munit_stream_t stream) {
   return l1_mean_bwd_t<bf16_t>(reinterpret_cast<const bf16_t*>(a), reinterpret_cast<const bf16_t*>(b), mask, npix, C, gout,
                                reinterpret_cast<bf16_t*>(da), reinterpret_cast<bf16_t*>(db), stream);
+}
+
+extern "C" int munit_pair_l1_fwd(const float* x_a, const float* x_b, const float* x_ab, const float* x_ba, size_t npix,
+                                 int C, float* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x_a && x_b && x_ab && x_ba && out && ws && npix > 0, "pair_l1_fwd: bad args");
+  MUNIT_CHECK_ARG(C >= 1 && C <= 4, "pair_l1_fwd: C must be 1..4, got %d", C);
+  MUNIT_CHECK_ARG(ws_bytes >= LOSS_PARTS * sizeof(float), "pair_l1_fwd: workspace too small");
+  const int parts = (int)std::min<long long>(LOSS_PARTS, ((long long)npix + NT - 1) / NT);
+  float* partial = reinterpret_cast<float*>(ws);
+  hipStream_t st = (hipStream_t)stream;
+#define MUNIT_PAIR_FWD(c)                                                                                          \
+  hipLaunchKernelGGL(pair_l1_partial_kernel<c>, dim3(parts), dim3(NT), 0, st, x_a, x_b, x_ab, x_ba, (long long)npix, \
+                     partial)
+  if (C == 1) MUNIT_PAIR_FWD(1);
+  else if (C == 2) MUNIT_PAIR_FWD(2);
+  else if (C == 3) MUNIT_PAIR_FWD(3);
+  else MUNIT_PAIR_FWD(4);
+#undef MUNIT_PAIR_FWD
+  MUNIT_CHECK_LAUNCH("pair_l1_partial");
+  hipLaunchKernelGGL(finish_mean_kernel, dim3(1), dim3(NT), 0, st, partial, parts, 1.0 / ((double)npix * C), out);
+  MUNIT_CHECK_LAUNCH("finish_mean");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_pair_l1_bwd(const float* x_a, const float* x_b, const float* x_ab, const float* x_ba, size_t npix,
+                                 int C, const float* gout, float* dx_ab, float* dx_ba, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x_a && x_b && x_ab && x_ba && gout && npix > 0, "pair_l1_bwd: bad args");
+  MUNIT_CHECK_ARG(C >= 1 && C <= 4, "pair_l1_bwd: C must be 1..4, got %d", C);
+  const int grid = grid_for((long long)npix);
+  hipStream_t st = (hipStream_t)stream;
+#define MUNIT_PAIR_BWD(c)                                                                                        \
+  hipLaunchKernelGGL(pair_l1_bwd_kernel<c>, dim3(grid), dim3(NT), 0, st, x_a, x_b, x_ab, x_ba, (long long)npix, gout, \
+                     dx_ab, dx_ba)
+  if (C == 1) MUNIT_PAIR_BWD(1);
+  else if (C == 2) MUNIT_PAIR_BWD(2);
+  else if (C == 3) MUNIT_PAIR_BWD(3);
+  else MUNIT_PAIR_BWD(4);
+#undef MUNIT_PAIR_BWD
+  MUNIT_CHECK_LAUNCH("pair_l1_bwd");
+  return MUNIT_OK;
 }
 
 extern "C" int munit_mse_const_fwd(const float* x, float target, size_t n, float* out, void* ws, size_t ws_bytes,

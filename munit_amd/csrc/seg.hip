@@ -228,6 +228,108 @@ __global__ void seg_ce_grad_kernel(const float* __restrict__ lg, const int* __re
     for (int k = 0; k < NCLS; ++k) g[p * NCLS + k] = sc * d[k];
   }
 }
+// ---- cross-entropy against a ground-truth map of the simulator's 10 classes (trainer.py:732-737, utils.py:1330-1353) ----
+constexpr int NMRG = 10;
+// cross-entropy of one pixel on the 19 logits merged into 10: merged class 0 is the constant 0, the others the sums of
+// their Cityscapes members.  Unmasked branch (mask == NULL): 10 classes.  Masked branch: logits (1-m)*merged with m
+// appended as the 11th logit, target (1-long(m))*gt + long(m)*10.  gt is the loader's float label, truncated like
+// .type(torch.long); no array is ever indexed by it.  A label outside 0..9 (or NaN / inf) makes the pixel's loss NaN and
+// its gradient 0.  g (optional) receives d loss / d z (19 values: a merged class's gradient goes to each member).
+__device__ inline float pixel_ce_gt(const float* z, float gt, const float* mask, long long pix, float* g) {
+  // fixed 11 entries so that every loop unrolls and zz stays in registers; the unmasked branch gives class 10 exp() = 0
+  float zz[NMRG + 1];
+  zz[0] = 0.f;
+  zz[1] = z[0] + z[1];
+  zz[2] = z[2] + z[3] + z[4];
+  zz[3] = z[5] + z[6] + z[7];
+  zz[4] = z[8];
+  zz[5] = z[9];
+  zz[6] = z[10];
+  zz[7] = z[11] + z[12];
+  zz[8] = z[13] + z[17] + z[18];
+  zz[9] = z[14] + z[15] + z[16];
+  const bool ok = gt > -1.f && gt < (float)NMRG;     // what truncates into 0..9; false for NaN
+  int t = ok ? (int)gt : -1;
+  float m = 0.f;
+  if (mask) {
+    m = mask[pix];
+    const int ml = (int)m;
+    t = ok ? (1 - ml) * t + ml * NMRG : -1;
+#pragma unroll
+    for (int k = 0; k < NMRG; ++k) zz[k] = (1.f - m) * zz[k];
+  }
+  zz[NMRG] = mask ? m : -INFINITY;
+  float mx = zz[0];
+#pragma unroll
+  for (int k = 1; k <= NMRG; ++k) mx = fmaxf(mx, zz[k]);
+  float se = 0.f;
+#pragma unroll
+  for (int k = 0; k <= NMRG; ++k) se += expf(zz[k] - mx);
+  const float lse = mx + logf(se);
+  float zt = 0.f;
+#pragma unroll
+  for (int k = 0; k <= NMRG; ++k) zt = k == t ? zz[k] : zt;
+  if (g) {
+    const float sc = ok ? (mask ? 1.f - m : 1.f) : 0.f;
+    float dm[NMRG];      // entry 0 (the constant class) is never read
+#pragma unroll
+    for (int k = 1; k < NMRG; ++k) dm[k] = sc * (expf(zz[k] - lse) - (k == t ? 1.f : 0.f));
+    g[0] = g[1] = dm[1];
+    g[2] = g[3] = g[4] = dm[2];
+    g[5] = g[6] = g[7] = dm[3];
+    g[8] = dm[4];
+    g[9] = dm[5];
+    g[10] = dm[6];
+    g[11] = g[12] = dm[7];
+    g[13] = g[17] = g[18] = dm[8];
+    g[14] = g[15] = g[16] = dm[9];
+  }
+  return ok ? lse - zt : NAN;
+}
+
+__global__ void seg_ce_gt_fwd_kernel(const float* __restrict__ lg, const float* __restrict__ gt, const float* __restrict__ mask,
+                                     int B, int h, int w, int S, float* __restrict__ part) {
+  __shared__ float red[NT / 64];
+  const int H = h * S, W = w * S;
+  const long long npix = (long long)B * H * W;
+  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+  float acc = 0.f;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(p % W);
+    const int y = (int)((p / W) % H);
+    const long long b = p / ((long long)W * H);
+    float z[NCLS];
+    up_logits(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), z);
+    acc += pixel_ce_gt(z, gt[p], mask, p, nullptr);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int i = 0; i < NT / 64; ++i) s += red[i];
+    part[blockIdx.x] = s;
+  }
+}
+__global__ void seg_ce_gt_grad_kernel(const float* __restrict__ lg, const float* __restrict__ gt, const float* __restrict__ mask,
+                                      int B, int h, int w, int S, const float* __restrict__ gout, float inv_n,
+                                      float* __restrict__ g) {
+  const int H = h * S, W = w * S;
+  const long long npix = (long long)B * H * W;
+  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+  const float sc = *gout * inv_n;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(p % W);
+    const int y = (int)((p / W) % H);
+    const long long b = p / ((long long)W * H);
+    float z[NCLS], d[NCLS];
+    up_logits(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), z);
+    pixel_ce_gt(z, gt[p], mask, p, d);
+#pragma unroll
+    for (int k = 0; k < NCLS; ++k) g[p * NCLS + k] = sc * d[k];
+  }
+}
+
 // adjoint of the bilinear up-sample as a gather: dl[b][i][j][k] = sum over the output pixels whose taps touch (i, j), in
 // fixed row / column order (the taps of row y reach i0(y) <= i <= i0(y) + 1, so y lies within S rows of [i*S, (i+1)*S))
 __global__ void seg_up_adjoint_kernel(const float* __restrict__ g, int B, int h, int w, int S, float* __restrict__ dl) {
@@ -288,7 +390,7 @@ __global__ void seg_labels_kernel(const float* __restrict__ lg, int B, int h, in
   }
 }
 
-int check_head(const float* lg, const int* labels, int B, int h, int w, int S) {
+int check_head(const float* lg, const void* labels, int B, int h, int w, int S) {
   MUNIT_CHECK_ARG(lg && labels && B > 0 && h > 0 && w > 0 && S > 0, "seg head: bad args");
   MUNIT_CHECK_ARG((long long)B * h * S * w * S * NCLS < (1ll << 40), "seg head: too large");
   return MUNIT_OK;
@@ -411,5 +513,49 @@ extern "C" int munit_seg_labels(const float* logits, int B, int h, int w, int S,
   const long long np = head_pix(B, h, w, S);
   hipLaunchKernelGGL(seg_labels_kernel, dim3(grid_for(np)), dim3(NT), 0, (hipStream_t)stream, logits, B, h, w, S, labels);
   MUNIT_CHECK_LAUNCH("seg_labels");
+  return MUNIT_OK;
+}
+
+// The same head against a ground-truth map (see pixel_ce_gt); reduction, up-sample adjoint and workspace are munit_seg_ce_*'s.
+extern "C" int munit_seg_ce_gt_fwd(const float* logits, const float* gt, const float* mask, int B, int h, int w, int S,
+                                   float norm, float* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  int rc = check_head(logits, gt, B, h, w, S);
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(out && ws && norm > 0.f, "seg_ce_gt_fwd: bad args");
+  const long long np = head_pix(B, h, w, S);
+  const unsigned nb = grid_for(np);
+  if (ws_bytes < (size_t)nb * sizeof(float)) {
+    munit_set_error("seg_ce_gt_fwd: workspace %zu < %zu", ws_bytes, (size_t)nb * sizeof(float));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* part = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(seg_ce_gt_fwd_kernel, dim3(nb), dim3(NT), 0, st, logits, gt, mask, B, h, w, S, part);
+  MUNIT_CHECK_LAUNCH("seg_ce_gt_fwd");
+  hipLaunchKernelGGL(seg_ce_final_kernel, dim3(1), dim3(64), 0, st, part, (int)nb, 1.0 / (double)norm, out);
+  MUNIT_CHECK_LAUNCH("seg_ce_final");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_seg_ce_gt_bwd(const float* logits, const float* gt, const float* mask, int B, int h, int w, int S,
+                                   float norm, const float* gout, float* dlogits, void* ws, size_t ws_bytes,
+                                   munit_stream_t stream) {
+  int rc = check_head(logits, gt, B, h, w, S);
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(gout && dlogits && ws && norm > 0.f, "seg_ce_gt_bwd: bad args");
+  const long long np = head_pix(B, h, w, S);
+  const size_t need = (size_t)np * NCLS * sizeof(float);
+  if (ws_bytes < need) {
+    munit_set_error("seg_ce_gt_bwd: workspace %zu < %zu", ws_bytes, need);
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* g = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(seg_ce_gt_grad_kernel, dim3(grid_for(np)), dim3(NT), 0, st, logits, gt, mask, B, h, w, S, gout,
+                     1.f / norm, g);
+  MUNIT_CHECK_LAUNCH("seg_ce_gt_grad");
+  hipLaunchKernelGGL(seg_up_adjoint_kernel, dim3(grid_for((long long)B * h * w * NCLS)), dim3(NT), 0, st, g, B, h, w, S,
+                     dlogits);
+  MUNIT_CHECK_LAUNCH("seg_up_adjoint");
   return MUNIT_OK;
 }

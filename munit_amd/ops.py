@@ -789,6 +789,53 @@ def l1_mean(a, b, mask=None):
     return _L1Mean.apply(a, b, mask)
 
 
+class _PairL1(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, x_a, x_b, x_ab, x_ba):
+        lib = _lib.load()
+        for t, nm in ((x_a, "x_a"), (x_b, "x_b"), (x_ab, "x_ab"), (x_ba, "x_ba")):
+            _require(t, "pair_l1 " + nm)
+            if t.dim() != 4 or t.shape != x_a.shape:
+                raise RuntimeError("munit_amd.pair_l1: four (B, C, H, W) images of one shape expected, got %s for %s"
+                                   % (tuple(t.shape), nm))
+        _same_device(x_a, x_b, x_ab, x_ba)
+        c = x_a.shape[1]
+        if not 1 <= c <= 4:
+            raise RuntimeError("munit_amd.pair_l1: 1..4 channels expected, got %d" % c)
+        if L1_SINK is not None:
+            L1_SINK.append(x_ab > x_b)
+            L1_SINK.append(x_ba > x_a)
+        x_a, x_b, x_ab, x_ba = nhwc(x_a), nhwc(x_b), nhwc(x_ab), nhwc(x_ba)
+        npix = x_a.numel() // c
+        out = torch.empty((), device=x_a.device, dtype=torch.float32)
+        ws = workspace(lib.munit_loss_workspace_bytes(x_a.numel()), x_a.device)
+        _lib.check(lib.munit_pair_l1_fwd(_p(x_a), _p(x_b), _p(x_ab), _p(x_ba), npix, c, _p(out), _p(ws), ws.numel(),
+                                         _stream()), "pair_l1_fwd")
+        ctx.c = c
+        ctx.save_for_backward(x_a, x_b, x_ab, x_ba)
+        return out
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, gout):
+        lib = _lib.load()
+        x_a, x_b, x_ab, x_ba = ctx.saved_tensors
+        gout = gout.contiguous()
+        dab = torch.empty_like(x_ab) if ctx.needs_input_grad[2] else None
+        dba = torch.empty_like(x_ba) if ctx.needs_input_grad[3] else None
+        _lib.check(lib.munit_pair_l1_bwd(_p(x_a), _p(x_b), _p(x_ab), _p(x_ba), x_a.numel() // ctx.c, ctx.c, _p(gout),
+                                         _p(dab), _p(dba), _stream()), "pair_l1_bwd")
+        return None, None, dab, dba
+
+
+def pair_l1(x_a, x_b, x_ab, x_ba):
+    """The synthetic-pair reconstruction loss (trainer.py:452-464): recon_criterion_mask(x_ab, x_b, 1 - align) +
+    recon_criterion_mask(x_ba, x_a, 1 - align) with align = (sum_c |x_a - x_b| == 0) formed inside the kernel.
+    Gradients go to x_ab and x_ba only."""
+    return _PairL1.apply(x_a, x_b, x_ab, x_ba)
+
+
 class _MseConst(Function):
     @staticmethod
     @_guarded
@@ -1131,6 +1178,63 @@ def seg_cross_entropy(logits, labels, mask=None, scale=8, norm=None):
     if norm is None:
         norm = labels.numel()
     return _SegCE.apply(logits, labels, mask, int(scale), float(norm))
+
+
+def _seg_gt_args(logits, gt, mask, scale):
+    logits = nhwc(logits)
+    _require(logits, "segmentation logits")
+    b, k, h, w = logits.shape
+    if k != 19:
+        raise RuntimeError("munit_amd.seg head: 19 classes expected, got %d" % k)
+    _require(gt, "segmentation ground truth")
+    if tuple(gt.shape) != (b, h * scale, w * scale) or not gt.is_contiguous():
+        raise RuntimeError("munit_amd.seg head: the ground truth must be contiguous float32 (%d, %d, %d), got %s"
+                           % (b, h * scale, w * scale, tuple(gt.shape)))
+    if mask is not None:
+        _require(mask, "segmentation mask")
+        if mask.numel() != b * h * scale * w * scale or not mask.is_contiguous():
+            raise RuntimeError("munit_amd.seg head: mask must hold one contiguous value per pixel")
+    _same_device(logits, gt, mask)
+    return logits, b, h, w
+
+
+class _SegCEGT(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, logits, gt, mask, scale, norm):
+        lib = _lib.load()
+        logits, b, h, w = _seg_gt_args(logits, gt, mask, scale)
+        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
+        out = torch.empty((), device=logits.device, dtype=torch.float32)
+        _lib.check(lib.munit_seg_ce_gt_fwd(_p(logits), _p(gt), _p(mask), b, h, w, scale, c_float(norm), _p(out), _p(ws),
+                                           ws.numel(), _stream()), "seg_ce_gt_fwd")
+        ctx.cfg = (scale, norm)
+        ctx.save_for_backward(logits, gt, mask)
+        return out
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, gout):
+        lib = _lib.load()
+        logits, gt, mask = ctx.saved_tensors
+        scale, norm = ctx.cfg
+        b, _, h, w = logits.shape
+        gout = gout.contiguous()
+        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
+        dl = torch.empty_like(logits)
+        _lib.check(lib.munit_seg_ce_gt_bwd(_p(logits), _p(gt), _p(mask), b, h, w, scale, c_float(norm), _p(gout), _p(dl),
+                                           _p(ws), ws.numel(), _stream()), "seg_ce_gt_bwd")
+        return dl, None, None, None, None
+
+
+def seg_cross_entropy_gt(logits, gt, mask=None, scale=8, norm=None):
+    """seg_cross_entropy against a ground-truth map of the simulator's 10 classes (trainer.py:732-737): the 19 up-sampled
+    logits are merged into 10 (merge_classes, utils.py:1330-1353) inside the kernel; gt is float32 (B, H, W) with values
+    0..9, truncated like .type(torch.long).  The masked form appends the mask as an 11th class.  A label outside 0..9
+    makes the loss NaN (include/munit_hip.h)."""
+    if norm is None:
+        norm = gt.numel()
+    return _SegCEGT.apply(logits, gt, mask, int(scale), float(norm))
 
 
 def seg_labels(logits, scale=8):

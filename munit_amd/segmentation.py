@@ -170,15 +170,20 @@ def load_segmentation_model(ckpt_path, classes):
     return model
 
 
-def seg_loss(model, x_orig, x_trans, mask=None):
+def seg_loss(model, x_orig, x_trans, mask=None, gt=None):
     """compute_semantic_seg_loss (trainer.py:706-771) summed over image pairs: x_orig / x_trans are lists of equal-sized
     batches (e.g. [x_a, x_b] and [x_ab, x_ba]); returns sum over pairs of the mean cross-entropy between the logits of
     x_trans[i] and the pseudo-labels of x_orig[i] (argmax of the network's output, no gradient).  mask: None (plain
-    19-class loss) or one tensor of 0/1 values covering all pairs' pixels in order (the masked 20-class loss)."""
+    19-class loss) or one tensor of 0/1 values covering all pairs' pixels in order (the masked 20-class loss).
+    gt: a ground-truth map of the simulator's 10 classes covering all pairs' pixels in order (float32, values 0..9).
+    With it the label pass over x_orig is skipped, as the reference skips it (trainer.py:733-741), and the logits are
+    merged into 10 classes (11 with a mask) inside the head kernel; the labels returned are None."""
+    b, _, h, w = x_trans[0].shape
+    if gt is not None:
+        return ops.seg_cross_entropy_gt(model(*x_trans), gt, mask, scale=8, norm=b * h * w), None
     with torch.no_grad():
         labels = ops.seg_labels(model(*x_orig))
     logits = model(*x_trans)
-    b, _, h, w = x_trans[0].shape
     return ops.seg_cross_entropy(logits, labels, mask, scale=8, norm=b * h * w), labels
 
 

@@ -16,8 +16,11 @@ What is different underneath (none of it changes results beyond fp32 rounding):
   * loss scalars stay on the device; nothing synchronises the host inside an update.
 
 The semantic-consistency loss (semantic_w > 0 with a semantic_ckpt_path) runs the user's frozen Resnet34_8s on
-the device (munit_amd/segmentation.py).  The other aux losses (VGG, domain classifiers, synthetic pairs) raise
-NotImplementedError when their weight is non-zero.
+the device (munit_amd/segmentation.py).  The synthetic-pair iteration of scripts/train.py:229-260 --
+gen_update(..., synth=True, semantic_gt_a, semantic_gt_b) -- adds the pair reconstruction loss (recon_synth_w) and takes
+the semantic loss against the simulator's label maps, the 19 logits merged into 10 classes inside the head kernel; the
+caller hands the pairs, masks and label maps in as tensors (the synthetic data loader is not part of this package).  The
+other aux losses (VGG, domain classifiers) raise NotImplementedError when their weight is non-zero.
 """
 import os
 import warnings
@@ -545,8 +548,48 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             raise ValueError("munit_amd: semantic_w > 0 needs a crop that is a multiple of 32 (the segmentation network's "
                              "1/8-resolution features split into 4 x 4 phases); got %d" % h)
 
-    def _semantic_loss(self, x_a, x_b, x_ab, x_ba, mask_a, mask_b):
-        """seg(x_a, x_ab, mask_a) + seg(x_b, x_ba, mask_b) (trainer.py:504-509) as one pass over each image pair."""
+    @staticmethod
+    def _check_semantic_gt(x_a, gt_a, gt_b):
+        """Argument checks of semantic_gt_a / semantic_gt_b (no device work): None when neither is given, else the two maps
+        viewed as (B, H, W)."""
+        if gt_a is None and gt_b is None:
+            return None
+        if gt_a is None or gt_b is None:
+            raise ValueError("munit_amd: semantic_gt_a and semantic_gt_b must be given together (got only semantic_gt_%s)"
+                             % ("b" if gt_a is None else "a"))
+        b, _, h, w = x_a.shape
+        out = []
+        for name, g in (("semantic_gt_a", gt_a), ("semantic_gt_b", gt_b)):
+            if not torch.is_tensor(g) or g.is_complex() or g.dtype == torch.bool:
+                raise ValueError("munit_amd: %s must be a tensor of a real dtype, got %s"
+                                 % (name, g.dtype if torch.is_tensor(g) else type(g)))
+            if tuple(g.shape) not in ((b, 1, h, w), (b, h, w)):
+                raise ValueError("munit_amd: %s must be (B, 1, H, W) or (B, H, W) at the image size %s, got %s"
+                                 % (name, (b, h, w), tuple(g.shape)))
+            g = g.detach().reshape(b, h, w)
+            if g.device.type == "cpu":      # the reference passes host tensors: those are range-checked here
+                bad = bool((~torch.isfinite(g)).any()) if g.is_floating_point() else False
+                if not bad:
+                    t = g.long()            # .type(torch.long), trainer.py:734
+                    bad = int(t.min()) < 0 or int(t.max()) > 9
+                if bad:
+                    raise ValueError("munit_amd: %s holds labels outside 0..9 (the simulator's 10 classes)" % name)
+            out.append(g)
+        return out
+
+    @staticmethod
+    def _gt_to_device(gts, dev):
+        """float32 (2B, H, W) on the device, each value already truncated as .type(torch.long) would."""
+        conv = []
+        for g in gts:
+            if g.is_floating_point() and g.dtype != torch.float32:
+                g = g.trunc()               # a float64 9.9999999999 must not round up to 10 in float32
+            conv.append(g.to(dev, torch.float32))
+        return torch.cat(conv).contiguous()
+
+    def _semantic_loss(self, x_a, x_b, x_ab, x_ba, mask_a, mask_b, gt=None):
+        """seg(x_a, x_ab, mask_a) + seg(x_b, x_ba, mask_b) (trainer.py:504-509) as one pass over each image pair.
+        gt: the ground-truth maps of both pairs (2B, H, W) float32, or None for pseudo-labels."""
         mask = None
         if not self.full_adaptation and (mask_a is not None or mask_b is not None):
             if mask_a is None or mask_b is None:
@@ -556,7 +599,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                     raise ValueError("munit_amd: semantic-loss masks must be (B, 1, H, W) at the image size %s, got %s"
                                      % (tuple(x_a.shape[2:]), tuple(m.shape)))
             mask = torch.cat([mask_a.float(), mask_b.float()]).contiguous()
-        loss, _ = seg_loss(self.segmentation_model, [x_a, x_b], [x_ab, x_ba], mask)
+        loss, _ = seg_loss(self.segmentation_model, [x_a, x_b], [x_ab, x_ba], mask, gt)
         return loss
 
     def _bind(self, device):
@@ -668,11 +711,13 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                    semantic_gt_a=None, semantic_gt_b=None):
         ops.set_compute(self.precision)
         hp = hyperparameters
-        if synth and hp.get("recon_synth_w", 0) > 0:
-            raise NotImplementedError("munit_amd: synthetic-pair reconstruction loss is outside the hot path")
-        if semantic_gt_a is not None or semantic_gt_b is not None:
-            raise NotImplementedError("munit_amd: the semantic loss against a synthetic ground truth (semantic_gt_a / "
-                                      "semantic_gt_b, merge_classes) is outside the hot path; only pseudo-labels are built")
+        pair_term = bool(synth) and hp.get("recon_synth_w", 0) > 0
+        gts = self._check_semantic_gt(x_a, semantic_gt_a, semantic_gt_b)
+        if not self.semantic_w:
+            gts = None                         # ignored, as in the reference (trainer.py:505-510)
+        if gts is not None and x_a.device.type != "cuda":
+            raise NotImplementedError("munit_amd: semantic_gt_a / semantic_gt_b run on the device only (there is no host "
+                                      "path for any loss); move the trainer and the images to a HIP device")
         self._check_aux(normalize_config(hp))
         self.gen_opt.zero_grad()
         # the reference draws these even when guided == 1 leaves them unused (trainer.py:366-367)
@@ -760,10 +805,15 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             br.join(self.loss_gen_recon_x_a, self.loss_gen_recon_x_b, self.loss_gen_recon_s_a, self.loss_gen_recon_s_b,
                     self.loss_gen_recon_c_a, self.loss_gen_recon_c_b, self.loss_gen_cycrecon_x_a,
                     self.loss_gen_cycrecon_x_b, self.loss_gen_adv_a, self.loss_gen_adv_b)
+            if pair_term or self.semantic_w:
+                br.join(x_ab, x_ba)            # both translations on the caller's stream
+            if pair_term:
+                # after the cycle terms: its two L1 sign patterns (x_ab > x_b, x_ba > x_a) are the last of the step
+                self.loss_gen_recon_synth = ops.pair_l1(x_a, x_b, x_ab, x_ba)
             self.loss_sem_seg = 0
             if self.semantic_w:
-                br.join(x_ab, x_ba)
-                self.loss_sem_seg = self._semantic_loss(x_a, x_b, x_ab, x_ba, mask_a, mask_b)
+                gt = None if gts is None else self._gt_to_device(gts, dev)
+                self.loss_sem_seg = self._semantic_loss(x_a, x_b, x_ab, x_ba, mask_a, mask_b, gt)
         finally:
             for p in d_params:
                 p.requires_grad_(True)
@@ -779,6 +829,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                       (hp["recon_x_cyc_w"], self.loss_gen_cycrecon_x_b)]
         if self.semantic_w:
             pairs.append((hp["semantic_w"], self.loss_sem_seg))
+        if pair_term:
+            pairs.append((hp["recon_synth_w"], self.loss_gen_recon_synth))
         self.loss_gen_total = ops.weighted_sum([t.detach() for _, t in pairs], [w for w, _ in pairs])
         live = [(w, t) for w, t in pairs if w != 0 and t.requires_grad]
         xch = None
@@ -806,7 +858,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self._log(comet_exp, ("loss_gen_adv_a", "loss_gen_adv_b", "loss_gen_recon_x_a", "loss_gen_recon_s_a",
                               "loss_gen_recon_c_a", "loss_gen_recon_x_b", "loss_gen_recon_s_b",
                               "loss_gen_recon_c_b", "loss_gen_cycrecon_x_a", "loss_gen_cycrecon_x_b",
-                              "loss_gen_total") + (("loss_sem_seg",) if self.semantic_w else ()))
+                              "loss_gen_total") + (("loss_sem_seg",) if self.semantic_w else ())
+                  + (("loss_gen_recon_synth",) if synth else ()))
 
     # ---- dis_update (trainer.py:1133-1190) ---------------------------------------------
     def dis_update(self, x_a, x_b, hyperparameters, comet_exp=None):
