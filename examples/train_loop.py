@@ -72,6 +72,9 @@ def main(argv=None, synth_pairs=None):
             trainer.dis_update(x_a, x_b, config)                        # scripts/train.py:182
             if (it + 1) % ratio == 0:
                 trainer.gen_update(x_a, x_b, config, m_a, m_b)          # scripts/train.py:185-187
+            cls_due = trainer.use_classifier_sr and (it + 1) % config["adaptation"]["classif_frequency"] == 0
+            if cls_due:                                                 # scripts/train.py:193-207: real codes, target 1
+                trainer.domain_classifier_sr_update(x_a, x_b, False, config["adaptation"]["dfeat_lambda"], it + 1)
             freq = int(config.get("synthetic_frequency", 0))
             if synth_pairs is not None and freq > 0 and it % freq == 0:  # scripts/train.py:229-260
                 x_as, x_bs, mask_s, sem_a, sem_b = next(synth_pairs)
@@ -79,6 +82,8 @@ def main(argv=None, synth_pairs=None):
                     sem_a = sem_b = None
                 trainer.dis_update(x_as, x_bs, config)
                 trainer.gen_update(x_as, x_bs, config, mask_s, mask_s, None, True, sem_a, sem_b)
+                if cls_due:                                             # scripts/train.py:261-274: synthetic codes, target 0
+                    trainer.domain_classifier_sr_update(x_as, x_bs, True, config["adaptation"]["dfeat_lambda"], it + 1)
             it += 1
             if args.output and args.save_every and it % args.save_every == 0 and local_rank == 0:
                 trainer.save(args.output, it - 1)      # file names carry iterations + 1 (trainer.py:1337-1344)

@@ -392,6 +392,38 @@ int munit_seg_ce_gt_bwd(const float* logits, const float* gt, const float* mask,
 /* labels = argmax over the 19 up-sampled logits (first maximal class on ties: torch's max(1)[1]). */
 int munit_seg_labels(const float* logits, int B, int h, int w, int S, int* labels, munit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Feature-level domain adaptation (adaptation.adv_lambda / dfeat_lambda): the kernels of domainClassifier
+ * (scripts/utils.py:1277-1327, 1370-1392) that are not convolutions.  fp32, NHWC, C % 4 == 0.  Deterministic: reductions
+ * run in a fixed order (per-block partials in ws, one finishing pass), no atomics.
+ * ------------------------------------------------------------------------------------ */
+/* nn.BatchNorm2d over x [R = B*H*W][C] (C <= 1024, C / 4 divides 256).  Training mode (eval 0; R >= 2):
+ * y = act((x - mean) * rstd * gamma + beta) with the batch mean and the BIASED variance (two passes: the squares are taken
+ * about the mean), rstd = 1 / sqrt(var + eps); mean [2][C] (the mean as a sum of two floats, high parts then low parts) and
+ * rstd [C] are written for the backward; running_mean / running_var
+ * move in place by `momentum`, running_var with the UNBIASED variance.  relu: 0 / 1.  eval 1: normalises with
+ * running_mean / running_var and writes y alone (mean, rstd, ws may be NULL).  ws: munit_batchnorm_workspace_bytes(C). */
+size_t munit_batchnorm_workspace_bytes(int C);
+int munit_batchnorm_fwd(const float* x, float* y, float* mean, float* rstd, float* running_mean, float* running_var,
+                        long long R, int C, const float* gamma, const float* beta, int relu, int eval, float eps,
+                        float momentum, void* ws, size_t ws_bytes, munit_stream_t stream);
+/* Backward of the training-mode forward.  y is read behind a ReLU only (relu 1; NULL otherwise).  dx is always written;
+ * dgamma / dbeta = acc * old + new (acc 0 or 1) when not NULL, untouched when NULL. */
+int munit_batchnorm_bwd(const float* x, const float* dy, const float* y, const float* gamma, const float* mean,
+                        const float* rstd, float* dx, float* dgamma, float* dbeta, float acc, long long R, int C,
+                        int relu, void* ws, size_t ws_bytes, munit_stream_t stream);
+/* nn.MaxPool2d(2): y [B][H/2][W/2][C] (floor: an odd trailing row / column is dropped; H, W >= 2).  idx (one byte per
+ * output) receives the window position kh*2 + kw of the winner: the FIRST maximal element in window order, torch's tie
+ * rule (a NaN counts as maximal).  bwd writes every dx element exactly once: dy at the winners, 0 at the losers and in the
+ * dropped row / column. */
+int munit_maxpool2_fwd(const float* x, float* y, unsigned char* idx, int B, int H, int W, int C, munit_stream_t stream);
+int munit_maxpool2_bwd(const float* dy, const unsigned char* idx, float* dx, int B, int H, int W, int C,
+                       munit_stream_t stream);
+/* nn.AvgPool2d((16, 16)) + squeeze on a map with 16 <= H, W <= 31: y [B][C] = mean of the top-left 16x16 window
+ * (C / 4 divides 256).  bwd: dx = dy / 256 inside the window, 0 outside. */
+int munit_avgpool16_fwd(const float* x, float* y, int B, int H, int W, int C, munit_stream_t stream);
+int munit_avgpool16_bwd(const float* dy, float* dx, int B, int H, int W, int C, munit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -599,3 +599,111 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         outs0 = self.forward(input_fake)
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
         return ops.scalar_sum([ops.mse_const(out0, 1.0) for out0 in outs0])
+
+
+# --------------------------------------------------------------------------------------
+# feature classifier (adaptation.adv_lambda / dfeat_lambda)
+# --------------------------------------------------------------------------------------
+class BatchNorm2d(nn.Module):
+    """Stands in for nn.BatchNorm2d (affine, track_running_stats): parameters `weight`, `bias`, buffers `running_mean`,
+    `running_var`, `num_batches_tracked` as in torch.  In training mode every forward normalises with the batch statistics
+    and moves the running ones (momentum 0.1, unbiased variance)."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1):
+        super().__init__()
+        self.num_features, self.eps, self.momentum = num_features, eps, momentum
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+        self.register_buffer("running_mean", torch.zeros(num_features))
+        self.register_buffer("running_var", torch.ones(num_features))
+        self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        # the count lives on the host (no launch per forward); the buffer receives it whenever state_dict() is read, and a
+        # loaded state dict hands its value back
+        self._tracked = 0
+        self.register_state_dict_pre_hook(self._publish_tracked)
+
+    @staticmethod
+    def _publish_tracked(module, prefix, keep_vars):
+        module.num_batches_tracked.fill_(module._tracked)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        if prefix + "num_batches_tracked" in state_dict:
+            self._tracked = int(state_dict[prefix + "num_batches_tracked"])
+
+    def forward(self, x, relu=False, need_weight_grads=True):
+        if self.training:
+            self._tracked += 1                 # nn.BatchNorm2d's num_batches_tracked
+        return ops.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, relu, self.eps, self.momentum,
+                              self.training, need_weight_grads)
+
+    def extra_repr(self):
+        return "%d, eps=%g, momentum=%g" % (self.num_features, self.eps, self.momentum)
+
+
+class BasicBlock(nn.Module):
+    """scripts/utils.py:1277-1327 as domainClassifier builds it: stride 1 (`stride=True`), a conv1x1 + BatchNorm2d shortcut
+    whenever the channel count changes."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1):
+        super().__init__()
+        if int(stride) != 1:
+            raise NotImplementedError("munit_amd.BasicBlock: stride %r (the feature classifier uses stride 1)" % (stride,))
+        self.conv1 = Conv2d(inplanes, planes, 3, 1, bias=False)
+        self.bn1 = BatchNorm2d(planes)
+        self.conv2 = Conv2d(planes, planes, 3, 1, bias=False)
+        self.bn2 = BatchNorm2d(planes)
+        self.stride = stride
+        self.downsample = None
+        if inplanes != planes:
+            self.downsample = nn.Sequential(Conv2d(inplanes, planes, 1, 1, bias=False), BatchNorm2d(planes))
+
+    def forward(self, x, need_weight_grads=True):
+        out = self.bn1(self.conv1(x, 1), True, need_weight_grads)
+        out = self.bn2(self.conv2(out, 1), False, need_weight_grads)
+        identity = x
+        if self.downsample is not None:
+            identity = self.downsample[1](self.downsample[0](x), False, need_weight_grads)
+        return ops.add_relu(out, identity, dann=True)
+
+
+class domainClassifier(_ApplyRefreshesImages, nn.Module):
+    """scripts/utils.py:1370-1392: MaxPool2d(2) -> BasicBlock(256, 128) -> MaxPool2d(2) -> BasicBlock(128, 64) ->
+    AvgPool2d((16, 16)) -> squeeze -> Linear(64, 1) on a content code (B, 256, h, w)."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.BasicBlock1 = BasicBlock(256, 128, True)
+        self.BasicBlock2 = BasicBlock(128, 64, True)
+        self.fc = Linear(64, 1)
+        self.output_dim = dim
+
+    @staticmethod
+    def check_code_hw(h, w):
+        """The 16x16 average followed by Linear(64, 1) needs exactly one window: the twice-pooled map must be 16..31 per axis."""
+        ph, pw = h // 2 // 2, w // 2 // 2
+        if not (16 <= ph <= 31 and 16 <= pw <= 31):
+            raise ValueError("munit_amd.domainClassifier: a %dx%d content code pools to %dx%d; AvgPool2d((16, 16)) + "
+                             "Linear(64, 1) need 16..31 on both axes (content codes of 64..127)" % (h, w, ph, pw))
+
+    def forward(self, x, need_weight_grads=True):
+        """need_weight_grads False: the backward pass forms the gradient of x only (the generator's use: the classifier's
+        weight gradients would be zeroed before any use)."""
+        x = ops.nhwc(x)
+        if x.dim() != 4 or x.shape[1] != 256:
+            raise ValueError("munit_amd.domainClassifier: a (B, 256, h, w) content code expected, got %s" % (tuple(x.shape),))
+        self.check_code_hw(x.shape[2], x.shape[3])
+        frozen = [] if need_weight_grads else [p for p in self.parameters() if p.requires_grad]
+        for p in frozen:
+            p.requires_grad_(False)
+        try:
+            h = ops.maxpool2(x)
+            h = self.BasicBlock1(h, need_weight_grads)
+            h = ops.maxpool2(h)
+            h = self.BasicBlock2(h, need_weight_grads)
+            out = self.fc(ops.avgpool16(h))
+        finally:
+            for p in frozen:
+                p.requires_grad_(True)
+        return out.reshape(1) if out.shape[0] == 1 else out      # the reference's .squeeze() drops the batch axis at B = 1

@@ -31,6 +31,9 @@ L1_SINK = None
 # likewise for the frozen segmentation network of the semantic loss (munit_amd/segmentation.py): its ReLU sign patterns,
 # max-pool winners and pseudo-labels, in call order, kept apart so that the generator's kink order above is untouched
 SEG_SINK = None
+# likewise for the feature classifiers of adv_lambda / dfeat_lambda (networks.domainClassifier): the max-pool winners, the
+# ReLU sign patterns behind batch_norm and the block tails, in call order
+DANN_SINK = None
 # bench.py sets this to {"alg": 0.0, "exec": 0.0} to add up, over one step, the algorithmic FLOPs of every convolution /
 # linear pass (SURVEY.md section 8d's definition) and the FLOPs the kernels actually issue (sub-pixel and box-sum
 # forms execute fewer).
@@ -1059,10 +1062,11 @@ def maxpool3s2(x):
 
 class _AddRelu(Function):
     """BasicBlock tail relu(a + r).  link: park the gradient of r there (the identity skip: the block's first convolution
-    adds it in its backward-data epilogue) and return none for r."""
+    adds it in its backward-data epilogue) and return none for r.  dann: a block of the feature classifier (its signs go to
+    DANN_SINK, not SEG_SINK)."""
     @staticmethod
     @_guarded
-    def forward(ctx, a, r, link):
+    def forward(ctx, a, r, link, dann=False):
         lib = _lib.load()
         a, r = nhwc(a), nhwc(r)
         _require(a, "block output")
@@ -1071,8 +1075,9 @@ class _AddRelu(Function):
             raise RuntimeError("munit_amd.add_relu: shapes differ (%s vs %s)" % (tuple(a.shape), tuple(r.shape)))
         y = torch.empty_like(a)
         _lib.check(lib.munit_add_relu_fwd(_p(a), _p(r), _p(y), a.numel(), _stream()), "add_relu_fwd")
-        if SEG_SINK is not None:
-            SEG_SINK.append(y > 0)
+        sink = DANN_SINK if dann else SEG_SINK
+        if sink is not None:
+            sink.append(y > 0)
         ctx.link = link
         ctx.save_for_backward(y)
         return y
@@ -1084,12 +1089,12 @@ class _AddRelu(Function):
         d = act_bwd_raw("relu", 0.0, y, nhwc(dy))
         if ctx.link is not None:
             ctx.link.park(d)
-            return d, None, None
-        return d, d, None
+            return d, None, None, None
+        return d, d, None, None
 
 
-def add_relu(a, r, link=None):
-    return _AddRelu.apply(a, r, link)
+def add_relu(a, r, link=None, dann=False):
+    return _AddRelu.apply(a, r, link, dann)
 
 
 def space_to_batch_raw(x, f, inverse=False):
@@ -1251,3 +1256,151 @@ def seg_labels(logits, scale=8):
     if SEG_SINK is not None:
         SEG_SINK.append(labels)
     return labels
+
+
+# ------------------------------------------------------------------------------------------
+# feature classifier of adaptation.adv_lambda / dfeat_lambda (networks.domainClassifier; include/munit_hip.h, dann.hip)
+# ------------------------------------------------------------------------------------------
+class _BatchNorm(Function):
+    """Training-mode nn.BatchNorm2d (+ReLU).  running_mean / running_var are updated in place by the forward kernel.
+    need_weight_grads False: backward forms dx only (gen_update: the classifier's weight gradients would be zeroed unused)."""
+    @staticmethod
+    @_guarded
+    def forward(ctx, x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads):
+        _require(x, "batch-norm input")
+        lib = _lib.load()
+        x = nhwc(x)
+        b, c, h, w = x.shape
+        for t, nm in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+            _require(t, "batch-norm " + nm)
+            if tuple(t.shape) != (c,) or not t.is_contiguous():
+                raise RuntimeError("munit_amd.batch_norm: %s must be a contiguous (%d,) tensor" % (nm, c))
+        _same_device(x, gamma, beta, running_mean, running_var)
+        y = torch.empty_like(x)
+        mean = torch.empty(2 * c, device=x.device, dtype=torch.float32)      # high parts, then low parts
+        rstd = torch.empty(c, device=x.device, dtype=torch.float32)
+        ws = workspace(lib.munit_batchnorm_workspace_bytes(c), x.device)
+        relu = int(bool(relu))
+        _lib.check(lib.munit_batchnorm_fwd(_p(x), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var), b * h * w, c,
+                                           _p(gamma), _p(beta), relu, 0, c_float(eps), c_float(momentum), _p(ws), ws.numel(),
+                                           _stream()), "batchnorm_fwd")
+        ctx.relu = relu
+        ctx.want = bool(need_weight_grads)
+        ctx.gbuf = getattr(gamma, "_munit_grad", None)
+        ctx.bbuf = getattr(beta, "_munit_grad", None)
+        ctx.save_for_backward(x, y if relu else None, gamma, mean, rstd)
+        if DANN_SINK is not None and relu:
+            DANN_SINK.append(y > 0)
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, y, gamma, mean, rstd = ctx.saved_tensors
+        dy = nhwc(dy)
+        b, c, h, w = x.shape
+        dx = torch.empty_like(x)
+        want = ctx.want and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        into = want and ctx.gbuf is not None and ctx.bbuf is not None
+        dgamma = dbeta = None
+        if want:
+            dgamma = ctx.gbuf if into else torch.empty_like(gamma)
+            dbeta = ctx.bbuf if into else torch.empty_like(gamma)
+        ws = workspace(lib.munit_batchnorm_workspace_bytes(c), x.device)
+        _lib.check(lib.munit_batchnorm_bwd(_p(x), _p(dy), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta),
+                                           c_float(1.0 if into else 0.0), b * h * w, c, ctx.relu, _p(ws), ws.numel(),
+                                           _stream()), "batchnorm_bwd")
+        if into or not want:
+            return dx, None, None, None, None, None, None, None, None
+        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None, None, None, None,
+                None, None, None)
+
+
+def batch_norm(x, gamma, beta, running_mean, running_var, relu=False, eps=1e-5, momentum=0.1, training=True,
+               need_weight_grads=True):
+    """nn.BatchNorm2d (scripts/utils.py:1293) [+ReLU].  training: normalise with the batch statistics (biased variance) and
+    move the running statistics in place (unbiased variance); else normalise with the running statistics (no gradient
+    is defined for that form: it completes the module, the classifier never takes it)."""
+    if training:
+        return _BatchNorm.apply(x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads)
+    _require(x, "batch-norm input")
+    lib = _lib.load()
+    x = nhwc(x.detach())
+    b, c, h, w = x.shape
+    for t, nm in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _require(t, "batch-norm " + nm)
+        if tuple(t.shape) != (c,) or not t.is_contiguous():
+            raise RuntimeError("munit_amd.batch_norm: %s must be a contiguous (%d,) tensor" % (nm, c))
+    _same_device(x, gamma, beta, running_mean, running_var)
+    y = torch.empty_like(x)
+    with _on(x):
+        _lib.check(lib.munit_batchnorm_fwd(_p(x), _p(y), None, None, _p(running_mean), _p(running_var), b * h * w, c,
+                                           _p(gamma), _p(beta), int(bool(relu)), 1, c_float(eps), c_float(momentum), None, 0,
+                                           _stream()), "batchnorm_fwd (eval)")
+    return y
+
+
+class _MaxPool2(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, x):
+        lib = _lib.load()
+        _require(x, "maxpool input")
+        x = nhwc(x)
+        b, c, h, w = x.shape
+        if h < 2 or w < 2 or c % 4:
+            raise RuntimeError("munit_amd.maxpool2: needs H, W >= 2 and C %% 4 == 0, got %s" % (tuple(x.shape),))
+        y = empty_nhwc(b, c, h // 2, w // 2, x)
+        idx = torch.empty((b, h // 2, w // 2, c), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.munit_maxpool2_fwd(_p(x), _p(y), _p(idx), b, h, w, c, _stream()), "maxpool2_fwd")
+        if DANN_SINK is not None:
+            DANN_SINK.append(idx)
+        ctx.shape = x.shape
+        ctx.save_for_backward(idx)
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        (idx,) = ctx.saved_tensors
+        b, c, h, w = ctx.shape
+        dy = nhwc(dy)
+        dx = empty_nhwc(b, c, h, w, dy)
+        _lib.check(lib.munit_maxpool2_bwd(_p(dy), _p(idx), _p(dx), b, h, w, c, _stream()), "maxpool2_bwd")
+        return dx
+
+
+def maxpool2(x):
+    """nn.MaxPool2d(2) (scripts/utils.py:1374): floor output size, ties to the first maximal element in window order."""
+    return _MaxPool2.apply(x)
+
+
+class _AvgPool16(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, x):
+        lib = _lib.load()
+        _require(x, "avgpool16 input")
+        x = nhwc(x)
+        b, c, h, w = x.shape
+        y = torch.empty((b, c), device=x.device, dtype=torch.float32)
+        _lib.check(lib.munit_avgpool16_fwd(_p(x), _p(y), b, h, w, c, _stream()), "avgpool16_fwd")
+        ctx.shape = x.shape
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        b, c, h, w = ctx.shape
+        dy = dy.contiguous()
+        dx = empty_nhwc(b, c, h, w, dy)
+        _lib.check(lib.munit_avgpool16_bwd(_p(dy), _p(dx), b, h, w, c, _stream()), "avgpool16_bwd")
+        return dx
+
+
+def avgpool16(x):
+    """nn.AvgPool2d((16, 16)) + .squeeze() on a map of 16..31 per axis (scripts/utils.py:1378, 1388): (B, C)."""
+    return _AvgPool16.apply(x)

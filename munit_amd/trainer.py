@@ -19,8 +19,15 @@ The semantic-consistency loss (semantic_w > 0 with a semantic_ckpt_path) runs th
 the device (munit_amd/segmentation.py).  The synthetic-pair iteration of scripts/train.py:229-260 --
 gen_update(..., synth=True, semantic_gt_a, semantic_gt_b) -- adds the pair reconstruction loss (recon_synth_w) and takes
 the semantic loss against the simulator's label maps, the 19 logits merged into 10 classes inside the head kernel; the
-caller hands the pairs, masks and label maps in as tensors (the synthetic data loader is not part of this package).  The
-other aux losses (VGG, domain classifiers) raise NotImplementedError when their weight is non-zero.
+caller hands the pairs, masks and label maps in as tensors (the synthetic data loader is not part of this package).
+
+Feature-level domain adaptation (adaptation.dfeat_lambda > 0, trainer.py:161-179): two domainClassifier(256) networks on the
+content codes, trained by domain_classifier_sr_update (training-mode BatchNorm2d, max-pool and 16x16 average are HIP kernels
+of their own, dann.hip) under their own optimizer classif_opt_sr; adaptation.adv_lambda > 0 adds the fooling term
+(target 0.5) to gen_update, whose backward forms the gradient of the two content codes only -- the classifiers' weight
+gradients, which the reference computes and zeroes unused (trainer.py:1241), are skipped.  fp32 and one device only; like
+the reference, save / resume do not carry the classifiers.  The other aux losses (VGG, the a/b domain classifier of
+domain_adv_w, sem_seg_lambda, the output classifiers) raise NotImplementedError when their weight is non-zero.
 """
 import os
 import warnings
@@ -30,7 +37,8 @@ import torch.nn as nn
 from torch.optim import Optimizer
 
 from . import ops
-from .networks import AdaINGen, AdaINGen_double, ContentEncoder, InstanceNorm2d, MsImageDis, _ApplyRefreshesImages
+from .networks import (AdaINGen, AdaINGen_double, ContentEncoder, InstanceNorm2d, MsImageDis, _ApplyRefreshesImages,
+                       domainClassifier)
 from .segmentation import colorize, seg_loss
 from .utils import get_model_list, get_scheduler, load_segmentation_model, normalize_config, weights_init
 
@@ -216,6 +224,12 @@ FORCE_ALLREDUCE = bool(os.environ.get("MUNIT_FORCE_ALLREDUCE"))
 # Data-parallel exchange of the generator gradient in two parts (SURVEY.md section 8e "launch on a side stream to overlap
 # with the remaining backward"): see GradExchange.  MUNIT_NO_OVERLAP_EXCHANGE=1 = one all-reduce after backward (A/B, tests).
 OVERLAP_EXCHANGE = not os.environ.get("MUNIT_NO_OVERLAP_EXCHANGE")
+
+
+def dp_size():
+    """Number of data-parallel ranks (1 without a process group)."""
+    import torch.distributed as dist
+    return dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
 
 
 def dp_world():
@@ -461,6 +475,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.train_seg = hyperparameters["adaptation"]["sem_seg_lambda"] > 0
         self.use_output_classifier_sr = hyperparameters["adaptation"]["output_classifier_lambda"] > 0
         self._check_aux(hyperparameters)
+        self._check_featda(hyperparameters, self.use_classifier_sr)
 
         if self.gen_state == 0:
             self.gen_a = AdaINGen(hyperparameters["input_dim_a"], hyperparameters["gen"])
@@ -510,6 +525,18 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self._check_semantic(hyperparameters)
             self.segmentation_model = load_segmentation_model(hyperparameters["semantic_ckpt_path"], 19)
 
+        # feature classifiers of the simulated / real adaptation (trainer.py:161-179): one optimizer over both, a scheduler
+        # that update_learning_rate never steps, nothing of them in save / resume
+        if self.use_classifier_sr:
+            self.domain_classifier_sr_b = domainClassifier(256)
+            self.domain_classifier_sr_a = domainClassifier(256)
+            dann_params = list(self.domain_classifier_sr_a.parameters()) + list(self.domain_classifier_sr_b.parameters())
+            self.classif_opt_sr = optimizer([p for p in dann_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
+                                            weight_decay=hyperparameters["weight_decay"])
+            self.domain_classifier_sr_a.apply(weights_init("gaussian"))
+            self.domain_classifier_sr_b.apply(weights_init("gaussian"))
+            self.classif_sr_scheduler = get_scheduler(self.classif_opt_sr, hyperparameters)
+
         self._consts = {}
         # deferred discriminator exchange + step (data parallel, _defer_dis_step)
         self._dis_pending, self._dis_event, self._dis_waited = None, None, set()
@@ -528,13 +555,38 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             bad.append("semantic_w (without a semantic_ckpt_path)")
         if hp.get("domain_adv_w", 0) > 0:
             bad.append("domain_adv_w")
-        for k in ("adv_lambda", "dfeat_lambda", "sem_seg_lambda", "output_classifier_lambda", "output_adv_lambda"):
+        for k in ("sem_seg_lambda", "output_classifier_lambda", "output_adv_lambda"):
             if hp["adaptation"].get(k, 0) > 0:
                 bad.append("adaptation." + k)
         if bad:
             raise NotImplementedError(
                 "munit_amd covers the AdaINGen + MsImageDis training step only; set these weights to 0 "
                 "(they need external checkpoints / models outside the hot path): " + ", ".join(bad))
+
+    @staticmethod
+    def _check_featda(hp, built):
+        """Refusals of adaptation.adv_lambda / adaptation.dfeat_lambda, before any device work.  built: whether this trainer
+        was constructed with dfeat_lambda > 0 (it then owns the classifiers)."""
+        ad = hp["adaptation"]
+        adv, dfeat = ad.get("adv_lambda", 0) > 0, ad.get("dfeat_lambda", 0) > 0
+        if adv and not (dfeat and built):
+            raise ValueError("munit_amd: adaptation.adv_lambda > 0 needs adaptation.dfeat_lambda > 0 at construction (the "
+                             "classifiers the generator is to fool are built and trained under dfeat_lambda)")
+        if not (adv or dfeat):
+            return
+        if hp.get("precision", "f32") != "f32":
+            raise NotImplementedError("munit_amd: adaptation.adv_lambda / adaptation.dfeat_lambda run in fp32 only "
+                                      "(precision %r)" % hp["precision"])
+        if dp_size() > 1:
+            raise NotImplementedError("munit_amd: adaptation.adv_lambda / adaptation.dfeat_lambda are not implemented for "
+                                      "data-parallel training (world size %d): the classifiers' gradients and batch "
+                                      "statistics are not exchanged" % dp_size())
+        n = hp["gen"]["n_downsample"]
+        try:
+            domainClassifier.check_code_hw(hp["crop_image_height"] >> n, hp["crop_image_width"] >> n)
+        except ValueError as e:
+            raise ValueError("munit_amd: adaptation.dfeat_lambda / adaptation.adv_lambda cannot run at crop %dx%d with "
+                             "gen.n_downsample %d: %s" % (hp["crop_image_height"], hp["crop_image_width"], n, e)) from None
 
     @staticmethod
     def _check_semantic(hp):
@@ -605,6 +657,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
     def _bind(self, device):
         self.dis_opt.bind(device)
         self.gen_opt.bind(device)
+        if self.use_classifier_sr:
+            self.classif_opt_sr.bind(device)
         self._consts = {}
         # flat-gradient ranges of the decoders and MLPs (final before the first encodes' backward: GradExchange)
         gens = [self.gen] if self.gen_state == 1 else [self.gen_a, self.gen_b]
@@ -645,12 +699,65 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         else:
             self.gen_opt.step()
 
+    def classif_opt_sr_step(self):
+        """trainer.py:243-250."""
+        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
+            self.classif_opt_sr.extrapolation()
+        else:
+            self.classif_opt_sr.step()
+
     # ---- criteria (trainer.py:279-305) ------------------------------------------------
     def recon_criterion(self, input, target):
         return ops.l1_mean(input, target)
 
     def recon_criterion_mask(self, input, target, mask):
         return ops.l1_mean(input, target, mask)
+
+    # ---- simulated / real feature classifiers (trainer.py:638-667, 1237-1265) -----------
+    @staticmethod
+    def _sr_target(domain_synth, fool):
+        return 0.5 if fool else (0.0 if domain_synth else 1.0)
+
+    def compute_classifier_sr_loss(self, c_a, c_b, domain_synth=False, fool=False, need_weight_grads=True):
+        """mean((cls_a(c_a) - t)^2) + mean((cls_b(c_b) - t)^2), t = 0.5 to fool, else 0 for synthetic and 1 for real codes.
+        need_weight_grads False (build extension): the backward pass forms the gradients of c_a / c_b only."""
+        if not self.use_classifier_sr:
+            raise ValueError("munit_amd: compute_classifier_sr_loss needs a trainer built with adaptation.dfeat_lambda > 0")
+        t = self._sr_target(domain_synth, fool)
+        output_a = self.domain_classifier_sr_a(c_a, need_weight_grads)
+        output_b = self.domain_classifier_sr_b(c_b, need_weight_grads)
+        return ops.scalar_sum([ops.mse_const(output_a, t), ops.mse_const(output_b, t)])
+
+    def domain_classifier_sr_update(self, x_a, x_b, domain_synth, lambda_classifier, step, comet_exp=None):
+        """trainer.py:1237-1265.  The codes are detached there: the encodes run without a tape, and only the content
+        encoders run (the style codes the reference also forms are never used)."""
+        ops.set_compute(self.precision)
+        if not self.use_classifier_sr:
+            raise ValueError("munit_amd: domain_classifier_sr_update needs a trainer built with adaptation.dfeat_lambda > 0")
+        self._check_featda(self.hyperparameters, True)
+        self.classif_opt_sr.zero_grad()
+        dev = x_a.device
+        x_a, x_b = ops.nhwc(x_a), ops.nhwc(x_b)
+        t = self._sr_target(domain_synth, False)
+        br = _Branches(dev)
+        br.adopt(x_a, x_b)
+
+        def half(x, k, cls):
+            with torch.no_grad():
+                c = self._content_enc(k)(x)
+            return ops.mse_const(cls(c.detach()), t)
+
+        l_a = br.run(0, lambda: half(x_a, 1, self.domain_classifier_sr_a))
+        l_b = br.run(1, lambda: half(x_b, 2, self.domain_classifier_sr_b))
+        br.join(l_a, l_b)
+        loss = ops.scalar_sum([l_a, l_b])
+        self.loss_classifier_sr_update = loss.detach()      # unweighted; the reference logs lambda_classifier * loss
+        torch.autograd.backward([loss], [self._const(lambda_classifier, dev)])
+        br.join()
+        ops.join_side_streams()
+        self.classif_opt_sr_step()
+        if comet_exp is not None and self.iterations % 100 == 0:
+            comet_exp.log_metric("loss_classifier_sr", (lambda_classifier * self.loss_classifier_sr_update).cpu(), step=step)
 
     # ---- generator dispatch -----------------------------------------------------------
     def _enc(self, x, k):
@@ -719,6 +826,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             raise NotImplementedError("munit_amd: semantic_gt_a / semantic_gt_b run on the device only (there is no host "
                                       "path for any loss); move the trainer and the images to a HIP device")
         self._check_aux(normalize_config(hp))
+        self._check_featda(hp, self.use_classifier_sr)
+        fool_sr = hp["adaptation"]["adv_lambda"] > 0
         self.gen_opt.zero_grad()
         # the reference draws these even when guided == 1 leaves them unused (trainer.py:366-367)
         s_a = torch.randn(x_a.size(0), self.style_dim, 1, 1)
@@ -766,6 +875,12 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             else:
                 raise ValueError("self.guided unknown value: %r" % (self.guided,))
             br.share(c_a, c_b, s_a_use, s_b_use)
+            sr_a = sr_b = None
+            if fool_sr:
+                # the fooling term (trainer.py:521-525) on the step's own codes; the classifiers' weight gradients would be
+                # zeroed unused by domain_classifier_sr_update (trainer.py:1241): only the codes' gradients are formed
+                sr_a = br.run(0, lambda: ops.mse_const(self.domain_classifier_sr_a(c_a, False), 0.5))
+                sr_b = br.run(1, lambda: ops.mse_const(self.domain_classifier_sr_b(c_b, False), 0.5))
             if reuse:
                 x_ba, x_ab = x_ba_kept, x_ab_kept
             else:
@@ -804,7 +919,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                 self.loss_gen_cycrecon_x_b = 0
             br.join(self.loss_gen_recon_x_a, self.loss_gen_recon_x_b, self.loss_gen_recon_s_a, self.loss_gen_recon_s_b,
                     self.loss_gen_recon_c_a, self.loss_gen_recon_c_b, self.loss_gen_cycrecon_x_a,
-                    self.loss_gen_cycrecon_x_b, self.loss_gen_adv_a, self.loss_gen_adv_b)
+                    self.loss_gen_cycrecon_x_b, self.loss_gen_adv_a, self.loss_gen_adv_b, sr_a, sr_b)
+            self.loss_classifier_sr = ops.scalar_sum([sr_a, sr_b]) if fool_sr else 0
             if pair_term or self.semantic_w:
                 br.join(x_ab, x_ba)            # both translations on the caller's stream
             if pair_term:
@@ -818,7 +934,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             for p in d_params:
                 p.requires_grad_(True)
         self.loss_gen_vgg_a = self.loss_gen_vgg_b = 0
-        self.domain_adv_loss = self.loss_classifier_sr = self.loss_output_classifier_sr = 0
+        self.domain_adv_loss = self.loss_output_classifier_sr = 0
 
         pairs = [(hp["gan_w"], self.loss_gen_adv_a), (hp["gan_w"], self.loss_gen_adv_b),
                  (hp["recon_x_w"], self.loss_gen_recon_x_a), (hp["recon_s_w"], self.loss_gen_recon_s_a),
@@ -831,6 +947,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             pairs.append((hp["semantic_w"], self.loss_sem_seg))
         if pair_term:
             pairs.append((hp["recon_synth_w"], self.loss_gen_recon_synth))
+        if fool_sr:
+            pairs.append((hp["adaptation"]["adv_lambda"], self.loss_classifier_sr))
         self.loss_gen_total = ops.weighted_sum([t.detach() for _, t in pairs], [w for w, _ in pairs])
         live = [(w, t) for w, t in pairs if w != 0 and t.requires_grad]
         xch = None
@@ -859,7 +977,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                               "loss_gen_recon_c_a", "loss_gen_recon_x_b", "loss_gen_recon_s_b",
                               "loss_gen_recon_c_b", "loss_gen_cycrecon_x_a", "loss_gen_cycrecon_x_b",
                               "loss_gen_total") + (("loss_sem_seg",) if self.semantic_w else ())
-                  + (("loss_gen_recon_synth",) if synth else ()))
+                  + (("loss_gen_recon_synth",) if synth else ()) + (("loss_classifier_sr",) if fool_sr else ()))
 
     # ---- dis_update (trainer.py:1133-1190) ---------------------------------------------
     def dis_update(self, x_a, x_b, hyperparameters, comet_exp=None):
