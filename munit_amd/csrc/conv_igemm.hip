@@ -1484,20 +1484,29 @@ __global__ void box2x2_kernel(const f32x4* __restrict__ dy, f32x4* __restrict__ 
   }
 }
 
+enum DgradRoute {
+  DG_WINO_S2,      // 4x4 stride-2 pad-1 fp32 layer: four F(3x3, 2x2) parity phases over dy (conv_wino.hip, KIND 2)
+  DG_WINO,         // 3x3 stride-1 pad-1 fp32 layer: Winograd F(2x2, 3x3) with the border fold in the input patch (conv_wino.hip)
+  DG_SMALL,        // 3 input channels, 7x7: padded-domain correlation on the head kernel (conv_small.hip) + fold_scalar_kernel
+  DG_FOLD_UPWINO,  // up-sampling 5x5 conv: interior as one Winograd launch over the four dy phases (KIND 3), 2-pixel frame folded
+  DG_FOLD_BOXSUM,  // up-sampling 5x5 conv: interior through the 2x2 box sum of dy, 2-pixel frame through the folded gather
+  DG_FOLD,         // stride-1, Cout % 32 == 0: pad / upsample adjoint folded into the gather (ROLE 2)
+  DG_CIN4,         // three output channels (the image head): dy re-laid with a zero 4th channel, 4-channel taps + fold
+  DG_DIRECT,       // the correlation writes dx itself (1x1 convs, linear layers); with an `add` operand it runs as DG_CORR
+  DG_CORR          // one launch phase per stride parity into the padded-domain buffer g + fold
+};
 struct DgradPlan {
+  int rc;                 // nothing else is filled in unless it is MUNIT_OK
+  DgradRoute route;
   int Ho, Wo, ps, TH, TW, Hq, Wq;
-  bool direct;  // write dx directly (no pad / upsample / add): 1x1 convs, linear layers
-  bool folded;  // stride-1, Cout % 32 == 0: pad/upsample adjoint folded into the gather (ROLE 2)
-  bool small;   // 3 input channels, 7x7: padded-domain correlation on the thread-per-pixel VALU kernel
-  bool boxsum;  // up-sampling 5x5 conv: interior through the 2x2 box sum of dy, 2-pixel frame through the folded gather
-  bool bf16s;   // dy (and the weight image) are bf16 in HBM: bf16-storage kernels (direct-to-LDS forms only)
-  bool patch;   // folded with at most two padded positions per axis: the LDS-patch form
-  bool upwino;  // boxsum layer whose interior runs as one Winograd launch over the four dy phases (conv_wino.hip, KIND 3)
-  bool wino_s2; // 4x4 stride-2 pad-1 fp32 layer: four F(3x3, 2x2) parity phases over dy (conv_wino.hip, KIND 2)
-  bool wino;    // 3x3 stride-1 pad-1 fp32 layer: Winograd F(2x2, 3x3) with the border fold in the input patch (conv_wino.hip)
-  bool cin4;    // three output channels (the image head): dy re-laid with a zero 4th channel, direct-to-LDS 4-channel taps
-  size_t wt_bytes, g_bytes, sk_bytes, c4_bytes;
-  size_t small_ws;   // small: workspace of the 3-output-channel forward kernel that computes the padded-domain correlation
+  bool bf16s;             // dy (and the weight image) are bf16 in HBM: bf16-storage kernels (direct-to-LDS forms only)
+  bool patch;             // DG_FOLD with at most two padded positions per axis: the LDS-patch form (IgemmParams.patch)
+  munit_prep_item prep;   // the weight image the pass multiplies by, pointers null
+  munit_conv_desc t;      // DG_SMALL: the padded-domain correlation as a forward layer (dy in, 3 channels out)
+  Cin4Plan cin4;          // DG_CIN4
+  // workspace = [weight image][g][tail]; tail = split-K slabs (slab_bytes) | DG_SMALL: the head kernel's workspace |
+  // DG_CIN4: [4-channel dy][padded weights]
+  size_t off_g, off_tail, slab_bytes, ws_bytes;
 };
 // number of padded/up-sampled coordinates folding onto one source coordinate (host mirror of fold_cands)
 int max_fold_cands(int H, int ups, int P, int reflect) {
@@ -1518,87 +1527,96 @@ int max_fold_cands(int H, int ups, int P, int reflect) {
   }
   return worst;
 }
-int plan_dgrad(const munit_conv_desc* d, DgradPlan* pl) {
-  int rc = munit_conv2d_out_hw(d, &pl->Ho, &pl->Wo);
-  if (rc) return rc;
-  MUNIT_CHECK_ARG(d->KH % d->stride == 0 && d->KW % d->stride == 0,
-                  "conv2d_dgrad: kernel %dx%d not a multiple of stride %d", d->KH, d->KW, d->stride);
-  pl->ps = d->stride;
-  pl->TH = d->KH / d->stride;
-  pl->TW = d->KW / d->stride;
-  pl->Hq = d->stride * (pl->Ho + pl->TH - 1);
-  pl->Wq = d->stride * (pl->Wo + pl->TW - 1);
-  pl->direct = d->pad == 0 && d->upsample == 0 && pl->Hq == d->H && pl->Wq == d->W;
+// The route of a backward-data pass and what follows from it, decided HERE and nowhere else: workspace, weight image, launch,
+// kernel name and executed FLOPs all read the plan.  The tests run in the order written.  Three special routes come first and
+// exclude each other by the filter: WINO_S2 needs 4x4 at stride 2, WINO 3x3 at stride 1 (both pad 1, upsample == 0, fp32), SMALL
+// 7x7 at stride 1 with Cin == 3.  What they leave takes the first general route that holds:
+//   * the fold routes: !direct, stride 1, Cout % 32 == 0, few enough fold candidates (bf16 storage: patchable as well).  Among
+//     them BOXSUM needs upsample == 1 and a 5x5 filter, and UPWINO is BOXSUM under further conditions;
+//   * CIN4: !direct, stride 1, Cout == 3 -- never a fold layer, and with Cin % 4 == 0 never SMALL;
+//   * DIRECT or CORR, by `direct`: no pad, no up-sampling and the stride phases tile H x W exactly, so the padded domain IS dx and
+//     the correlation writes it without a fold kernel.  (pad == 1 keeps both Winograd routes apart from it; SMALL asks for !direct.)
+// A WINO or SMALL layer may be foldable too: there the order decides.
+// Kept as they were found, though they look unintended:
+//   * wino_geometry_ok refuses act == TANH, a property of the forward epilogue, and so keeps such a layer's dx off DG_WINO;
+//   * SMALL is tried before the fold routes, so a 7x7 layer with 3 input channels and Cout % 32 == 0 never folds;
+//   * MUNIT_DEBUG_NO_FOLD takes `patch` with it, so it sends the bf16-storage layers to DG_CORR as well;
+//   * DG_FOLD_UPWINO takes no box sum, yet its g is sized for S like DG_FOLD_BOXSUM's.
+DgradPlan plan_dgrad(const munit_conv_desc* d) {
+  DgradPlan pl{};
+  if ((pl.rc = munit_conv2d_out_hw(d, &pl.Ho, &pl.Wo)) != MUNIT_OK) return pl;
+  if (d->KH % d->stride != 0 || d->KW % d->stride != 0) {
+    munit_set_error("conv2d_dgrad: kernel %dx%d not a multiple of stride %d", d->KH, d->KW, d->stride);
+    pl.rc = MUNIT_ERR_ARG;
+    return pl;
+  }
+  pl.ps = d->stride;
+  pl.TH = d->KH / d->stride;
+  pl.TW = d->KW / d->stride;
+  pl.Hq = d->stride * (pl.Ho + pl.TH - 1);
+  pl.Wq = d->stride * (pl.Wo + pl.TW - 1);
+  const bool direct = d->pad == 0 && d->upsample == 0 && pl.Hq == d->H && pl.Wq == d->W;
   const int reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-  pl->folded = !pl->direct && d->stride == 1 && d->Cout % 32 == 0 && d->KH == d->KW &&
-               (d->H << d->upsample) + 2 * d->pad < 0xFFFF && (d->W << d->upsample) + 2 * d->pad < 0xFFFF &&
-               max_fold_cands(d->H, d->upsample, d->pad, reflect) <= 4 &&
-               max_fold_cands(d->W, d->upsample, d->pad, reflect) <= 4;
-  {
-    munit_conv_desc t{};
-    t.B = d->B; t.H = pl->Ho; t.W = pl->Wo; t.Cin = d->Cout; t.Cout = d->Cin; t.KH = pl->TH; t.KW = pl->TW;
-    t.stride = 1; t.pad = pl->TH - 1; t.pad_mode = MUNIT_PAD_ZERO;
-    pl->small = !pl->direct && pl->ps == 1 && munit_small_fwd_supported(&t) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_DGRAD");
-    if (pl->small) pl->folded = false;
-    pl->small_ws = pl->small ? munit_small_fwd_workspace(&t) : 0;
-    if (MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_FOLD")) pl->folded = false;
+  munit_conv_desc& t = pl.t;
+  t.B = d->B; t.H = pl.Ho; t.W = pl.Wo; t.Cin = d->Cout; t.Cout = d->Cin; t.KH = pl.TH; t.KW = pl.TW;
+  t.stride = 1; t.pad = pl.TH - 1; t.pad_mode = MUNIT_PAD_ZERO; t.upsample = 0; t.act = MUNIT_ACT_NONE;
+  t.in_dtype = d->out_dtype; t.out_dtype = MUNIT_DTYPE_F32;
+  int kind = MUNIT_PREP_DGRAD;
+  if (wino_s2_dgrad_ok(d)) {
+    pl.route = DG_WINO_S2; kind = MUNIT_PREP_WINOGRAD_S2_DGRAD;
+  } else if (wino_geometry_ok(d) && munit_wino_ok(d->B, d->H, d->W, d->Cout, d->Cin)) {
+    pl.route = DG_WINO; kind = MUNIT_PREP_WINOGRAD_DGRAD;
+  } else if (!direct && pl.ps == 1 && munit_small_fwd_supported(&t) && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SMALL_DGRAD")) {
+    pl.route = DG_SMALL;   // (reads a bf16 dy itself: no bf16 weight image)
+  } else {
+    // bf16 storage: dy is bf16 (d->out_dtype), dx / the padded-domain buffer g take d->in_dtype.  Only the direct-to-LDS
+    // forms exist in this mode: folded layers must be patchable, everything else runs as a plain correlation + fold_kernel
+    // (the up-sampling convs then issue all 100 MACs per source pixel: cheap on the bf16 pipe, and no box sum).
+    pl.bf16s = d->out_dtype == MUNIT_DTYPE_BF16;
+    const bool foldable = !direct && d->stride == 1 && d->Cout % 32 == 0 && d->KH == d->KW &&
+                          (d->H << d->upsample) + 2 * d->pad < 0xFFFF && (d->W << d->upsample) + 2 * d->pad < 0xFFFF &&
+                          max_fold_cands(d->H, d->upsample, d->pad, reflect) <= 4 &&
+                          max_fold_cands(d->W, d->upsample, d->pad, reflect) <= 4 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_FOLD");
+    pl.patch = foldable && d->upsample == 0 && max_fold_cands(d->H, 0, d->pad, reflect) <= 2 &&
+               max_fold_cands(d->W, 0, d->pad, reflect) <= 2;
+    if (foldable && (!pl.bf16s || pl.patch)) {
+      const bool boxsum = !pl.bf16s && d->in_dtype == MUNIT_DTYPE_F32 && d->upsample == 1 && d->KH == 5 && d->pad == 2 && reflect &&
+                          d->Cin % 4 == 0 && d->H >= 8 && d->W >= 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_BOXSUM");
+      const bool upwino = boxsum && d->compute == MUNIT_COMPUTE_F32 && d->H % 2 == 0 && d->W % 2 == 0 && d->Cout % 8 == 0 &&
+                          d->Cin % 64 == 0 && (long long)d->B * 4 * d->H * d->W * d->Cout < (1ll << 29) &&
+                          !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINOGRAD");
+      pl.route = upwino ? DG_FOLD_UPWINO : boxsum ? DG_FOLD_BOXSUM : DG_FOLD;
+      if (upwino) kind = MUNIT_PREP_SUBPIXEL_WINOGRAD_DGRAD;
+    } else if (!direct && pl.ps == 1 && d->Cout == 3 && d->out_dtype == MUNIT_DTYPE_F32 && pl.TH * pl.TW <= 64 && d->Cin % 4 == 0 &&
+               NWAVES == 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_CIN4")) {
+      pl.route = DG_CIN4;
+    } else {
+      pl.route = direct ? DG_DIRECT : DG_CORR;
+    }
   }
-  pl->patch = pl->folded && d->upsample == 0 && max_fold_cands(d->H, 0, d->pad, reflect) <= 2 &&
-              max_fold_cands(d->W, 0, d->pad, reflect) <= 2;
-  pl->wino_s2 = wino_s2_dgrad_ok(d);
-  if (pl->wino_s2) {
-    pl->direct = pl->folded = pl->small = pl->patch = pl->boxsum = pl->bf16s = pl->cin4 = pl->wino = pl->upwino = false;
-    pl->wt_bytes = align_up((size_t)4 * wino_image_elems(d->Cout, d->Cin) * 4, 256);
-    pl->g_bytes = 256;
-    pl->sk_bytes = pl->c4_bytes = pl->small_ws = 0;
-    return MUNIT_OK;
+  pl.prep = munit_prep_item{nullptr, nullptr, d->Cout, d->KH, d->KW, d->Cin, kind, pl.ps, pl.bf16s};
+  pl.off_g = align_up((size_t)prep_elems(pl.prep) * (pl.bf16s ? 2 : 4), 256);
+  // g, the padded-domain buffer in dx's element type.  DG_DIRECT has it for a call with an `add` operand, which the plan cannot see.
+  size_t g_bytes = align_up((size_t)d->B * pl.Hq * pl.Wq * d->Cin * (d->in_dtype == MUNIT_DTYPE_BF16 ? 2 : 4), 256), tail = 0;
+  switch (pl.route) {
+    case DG_WINO_S2: case DG_WINO: case DG_FOLD: g_bytes = 256; break;   // dx is written directly, `add` added onto it
+    case DG_SMALL: tail = munit_small_fwd_workspace(&t); break;
+    case DG_FOLD_UPWINO: case DG_FOLD_BOXSUM:   // g holds S; the frame launch (few tiles, 25-tap K) is split over K
+      g_bytes = align_up((size_t)d->B * pl.Ho * pl.Wo * d->Cout * sizeof(float), 256);
+      tail = pl.slab_bytes = splitk_bytes(d->B * (4 * d->W + 4 * (d->H - 4)), d->Cin, d->KH * d->KW * d->Cout, 1);
+      break;
+    case DG_CIN4:
+      pl.cin4 = plan_cin4((long long)d->B * pl.Ho * pl.Wo, d->Cin, pl.TH * pl.TW);
+      tail = pl.cin4.x4_bytes + pl.cin4.w4_bytes;
+      break;
+    case DG_DIRECT: case DG_CORR:   // (bf16 storage: no split-K, see launch_igemm)
+      if (!pl.bf16s)
+        tail = pl.slab_bytes = splitk_bytes(d->B * (pl.Ho + pl.TH - 1) * (pl.Wo + pl.TW - 1), d->Cin, pl.TH * pl.TW * d->Cout, pl.ps * pl.ps);
+      break;
   }
-  pl->wino = wino_geometry_ok(d) && munit_wino_ok(d->B, d->H, d->W, d->Cout, d->Cin);
-  if (pl->wino) {
-    pl->direct = pl->folded = pl->small = pl->patch = pl->boxsum = pl->bf16s = pl->cin4 = pl->upwino = pl->wino_s2 = false;
-    pl->wt_bytes = align_up((size_t)wino_image_elems(d->Cout, d->Cin) * 4, 256);
-    pl->g_bytes = 256;
-    pl->sk_bytes = pl->c4_bytes = pl->small_ws = 0;
-    return MUNIT_OK;
-  }
-  // bf16 storage: dy is bf16 (d->out_dtype), dx / the padded-domain buffer g take d->in_dtype.  Only the direct-to-LDS
-  // forms exist in this mode: folded layers must be patchable, everything else runs as a plain correlation + fold_kernel
-  // (the up-sampling convs then issue all 100 MACs per source pixel: cheap on the bf16 pipe, and no box sum).
-  pl->bf16s = d->out_dtype == MUNIT_DTYPE_BF16 && !pl->small;
-  if (pl->bf16s && !pl->patch) pl->folded = false;
-  pl->boxsum = pl->folded && !pl->bf16s && d->in_dtype == MUNIT_DTYPE_F32 && d->upsample == 1 && d->KH == 5 && d->pad == 2 &&
-               reflect && d->Cout % 32 == 0 && d->Cin % 4 == 0 && d->H >= 8 && d->W >= 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_BOXSUM");
-  pl->upwino = pl->boxsum && d->compute == MUNIT_COMPUTE_F32 && d->out_dtype == MUNIT_DTYPE_F32 && d->H % 2 == 0 && d->W % 2 == 0 &&
-               d->Cout % 8 == 0 && d->Cin % 64 == 0 && (long long)d->B * 4 * d->H * d->W * d->Cout < (1ll << 29) &&
-               !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_WINOGRAD");
-  const size_t esz = d->in_dtype == MUNIT_DTYPE_BF16 ? 2 : 4;   // element size of dx and g
-  pl->wt_bytes = align_up((size_t)d->Cout * d->KH * d->KW * d->Cin * (pl->bf16s ? 2 : 4), 256);
-  if (pl->upwino) pl->wt_bytes = align_up(((size_t)d->Cout * 25 * d->Cin + (size_t)4 * wino_image_elems(d->Cout, d->Cin)) * 4, 256);
-  pl->g_bytes = align_up((size_t)d->B * pl->Hq * pl->Wq * d->Cin * esz, 256);
-  if (pl->folded) pl->g_bytes = 256;  // no padded-domain buffer (an `add` operand falls back, see below)
-  if (pl->boxsum) pl->g_bytes = align_up((size_t)d->B * pl->Ho * pl->Wo * d->Cout * sizeof(float), 256);  // S
-  pl->cin4 = false;
-  pl->c4_bytes = 0;
-  if (pl->bf16s) {
-    pl->sk_bytes = 0;
-    return MUNIT_OK;
-  }
-  if (!pl->direct && !pl->folded && !pl->small && pl->ps == 1 && d->Cout == 3 && d->out_dtype == MUNIT_DTYPE_F32 &&
-      pl->TH * pl->TW <= 64 && d->Cin % 4 == 0 && NWAVES == 8 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_CIN4")) {
-    const Cin4Plan c = plan_cin4((long long)d->B * pl->Ho * pl->Wo, d->Cin, pl->TH * pl->TW);
-    pl->cin4 = true;
-    pl->c4_bytes = c.x4_bytes + c.w4_bytes;
-    pl->sk_bytes = 0;
-    return MUNIT_OK;
-  }
-  if (pl->boxsum) {
-    pl->sk_bytes = splitk_bytes(d->B * (4 * d->W + 4 * (d->H - 4)), d->Cin, d->KH * d->KW * d->Cout, 1);
-    return MUNIT_OK;
-  }
-  pl->sk_bytes = pl->small ? pl->small_ws : pl->folded ? 0
-                 : splitk_bytes(d->B * (pl->Ho + pl->TH - 1) * (pl->Wo + pl->TW - 1), d->Cin,
-                                pl->TH * pl->TW * d->Cout, pl->ps * pl->ps);
-  return MUNIT_OK;
+  pl.off_tail = pl.off_g + g_bytes;
+  pl.ws_bytes = pl.off_tail + tail;
+  return pl;
 }
 
 // Launch parameters of the backward-data entry point (pointers left null), shared with munit_igemm_kernel_name like
@@ -1640,7 +1658,7 @@ void set_boxsum_frame(IgemmParams* p, const munit_conv_desc* d) {
   p->frame = 2;
   p->M = d->B * (4 * d->W + 4 * (d->H - 4));
 }
-// plain correlation over the padded domain, one launch phase per stride parity (fold_kernel follows unless pl.direct)
+// plain correlation over the padded domain, one launch phase per stride parity (a fold kernel follows unless the route is DG_DIRECT)
 IgemmParams dgrad_corr_params(const munit_conv_desc* d, const DgradPlan& pl) {
   IgemmParams p{};
   p.B = d->B; p.H = pl.Ho; p.W = pl.Wo; p.Cin = d->Cout;
@@ -1667,9 +1685,8 @@ bool fold_vectorised(const munit_conv_desc* d) { return d->Cin % 4 == 0; }   // 
 }  // namespace
 
 extern "C" size_t munit_conv2d_dgrad_workspace_bytes(const munit_conv_desc* d) {
-  DgradPlan pl;
-  if (plan_dgrad(d, &pl)) return 0;
-  return pl.wt_bytes + pl.g_bytes + pl.sk_bytes + pl.c4_bytes;
+  const DgradPlan pl = plan_dgrad(d);
+  return pl.rc ? 0 : pl.ws_bytes;
 }
 
 extern "C" int munit_conv2d_dgrad(const munit_conv_desc* d, const void* dy, const float* w,
@@ -1690,17 +1707,34 @@ int launch_fold(const munit_conv_desc* d, const DgradPlan& pl, const void* g, co
   MUNIT_CHECK_LAUNCH("fold");
   return MUNIT_OK;
 }
+int launch_fold_scalar(const munit_conv_desc* d, const DgradPlan& pl, const float* g, const float* add, float* dx, hipStream_t st) {
+  const int reflect = d->pad_mode == MUNIT_PAD_REFLECT;
+  long long total = (long long)d->B * d->H * d->W * d->Cin;
+  int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
+  hipLaunchKernelGGL(fold_scalar_kernel, dim3(blocks), dim3(256), 0, st, g, add, dx, d->B, d->H, d->W,
+                     d->Cin, d->upsample, d->pad, reflect, pl.Hq, pl.Wq);
+  MUNIT_CHECK_LAUNCH("fold");
+  return MUNIT_OK;
+}
+// dx += add, for the routes that write dx without a fold kernel
+int launch_add_inplace(const munit_conv_desc* d, float* dx, const float* add, hipStream_t st) {
+  long long n = (long long)d->B * d->H * d->W * d->Cin;
+  int blocks = (int)std::min<long long>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks), dim3(256), 0, st, dx, add, n);
+  MUNIT_CHECK_LAUNCH("add_inplace");
+  return MUNIT_OK;
+}
 }  // namespace
 
 extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void* dy_, const float* w, const void* wp,
                                            const void* add_, void* dx_, void* ws, size_t ws_bytes,
                                            munit_stream_t stream) {
-  DgradPlan pl;
-  int rc = plan_dgrad(d, &pl);
+  const DgradPlan pl = plan_dgrad(d);
+  int rc = pl.rc;
   if (rc) return rc;
   MUNIT_CHECK_ARG(dy_ && (w || wp) && dx_ && ws, "conv2d_dgrad: null pointer");
-  if (ws_bytes < pl.wt_bytes + pl.g_bytes + pl.sk_bytes + pl.c4_bytes) {
-    munit_set_error("conv2d_dgrad: workspace %zu < %zu", ws_bytes, pl.wt_bytes + pl.g_bytes + pl.sk_bytes + pl.c4_bytes);
+  if (ws_bytes < pl.ws_bytes) {
+    munit_set_error("conv2d_dgrad: workspace %zu < %zu", ws_bytes, pl.ws_bytes);
     return MUNIT_ERR_WORKSPACE;
   }
   // element types: dy = d->out_dtype, dx / add / g = d->in_dtype.  The fp32 names below keep the fp32 code readable; in
@@ -1712,125 +1746,84 @@ extern "C" int munit_conv2d_dgrad_prepared(const munit_conv_desc* d, const void*
   MUNIT_CHECK_ARG(!dx_bf16 || d->Cin % 4 == 0, "conv2d_dgrad: bf16 dx needs Cin %% 4 == 0");
   hipStream_t st = (hipStream_t)stream;
   const float* wt = reinterpret_cast<const float*>(wp);
-  float* g = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + pl.wt_bytes);
-  const bool direct = pl.direct && add == nullptr;
+  float* g = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + pl.off_g);
+  char* tail = reinterpret_cast<char*>(ws) + pl.off_tail;
   if (wt == nullptr) {   // no prepared image from the caller: re-lay the weights into the workspace
-    PrepItem it{w, reinterpret_cast<float*>(ws), d->Cout, d->KH, d->KW, d->Cin,
-                pl.wino_s2 ? MUNIT_PREP_WINOGRAD_S2_DGRAD : pl.wino ? MUNIT_PREP_WINOGRAD_DGRAD
-                : pl.upwino ? MUNIT_PREP_SUBPIXEL_WINOGRAD_DGRAD : MUNIT_PREP_DGRAD, pl.ps, pl.bf16s ? 1 : 0};
+    munit_prep_item it = pl.prep;
+    it.w = w; it.wp = reinterpret_cast<float*>(ws);
     rc = launch_prep_one(it, st);
     if (rc) return rc;
     wt = it.wp;
   }
-  if (pl.wino_s2) {
-    rc = munit_wino_launch(wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD_S2, dy, wt, nullptr, dx), st);
-    if (rc) return rc;
-    if (add != nullptr) {
-      long long n = (long long)d->B * d->H * d->W * d->Cin;
-      int blocks = (int)std::min<long long>((n + 255) / 256, 8192);
-      hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks), dim3(256), 0, st, dx, add, n);
-      MUNIT_CHECK_LAUNCH("add_inplace");
+  switch (pl.route) {
+    case DG_WINO_S2:
+      rc = munit_wino_launch(wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD_S2, dy, wt, nullptr, dx), st);
+      if (rc || add == nullptr) return rc;
+      return launch_add_inplace(d, dx, add, st);
+    case DG_WINO: {
+      WinoParams q = wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD, dy, wt, nullptr, dx);
+      q.add = add;    // added in the kernel's epilogue (dx and add share the layout)
+      return munit_wino_launch(q, st);
     }
-    return MUNIT_OK;
-  }
-  if (pl.wino) {
-    WinoParams q = wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD, dy, wt, nullptr, dx);
-    q.add = add;    // added in the kernel's epilogue (dx and add share the layout)
-    return munit_wino_launch(q, st);
-  }
-  {
-    // data gradient of a 7x7 conv with 3 input channels (first encoder layers): the padded-domain
-    // correlation has N = 3 -> thread-per-pixel VALU kernel instead of a 95 %-padded MFMA tile
-    munit_conv_desc t{};
-    t.B = d->B; t.H = pl.Ho; t.W = pl.Wo; t.Cin = d->Cout; t.Cout = d->Cin; t.KH = pl.TH; t.KW = pl.TW;
-    t.stride = 1; t.pad = pl.TH - 1; t.pad_mode = MUNIT_PAD_ZERO; t.upsample = 0; t.act = MUNIT_ACT_NONE;
-    t.in_dtype = d->out_dtype; t.out_dtype = MUNIT_DTYPE_F32;
-    if (pl.small) {
+    case DG_SMALL:
+      // data gradient of a 7x7 conv with 3 input channels (first encoder layers): the padded-domain
+      // correlation has N = 3 -> thread-per-pixel VALU kernel instead of a 95 %-padded MFMA tile
       MUNIT_CHECK_ARG(!dx_bf16, "conv2d_dgrad: the 3-channel data gradient is fp32");
-      rc = munit_small_fwd(&t, pl.Hq, pl.Wq, dy_, wt, nullptr, g, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, st);
+      rc = munit_small_fwd(&pl.t, pl.Hq, pl.Wq, dy_, wt, nullptr, g, tail, st);
       if (rc) return rc;
-      const int reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-      long long total = (long long)d->B * d->H * d->W * d->Cin;
-      int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-      hipLaunchKernelGGL(fold_scalar_kernel, dim3(blocks), dim3(256), 0, st, g, add, dx, d->B, d->H, d->W,
-                         d->Cin, d->upsample, d->pad, reflect, pl.Hq, pl.Wq);
-      MUNIT_CHECK_LAUNCH("fold");
-      return MUNIT_OK;
-    }
-  }
-  if (pl.folded) {
-    IgemmParams p = dgrad_fold_params(d, pl);
-    p.x = dy; p.w = wt; p.bias = nullptr; p.y = dx;
-    MUNIT_CHECK_ARG(dgrad_fold_dtypes_ok(d, pl), "conv2d_dgrad: unsupported dtype combination");
-    if (pl.boxsum && pl.upwino) {
-      // interior source pixels 2..H-3 x 2..W-3 as ONE Winograd launch: the four output phases of dy are 3x3-correlated with the
-      // rotated merged filters and summed (K = 4 Cout); no box sum, no padding
-      rc = munit_wino_launch(wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD_UP, dy, wt + (size_t)d->Cout * 25 * d->Cin, nullptr,
-                                         dx + ((long long)2 * d->W + 2) * d->Cin), st);
-      if (rc) return rc;
-      set_boxsum_frame(&p, d);
-      rc = launch_igemm<2>(p, 1, st, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, pl.sk_bytes);
-    } else if (pl.boxsum) {
-      // interior source pixels 2..H-3 x 2..W-3: dx[i][j] = sum_taps wt[t][r] . S[2i-2+t][2j-2+r] -- one gather per element
-      {
-        const long long total = (long long)d->B * pl.Ho * pl.Wo * (d->Cout / 4);
-        hipLaunchKernelGGL(box2x2_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 16384)), dim3(256), 0, st,
-                           reinterpret_cast<const f32x4*>(dy), reinterpret_cast<f32x4*>(g), d->B, pl.Ho, pl.Wo, d->Cout / 4);
-        MUNIT_CHECK_LAUNCH("box2x2");
+      return launch_fold_scalar(d, pl, g, add, dx, st);
+    case DG_FOLD_UPWINO: case DG_FOLD_BOXSUM: case DG_FOLD: {
+      IgemmParams p = dgrad_fold_params(d, pl);
+      p.x = dy; p.w = wt; p.bias = nullptr; p.y = dx;
+      MUNIT_CHECK_ARG(dgrad_fold_dtypes_ok(d, pl), "conv2d_dgrad: unsupported dtype combination");
+      if (pl.route == DG_FOLD) {
+        rc = launch_igemm<2>(p, 1, st);
+      } else {
+        if (pl.route == DG_FOLD_UPWINO) {
+          // interior source pixels 2..H-3 x 2..W-3 as ONE Winograd launch: the four output phases of dy are 3x3-correlated with
+          // the rotated merged filters and summed (K = 4 Cout); no box sum, no padding
+          rc = munit_wino_launch(wino_params(d, pl.Ho, pl.Wo, WINO_DGRAD_UP, dy, wt + (size_t)d->Cout * 25 * d->Cin, nullptr,
+                                             dx + ((long long)2 * d->W + 2) * d->Cin), st);
+        } else {
+          // interior source pixels 2..H-3 x 2..W-3: dx[i][j] = sum_taps wt[t][r] . S[2i-2+t][2j-2+r] -- one gather per element
+          const long long total = (long long)d->B * pl.Ho * pl.Wo * (d->Cout / 4);
+          hipLaunchKernelGGL(box2x2_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 16384)), dim3(256), 0, st,
+                             reinterpret_cast<const f32x4*>(dy), reinterpret_cast<f32x4*>(g), d->B, pl.Ho, pl.Wo, d->Cout / 4);
+          MUNIT_CHECK_LAUNCH("box2x2");
+          IgemmParams q = boxsum_interior_params(p, d);
+          q.x = g;
+          q.y = dx + ((long long)2 * d->W + 2) * d->Cin;
+          rc = launch_igemm<0>(q, 1, st);
+        }
+        if (rc) return rc;
+        // the 2-pixel frame keeps the general folded gather (reflections add further positions there), split over K
+        set_boxsum_frame(&p, d);
+        rc = launch_igemm<2>(p, 1, st, tail, pl.slab_bytes);
       }
-      IgemmParams q = boxsum_interior_params(p, d);
-      q.x = g;
-      q.y = dx + ((long long)2 * d->W + 2) * d->Cin;
-      rc = launch_igemm<0>(q, 1, st);
-      if (rc) return rc;
-      // the 2-pixel frame keeps the general folded gather (reflections add further positions there), split over K
-      set_boxsum_frame(&p, d);
-      rc = launch_igemm<2>(p, 1, st, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, pl.sk_bytes);
-    } else {
-      rc = launch_igemm<2>(p, 1, st);
-    }
-    if (rc) return rc;
-    if (add != nullptr) {
+      if (rc || add == nullptr) return rc;
       MUNIT_CHECK_ARG(!dx_bf16, "conv2d_dgrad: `add` with a bf16 dx is not supported on the folded path");
-      long long n = (long long)d->B * d->H * d->W * d->Cin;
-      int blocks = (int)std::min<long long>((n + 255) / 256, 8192);
-      hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks), dim3(256), 0, st, dx, add, n);
-      MUNIT_CHECK_LAUNCH("add_inplace");
+      return launch_add_inplace(d, dx, add, st);
     }
-    return MUNIT_OK;
+    case DG_CIN4: case DG_DIRECT: case DG_CORR: break;   // the padded-domain correlation below
   }
   MUNIT_CHECK_ARG(pl.TH == pl.TW, "conv2d_dgrad: non-square kernels are not supported");
+  const bool direct = pl.route == DG_DIRECT && add == nullptr;
   IgemmParams p = dgrad_corr_params(d, pl);
   p.x = dy; p.w = wt; p.bias = nullptr; p.y = direct ? (void*)dx : (void*)g;
-  if (pl.cin4) {
+  if (pl.route == DG_CIN4) {
     // image head: dy has three channels -> 4-channel re-layout of dy and of the transposed weights, direct-to-LDS taps
-    char* c4 = reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes;
-    const long long npix = (long long)d->B * pl.Ho * pl.Wo;
-    const Cin4Plan c = plan_cin4(npix, d->Cin, pl.TH * pl.TW);
-    rc = build_cin4(c, dy, npix, wt, d->Cin, pl.TH * pl.TW, c4, st);
+    rc = build_cin4(pl.cin4, dy, (long long)d->B * pl.Ho * pl.Wo, wt, d->Cin, pl.TH * pl.TW, tail, st);
     if (rc) return rc;
-    p.x = reinterpret_cast<const float*>(c4);
-    p.w = reinterpret_cast<const float*>(c4 + c.x4_bytes);
-    set_cin4(&p, c);
+    p.x = reinterpret_cast<const float*>(tail);
+    p.w = reinterpret_cast<const float*>(tail + pl.cin4.x4_bytes);
+    set_cin4(&p, pl.cin4);
     rc = launch_igemm<1>(p, 1, st);
   } else {
-    rc = launch_igemm<1>(p, pl.ps * pl.ps, st, reinterpret_cast<char*>(ws) + pl.wt_bytes + pl.g_bytes, pl.sk_bytes);
+    rc = launch_igemm<1>(p, pl.ps * pl.ps, st, tail, pl.slab_bytes);
   }
-  if (rc) return rc;
-  if (!direct) {
-    const int reflect = d->pad_mode == MUNIT_PAD_REFLECT;
-    if (fold_vectorised(d)) {
-      rc = dx_bf16 ? launch_fold<bf16_t>(d, pl, g, add_, dx_, st) : launch_fold<float>(d, pl, g, add_, dx_, st);
-      if (rc) return rc;
-    } else {
-      long long total = (long long)d->B * d->H * d->W * d->Cin;
-      int blocks = (int)std::min<long long>((total + 255) / 256, 8192);
-      hipLaunchKernelGGL(fold_scalar_kernel, dim3(blocks), dim3(256), 0, st, g, add, dx, d->B, d->H, d->W,
-                         d->Cin, d->upsample, d->pad, reflect, pl.Hq, pl.Wq);
-      MUNIT_CHECK_LAUNCH("fold");
-    }
-  }
-  return MUNIT_OK;
+  if (rc || direct) return rc;
+  if (!fold_vectorised(d)) return launch_fold_scalar(d, pl, g, add, dx, st);
+  return dx_bf16 ? launch_fold<bf16_t>(d, pl, g, add_, dx_, st) : launch_fold<float>(d, pl, g, add_, dx_, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1842,20 +1835,15 @@ extern "C" int munit_conv2d_prep_item(const munit_conv_desc* d, int pass, const 
   if (rc) return rc;
   MUNIT_CHECK_ARG(out != nullptr, "conv2d_prep_item: null item");
   MUNIT_CHECK_ARG(pass == MUNIT_PASS_FWD || pass == MUNIT_PASS_DGRAD, "conv2d_prep_item: pass must be MUNIT_PASS_FWD or _DGRAD");
-  munit_prep_item it{w, wp, d->Cout, d->KH, d->KW, d->Cin, MUNIT_PREP_NONE, 1, 0};
+  munit_prep_item it;
   if (pass == MUNIT_PASS_FWD) {
-    const FwdPlan fp = plan_fwd(d);
-    it.kind = fp.prep.kind;
-    it.bf16 = fp.prep.bf16;
+    it = plan_fwd(d).prep;
   } else {
-    DgradPlan pl;
-    rc = plan_dgrad(d, &pl);
-    if (rc) return rc;
-    it.kind = pl.wino_s2 ? MUNIT_PREP_WINOGRAD_S2_DGRAD : pl.wino ? MUNIT_PREP_WINOGRAD_DGRAD
-              : pl.upwino ? MUNIT_PREP_SUBPIXEL_WINOGRAD_DGRAD : MUNIT_PREP_DGRAD;
-    it.ps = pl.ps;
-    it.bf16 = pl.bf16s ? 1 : 0;
+    const DgradPlan pl = plan_dgrad(d);
+    if (pl.rc) return pl.rc;
+    it = pl.prep;
   }
+  it.w = w; it.wp = wp;
   *out = it;
   return MUNIT_OK;
 }
@@ -1963,49 +1951,48 @@ const char* munit_igemm_kernel_name(const munit_conv_desc* d, int pass) {
     if (f == IG_CT2) return "conv_igemm_kernel<.., 0, 2>";
     return "conv_igemm_kernel<fwd>";
   }
-  DgradPlan pl;
-  if (plan_dgrad(d, &pl)) return "invalid";
+  const DgradPlan pl = plan_dgrad(d);
+  if (pl.rc) return "invalid";
   if (x_bf16 && d->Cin % 4 != 0) return "refused: bf16 dx needs Cin % 4 == 0";
-  if (pl.wino) return refl ? "conv_wino_kernel<2, 0>" : "conv_wino_kernel<1, 0>";
-  if (pl.wino_s2) return refl ? "conv_wino_kernel<0, 2>" : "conv_wino_kernel<1, 2>";
-  // (the correlation reads dy: Cout input channels of d->out_dtype)
-  if (pl.small) return x_bf16 ? "refused: the 3-channel data gradient is fp32" : head[1][munit_small_fwd_kernel(d->Cout)][y_bf16];
-  if (pl.folded) {
-    if (!dgrad_fold_dtypes_ok(d, pl)) return "refused: unsupported dtype combination";
-    IgemmParams p = dgrad_fold_params(d, pl);
-    const int bn = igemm_bn(p);
-    if (pl.boxsum && pl.upwino) return "conv_wino_kernel<1, 3> + conv_igemm_kernel frame";
-    if (pl.boxsum) {
-      const IgemmForm in = igemm_form(boxsum_interior_params(p, d), 0);
-      set_boxsum_frame(&p, d);
-      const IgemmForm fr = igemm_form(p, 2);
-      if (igemm_refusal(in)) return igemm_refusal(in);
-      if (igemm_refusal(fr)) return igemm_refusal(fr);
-      if (in == IG_CT1 && fr == IG_CT1) return "box2x2_kernel + conv_igemm_kernel<.., 1> (box-sum backward-data)";
-      if (in == IG_CT2 && fr == IG_CT2) return "box2x2_kernel + conv_igemm_kernel<.., 2> (box-sum backward-data)";
-      return "box2x2_kernel + conv_igemm_kernel (box-sum backward-data)";
+  switch (pl.route) {
+    case DG_WINO_S2: return refl ? "conv_wino_kernel<0, 2>" : "conv_wino_kernel<1, 2>";
+    case DG_WINO: return refl ? "conv_wino_kernel<2, 0>" : "conv_wino_kernel<1, 0>";
+    // (the correlation reads dy: Cout input channels of d->out_dtype)
+    case DG_SMALL: return x_bf16 ? "refused: the 3-channel data gradient is fp32" : head[1][munit_small_fwd_kernel(d->Cout)][y_bf16];
+    case DG_FOLD_UPWINO: case DG_FOLD_BOXSUM: case DG_FOLD: {
+      if (!dgrad_fold_dtypes_ok(d, pl)) return "refused: unsupported dtype combination";
+      IgemmParams p = dgrad_fold_params(d, pl);
+      const int bn = igemm_bn(p);
+      if (pl.route == DG_FOLD_UPWINO) return "conv_wino_kernel<1, 3> + conv_igemm_kernel frame";
+      if (pl.route == DG_FOLD_BOXSUM) {
+        const IgemmForm in = igemm_form(boxsum_interior_params(p, d), 0);
+        set_boxsum_frame(&p, d);
+        const IgemmForm fr = igemm_form(p, 2);
+        if (igemm_refusal(in)) return igemm_refusal(in);
+        if (igemm_refusal(fr)) return igemm_refusal(fr);
+        if (in == IG_CT1 && fr == IG_CT1) return "box2x2_kernel + conv_igemm_kernel<.., 1> (box-sum backward-data)";
+        if (in == IG_CT2 && fr == IG_CT2) return "box2x2_kernel + conv_igemm_kernel<.., 2> (box-sum backward-data)";
+        return "box2x2_kernel + conv_igemm_kernel (box-sum backward-data)";
+      }
+      const IgemmForm f = igemm_form(p, 2);
+      if (igemm_refusal(f)) return igemm_refusal(f);
+      if (f == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 2, 4> (LDS-patch fold)" : "conv_igemm_kernel<128, true, 2, 4> (LDS-patch fold)";
+      if (f == IG_PATCH) return "conv_igemm_kernel<.., 2, 3> (LDS-patch fold)";
+      if (f == IG_CT1) return "conv_igemm_kernel<.., 2, 1> (folded gather)";
+      if (f == IG_CT2) return "conv_igemm_kernel<.., 2, 2> (folded gather)";
+      return "conv_igemm_kernel<.., 2, 0> (folded gather)";
     }
-    const IgemmForm f = igemm_form(p, 2);
-    if (igemm_refusal(f)) return igemm_refusal(f);
-    if (f == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 2, 4> (LDS-patch fold)" : "conv_igemm_kernel<128, true, 2, 4> (LDS-patch fold)";
-    if (f == IG_PATCH) return "conv_igemm_kernel<.., 2, 3> (LDS-patch fold)";
-    if (f == IG_CT1) return "conv_igemm_kernel<.., 2, 1> (folded gather)";
-    if (f == IG_CT2) return "conv_igemm_kernel<.., 2, 2> (folded gather)";
-    return "conv_igemm_kernel<.., 2, 0> (folded gather)";
+    case DG_CIN4: case DG_DIRECT: case DG_CORR: break;   // the padded-domain correlation below
   }
   if (pl.TH != pl.TW) return "refused: non-square kernels are not supported";
   IgemmParams p = dgrad_corr_params(d, pl);
   const int bn = igemm_bn(p);
-  if (pl.cin4) {
-    set_cin4(&p, plan_cin4(1, d->Cin, pl.TH * pl.TW));
-    const IgemmForm f = igemm_form(p, 1);
-    if (igemm_refusal(f)) return igemm_refusal(f);
-    return x_bf16 ? "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps) + fold_kernel<bf16_t>"
-                  : "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps)";
-  }
+  if (pl.route == DG_CIN4) set_cin4(&p, pl.cin4);
   const IgemmForm f = igemm_form(p, 1);
   if (igemm_refusal(f)) return igemm_refusal(f);
-  if (pl.direct) {      // (an `add` operand sends a direct layer through fold_kernel: the name is that of the call without one)
+  if (pl.route == DG_CIN4) return x_bf16 ? "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps) + fold_kernel<bf16_t>"
+                                         : "conv_igemm_kernel<.., 1, 5> (3 output channels as 4-channel taps)";
+  if (pl.route == DG_DIRECT) {   // (an `add` operand sends a direct layer through fold_kernel: the name is that of the call without one)
     if (f == IG_BF16S) return bn == 64 ? "conv_igemm_kernel<64, true, 1, 4> direct" : "conv_igemm_kernel<128, true, 1, 4> direct";
     if (f == IG_CT1) return "conv_igemm_kernel<.., 1, 1> direct";
     if (f == IG_CT2) return "conv_igemm_kernel<.., 1, 2> direct";
@@ -2036,17 +2023,20 @@ double munit_igemm_executed_flops(const munit_conv_desc* d, int pass) {
       default: return cc * d->B * Ho * Wo * d->KH * d->KW;
     }
   }
-  DgradPlan pl;
-  if (plan_dgrad(d, &pl)) return 0.0;
-  if (pl.wino) return cc * d->B * (d->H / 2) * (d->W / 2) * 16;
-  if (pl.wino_s2) return 4 * cc * d->B * cdiv(d->H / 2 + 1, 3) * cdiv(d->W / 2 + 1, 3) * 16;
-  if (pl.boxsum && pl.upwino) return cc * d->B * ((double)((d->H - 4) / 2) * ((d->W - 4) / 2) * 4 * 16 + (4.0 * d->W + 4.0 * (d->H - 4)) * 25);
-  if (pl.boxsum) return cc * d->B * ((double)(d->H - 4) * (d->W - 4) + 4.0 * d->W + 4.0 * (d->H - 4)) * d->KH * d->KW;
-  if (pl.folded) return cc * d->B * d->H * d->W * d->KH * d->KW;
-  if (pl.direct) return cc * d->B * Ho * Wo * d->KH * d->KW;
-  if (pl.cin4) return 2.0 * d->Cin * d->B * (double)(pl.Ho + pl.TH - 1) * (pl.Wo + pl.TW - 1) * plan_cin4(1, 1, pl.TH * pl.TW).kpad;
-  // phase launches over the padded domain (also the 3-channel first layer through the thread-per-pixel kernel)
-  return cc * d->B * (double)(pl.Ho + pl.TH - 1) * (pl.Wo + pl.TW - 1) * pl.TH * pl.TW * pl.ps * pl.ps;
+  const DgradPlan pl = plan_dgrad(d);
+  if (pl.rc) return 0.0;
+  switch (pl.route) {
+    case DG_WINO_S2: return 4 * cc * d->B * cdiv(d->H / 2 + 1, 3) * cdiv(d->W / 2 + 1, 3) * 16;
+    case DG_WINO: return cc * d->B * (d->H / 2) * (d->W / 2) * 16;
+    case DG_FOLD_UPWINO: return cc * d->B * ((double)((d->H - 4) / 2) * ((d->W - 4) / 2) * 4 * 16 + (4.0 * d->W + 4.0 * (d->H - 4)) * 25);
+    case DG_FOLD_BOXSUM: return cc * d->B * ((double)(d->H - 4) * (d->W - 4) + 4.0 * d->W + 4.0 * (d->H - 4)) * d->KH * d->KW;
+    case DG_FOLD: return cc * d->B * d->H * d->W * d->KH * d->KW;
+    case DG_DIRECT: return cc * d->B * Ho * Wo * d->KH * d->KW;
+    case DG_CIN4: return 2.0 * d->Cin * d->B * (double)(pl.Ho + pl.TH - 1) * (pl.Wo + pl.TW - 1) * pl.cin4.kpad;
+    // phase launches over the padded domain (also the 3-channel first layer through the thread-per-pixel kernel)
+    case DG_SMALL: case DG_CORR: return cc * d->B * (double)(pl.Ho + pl.TH - 1) * (pl.Wo + pl.TW - 1) * pl.TH * pl.TW * pl.ps * pl.ps;
+  }
+  return 0.0;   // (not reached: every route returns above)
 }
 
 // ---------------------------------------------------------------------------------------------------------
