@@ -5,9 +5,13 @@ update_learning_rate first, periodic save).  Control plane only -- no comet, FID
   python examples/train_loop.py --config configs.yaml --data-root /path/with/trainA,trainB,testA,testB [--iters N]
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_loop.py ...      (data parallel, RCCL)
 
-The synthetic-pair iteration of scripts/train.py:229-260 runs when main() is called from Python with `synth_pairs`, an
-iterator of (x_as, x_bs, mask_s, sem_a, sem_b) batches: this package has no synthetic data loader, so the caller supplies
-the tensors (sem_a / sem_b may be None, the reference's `synthetic_seg_gt: 0`).
+The synthetic-pair iteration of scripts/train.py:229-260 runs every `synthetic_frequency` iterations when the five lists
+of munit_amd.data.get_synthetic_data_loader are given: --synth-list-a, --synth-list-b, --synth-mask-list, --seg-list-a and
+--seg-list-b, each falling back to the config key the reference reads (data_list_train_a_synth, data_list_train_b_synth,
+data_list_train_b_seg_synth, seg_list_a, seg_list_b; scripts/train.py:104-117) when that file exists.  The loader is
+restarted when it runs out.  Called from Python, main() also takes `synth_pairs`, an iterator of
+(x_as, x_bs, mask_s, sem_a, sem_b) batches, which then takes precedence (sem_a / sem_b may be None, the reference's
+`synthetic_seg_gt: 0`).  Without the lists and without `synth_pairs` no synthetic iteration runs.
 """
 import argparse
 import os
@@ -19,12 +23,43 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+SYNTH_LISTS = (("synth_list_a", "data_list_train_a_synth"), ("synth_list_b", "data_list_train_b_synth"),
+               ("synth_mask_list", "data_list_train_b_seg_synth"), ("seg_list_a", "seg_list_a"), ("seg_list_b", "seg_list_b"))
+
+
+def synth_lists(args, config):
+    """The five list files of the synthetic loader, or None when one is missing: the command line first, then the config
+    key when the file it names exists."""
+    out = []
+    for arg, key in SYNTH_LISTS:
+        f = getattr(args, arg)
+        if not f and isinstance(config.get(key), str) and os.path.isfile(config[key]):
+            f = config[key]
+        if not f:
+            return None
+        out.append(f)
+    return out
+
+
+def restarting(loader):
+    """Batches of `loader` for ever: a new epoch (new order, new draws) whenever it runs out."""
+    while True:
+        n = 0
+        for batch in loader:
+            n += 1
+            yield batch
+        if n == 0:
+            raise RuntimeError("the synthetic loader yields no batch (fewer samples than one batch)")
+
+
 def main(argv=None, synth_pairs=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
     ap.add_argument("--data-root", default=None, help="folder with trainA/ trainB/ testA/ testB (overrides the YAML lists)")
     ap.add_argument("--file-list-a"), ap.add_argument("--file-list-b")
     ap.add_argument("--mask-list-a"), ap.add_argument("--mask-list-b")
+    ap.add_argument("--synth-list-a"), ap.add_argument("--synth-list-b"), ap.add_argument("--synth-mask-list")
+    ap.add_argument("--seg-list-a"), ap.add_argument("--seg-list-b")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--output", default=None, help="checkpoint directory")
     ap.add_argument("--save-every", type=int, default=0)
@@ -57,6 +92,11 @@ def main(argv=None, synth_pairs=None):
         root = args.data_root or config["data_root"]
         loader_a = D.get_data_loader_folder(os.path.join(root, "trainA"), b, True, ns, h, w, nw, seed=1)
         loader_b = D.get_data_loader_folder(os.path.join(root, "trainB"), b, True, ns, h, w, nw, seed=2)
+
+    if synth_pairs is None:                       # scripts/train.py:104-117: the synthetic paired loader
+        lists = synth_lists(args, config)
+        if lists is not None:
+            synth_pairs = restarting(D.get_synthetic_data_loader(*lists, b, True, ns, h, w, nw, seed=3))
 
     if args.output and local_rank == 0:
         os.makedirs(args.output, exist_ok=True)   # the reference's prepare_sub_folder (utils.py:817-834)

@@ -322,10 +322,11 @@ int munit_scale(const float* x, float* y, size_t n, float alpha, int accumulate,
 typedef struct {
   long long src_off;  /* byte offset of the image in pool */
   int src_h, src_w;   /* decoded size */
-  int rs_h, rs_w;     /* size after Resize (= src size when no resize); unused for masks */
+  int rs_h, rs_w;     /* size after Resize (= src size when no resize); unused by munit_mask_preprocess */
   int crop_i, crop_j; /* top-left corner of the crop window in the resized image */
   int flip;           /* 1: flipped left-right before the resize */
-  int reserved;
+  int kind;           /* munit_label_preprocess only: 0 mask, 1 label map.  munit_image_preprocess and
+                         munit_mask_preprocess ignore the field (it was `reserved`; the layout is unchanged) */
 } munit_image_desc;
 
 int munit_image_ksize(int src_size, int rs_size);
@@ -339,6 +340,21 @@ int munit_image_preprocess(const unsigned char* pool, const munit_image_desc* de
 size_t munit_mask_preprocess_workspace_bytes(int B, int out_h, int out_w);
 int munit_mask_preprocess(const unsigned char* pool, const munit_image_desc* descs, int B, int out_h,
                           int out_w, float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
+/* Plane chain of MyDatasetSynthetic.transform (utils.py:495-543) for N single-band uint8 planes -- for a batch of B
+ * synthetic samples N = 3B: the masks, the semantic_a maps, the semantic_b maps.  Unlike munit_mask_preprocess, each
+ * plane is flipped, resized with Pillow's NEAREST to the descriptor's (rs_w, rs_h) -- the size of the resized image --
+ * and cropped at (crop_i, crop_j); only the crop window is computed.  out: [N][out_h][out_w] fp32.
+ *   kind 0 (mask): 1.0f where (vmax == 1 ? v == 1 : v >= 128), else 0.0f, vmax = the maximum of the plane's crop
+ *     window: to_tensor (x255 when np.max of the cropped mask is 1) followed by > 0.5 -> 1, < 0.5 -> 0 (no byte gives
+ *     exactly 0.5);
+ *   kind 1 (label map): mapping() of utils.py:1356-1366 on the grey value -- 255 -> 8, 200 -> 7, 178 -> 6, 149 -> 5,
+ *     133 -> 4, 76 -> 3, 55 -> 2, 29 -> 1, every other value unchanged -- as a float.
+ * The descriptors are device memory and cannot be validated: a window position outside [0, rs) or a source index
+ * outside [0, src) reads no pixel and counts as grey value 0; nothing is read outside a plane of the stated size.
+ * The workspace holds the index tables and the per-plane maxima; there is no host synchronisation. */
+size_t munit_label_preprocess_workspace_bytes(int N, int out_h, int out_w);
+int munit_label_preprocess(const unsigned char* pool, const munit_image_desc* descs, int N, int out_h,
+                           int out_w, float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Semantic-consistency loss (scripts/trainer.py:706-771): the frozen Resnet34_8s segmentation network

@@ -36,7 +36,7 @@ class PrepItem(Structure):
 class ImageDesc(Structure):
     """munit_image_desc."""
     _fields_ = [("src_off", ctypes.c_longlong), ("src_h", c_int), ("src_w", c_int), ("rs_h", c_int), ("rs_w", c_int),
-                ("crop_i", c_int), ("crop_j", c_int), ("flip", c_int), ("reserved", c_int)]
+                ("crop_i", c_int), ("crop_j", c_int), ("flip", c_int), ("kind", c_int)]
 
 
 _P = c_void_p  # device pointers travel as integers
@@ -111,6 +111,8 @@ SIGNATURES = {
     "munit_image_preprocess": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "munit_mask_preprocess_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "munit_mask_preprocess": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "munit_label_preprocess_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "munit_label_preprocess": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "munit_seg_input_fwd": (c_int, [_P, _P, c_size_t, _P]),
     "munit_seg_input_bwd": (c_int, [_P, _P, c_size_t, _P]),
     "munit_space_to_batch": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

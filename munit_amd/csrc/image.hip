@@ -9,7 +9,8 @@
 // anti-aliased triangle filter, coefficients computed in double and rounded to 22-bit fixed point,
 // horizontal pass then vertical pass with a uint8 rounding between them -- restated here so that the
 // result is bit-identical to Image.resize.  Masks use the NEAREST path (ImagingScaleAffine: source
-// index tables from a running double accumulator).
+// index tables from a running double accumulator); so do the mask and the label maps of the synthetic
+// pairs (MyDatasetSynthetic.transform, utils.py:483-553), whose chain differs: munit_label_preprocess.
 #include "common.h"
 
 namespace {
@@ -116,8 +117,12 @@ __global__ void image_resample_kernel(const unsigned char* __restrict__ pool,
 
 // NEAREST index tables (ImagingScaleAffine): one thread per (sample, axis) walks xo += a0 in double.
 //   tab layout per sample: [out_h row indices][out_w column indices] (-1 = no source pixel)
+// windowed 0 (munit_mask_preprocess): the plane is resized to (out_w, out_h) and the table covers all of it.
+// windowed 1 (munit_label_preprocess): the plane is resized to the descriptor's (rs_w, rs_h) and the table keeps
+// the window [crop, crop + out) of that walk.  The accumulator always starts at index 0: (x + 0.5) * a rounds
+// differently from the running sum, and Pillow uses the running sum.  Window positions outside [0, rs) get -1.
 __global__ void nearest_tables_kernel(const munit_image_desc* __restrict__ descs, int B, int out_h, int out_w,
-                                      int* __restrict__ tab) {
+                                      int windowed, int* __restrict__ tab) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 2 * B) return;
   const int b = i >> 1;
@@ -125,12 +130,20 @@ __global__ void nearest_tables_kernel(const munit_image_desc* __restrict__ descs
   const munit_image_desc d = descs[b];
   const int in_size = is_row ? d.src_h : d.src_w;
   const int n = is_row ? out_h : out_w;
+  const int rs = windowed ? (is_row ? d.rs_h : d.rs_w) : n;
+  const int crop = windowed ? (is_row ? d.crop_i : d.crop_j) : 0;
   int* t = tab + (long long)b * (out_h + out_w) + (is_row ? 0 : out_h);
-  const double a = (double)in_size / (double)n;
+  if (windowed)
+    for (int x = 0; x < n; ++x) t[x] = -1;
+  long long end = (long long)crop + n;
+  if (end > rs) end = rs;
+  const double a = (double)in_size / (double)rs;
   double xo = 0.0 + a * 0.5;
-  for (int x = 0; x < n; ++x) {
-    const int xin = xo < 0.0 ? -1 : (int)xo;
-    t[x] = (xin >= 0 && xin < in_size) ? xin : -1;
+  for (long long x = 0; x < end; ++x) {
+    if (x >= crop) {
+      const int xin = xo < 0.0 ? -1 : (int)xo;
+      t[x - crop] = (xin >= 0 && xin < in_size) ? xin : -1;
+    }
     xo += a;
   }
 }
@@ -173,6 +186,80 @@ __global__ void mask_scale_kernel(float* __restrict__ out, const int* __restrict
     float t = __fdiv_rn(out[i], 255.f);       // ToTensor
     if (vmax[b] == 1) t = t * 255.f;          // utils.py:326-329
     out[i] = t;
+  }
+}
+
+// mapping() of the reference (utils.py:1356-1366) on a grey value: the simulator's nine label colours become class
+// indices, every other value stays what it is.  (v / 255f) * 255f == v for all 256 bytes, so this integer table is the
+// reference's to_tensor(x) * 255 followed by the fp32 equality tests.
+__device__ inline int label_class(int v) {
+  switch (v) {
+    case 255: return 8;
+    case 200: return 7;
+    case 178: return 6;
+    case 149: return 5;
+    case 133: return 4;
+    case 76: return 3;
+    case 55: return 2;
+    case 29: return 1;
+    default: return v;
+  }
+}
+
+constexpr int LABEL_BLOCK = 256;
+
+// Plane chain of MyDatasetSynthetic.transform (utils.py:495-543) for the mask (kind 0) and the two label maps (kind 1):
+// flip, NEAREST resize to the resized image's (rs_w, rs_h), crop at (crop_i, crop_j).  One thread per output pixel.
+// Label planes are finished here (mapping); mask planes store the grey value and take the maximum of their crop window
+// -- reduced in LDS first, so a workgroup issues one global atomic per plane it touches -- for label_finish_kernel.
+__global__ void __launch_bounds__(LABEL_BLOCK)
+label_gather_kernel(const unsigned char* __restrict__ pool, const munit_image_desc* __restrict__ descs, int N, int out_h,
+                    int out_w, const int* __restrict__ tab, float* __restrict__ out, int* __restrict__ vmax) {
+  __shared__ int smax[LABEL_BLOCK];     // 256 consecutive pixels touch at most 256 planes
+  const long long hw = (long long)out_h * out_w;
+  const long long total = (long long)N * hw;
+  for (long long base = (long long)blockIdx.x * LABEL_BLOCK; base < total; base += (long long)gridDim.x * LABEL_BLOCK) {
+    const int b0 = (int)(base / hw);
+    smax[threadIdx.x] = 0;
+    __syncthreads();
+    const long long i = base + threadIdx.x;
+    if (i < total) {
+      const int b = (int)(i / hw);
+      const int rem = (int)(i - (long long)b * hw);
+      const int y = rem / out_w, x = rem - y * out_w;
+      const munit_image_desc d = descs[b];
+      const int* t = tab + (long long)b * (out_h + out_w);
+      const int sy = t[y];
+      int sx = t[out_h + x];
+      int v = 0;
+      if (sy >= 0 && sx >= 0) {
+        if (d.flip) sx = d.src_w - 1 - sx;
+        v = pool[d.src_off + (long long)sy * d.src_w + sx];
+      }
+      if (d.kind != 0) {
+        out[i] = (float)label_class(v);
+      } else {
+        out[i] = (float)v;
+        if (v > 0) atomicMax(&smax[b - b0], v);
+      }
+    }
+    __syncthreads();
+    const int m = smax[threadIdx.x];
+    if (m > 0) atomicMax(&vmax[b0 + threadIdx.x], m);   // slot k is cleared by thread k itself: no barrier needed
+  }
+}
+
+// Mask rule of utils.py:537-543 in integers: to_tensor (x255 when the crop's maximum is 1), then > 0.5 -> 1, < 0.5 -> 0.
+// No byte lands on 0.5 (v / 255 for v = 127, 128 is 0.498, 0.502).
+__global__ void label_finish_kernel(const munit_image_desc* __restrict__ descs, float* __restrict__ out,
+                                    const int* __restrict__ vmax, int N, long long hw) {
+  const long long total = (long long)N * hw;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / hw);
+    if (descs[b].kind != 0) continue;
+    const int v = (int)out[i];
+    out[i] = (vmax[b] == 1 ? v == 1 : v >= 128) ? 1.0f : 0.0f;
   }
 }
 
@@ -232,7 +319,7 @@ extern "C" int munit_mask_preprocess(const unsigned char* pool, const munit_imag
     munit_set_error("mask_preprocess: memset failed");
     return MUNIT_ERR_LAUNCH;
   }
-  hipLaunchKernelGGL(nearest_tables_kernel, dim3(cdiv(2 * B, 64)), dim3(64), 0, st, descs, B, out_h, out_w, tab);
+  hipLaunchKernelGGL(nearest_tables_kernel, dim3(cdiv(2 * B, 64)), dim3(64), 0, st, descs, B, out_h, out_w, 0, tab);
   MUNIT_CHECK_LAUNCH("nearest_tables");
   hipLaunchKernelGGL(mask_gather_kernel, dim3(grid_for((long long)B * out_h * out_w)), dim3(256), 0, st, pool, descs, B,
                      out_h, out_w, tab, out, vmax);
@@ -240,5 +327,36 @@ extern "C" int munit_mask_preprocess(const unsigned char* pool, const munit_imag
   hipLaunchKernelGGL(mask_scale_kernel, dim3(grid_for((long long)B * out_h * out_w)), dim3(256), 0, st, out, vmax, B,
                      out_h * out_w);
   MUNIT_CHECK_LAUNCH("mask_scale");
+  return MUNIT_OK;
+}
+
+extern "C" size_t munit_label_preprocess_workspace_bytes(int N, int out_h, int out_w) {
+  return align_up((size_t)N * (out_h + out_w + 1) * sizeof(int), 256);
+}
+
+extern "C" int munit_label_preprocess(const unsigned char* pool, const munit_image_desc* descs, int N, int out_h,
+                                      int out_w, float* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(pool && descs && out && ws, "label_preprocess: null pointer");
+  MUNIT_CHECK_ARG(N > 0 && out_h > 0 && out_w > 0, "label_preprocess: bad shape");
+  if (ws_bytes < munit_label_preprocess_workspace_bytes(N, out_h, out_w)) {
+    munit_set_error("label_preprocess: workspace %zu < %zu", ws_bytes, munit_label_preprocess_workspace_bytes(N, out_h, out_w));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  int* tab = reinterpret_cast<int*>(ws);
+  int* vmax = tab + (size_t)N * (out_h + out_w);
+  if (hipMemsetAsync(vmax, 0, (size_t)N * sizeof(int), st) != hipSuccess) {
+    munit_set_error("label_preprocess: memset failed");
+    return MUNIT_ERR_LAUNCH;
+  }
+  const long long total = (long long)N * out_h * out_w;
+  hipLaunchKernelGGL(nearest_tables_kernel, dim3(cdiv(2 * N, 64)), dim3(64), 0, st, descs, N, out_h, out_w, 1, tab);
+  MUNIT_CHECK_LAUNCH("nearest_tables");
+  hipLaunchKernelGGL(label_gather_kernel, dim3(grid_for(total)), dim3(LABEL_BLOCK), 0, st, pool, descs, N, out_h, out_w, tab,
+                     out, vmax);
+  MUNIT_CHECK_LAUNCH("label_gather");
+  hipLaunchKernelGGL(label_finish_kernel, dim3(grid_for(total)), dim3(256), 0, st, descs, out, vmax, N,
+                     (long long)out_h * out_w);
+  MUNIT_CHECK_LAUNCH("label_finish");
   return MUNIT_OK;
 }

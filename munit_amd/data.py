@@ -5,13 +5,16 @@ Mirrors the loader API of the reference (same function names, argument order and
   get_data_loader_list(root, file_list, ...)       scripts/utils.py:192-250   (ImageFilelist, scripts/data.py:25-49)
   get_data_loader_folder(input_folder, ...)        scripts/utils.py:680-740   (ImageFolder, scripts/data.py:116-153)
   get_data_loader_mask_and_im(file_list, mask_list, ...)  scripts/utils.py:638-677 (MyDataset, utils.py:270-363)
+  get_synthetic_data_loader(file_list_a, file_list_b, mask_list, sem_list_a, sem_list_b, ...)
+                                                   scripts/utils.py:583-635   (MyDatasetSynthetic, utils.py:458-580)
   default_txt_reader / default_flist_reader        scripts/utils.py:253-267 / scripts/data.py:13-23
 
 Design (MI355X-first, not the reference's worker-process + CPU-transform pipeline):
   * host threads only DECODE files (PIL releases the GIL while decoding) into one pinned staging buffer
     per batch: [descriptors][image 0 bytes][image 1 bytes]... -> ONE async H2D copy per batch on a side stream;
   * flip / anti-aliased bilinear resize / crop / ToTensor / Normalize run as one HIP pass over the batch
-    (munit_image_preprocess, munit_mask_preprocess: csrc/image.hip, bit-identical to PIL + torchvision),
+    (munit_image_preprocess, munit_mask_preprocess, munit_label_preprocess: csrc/image.hip, bit-identical to PIL +
+    torchvision),
     producing the channels_last fp32 batch the convolutions consume -- no per-sample CPU tensors, no
     collate, no NCHW->NHWC copy;
   * a producer thread keeps `prefetch` batches in flight, so decode + PCIe of step n+1 overlap step n;
@@ -103,6 +106,23 @@ def _decode_mask(path):
                              % (path, im.mode))
         arr = np.frombuffer(im.tobytes(), dtype=np.uint8).reshape(im.size[1], im.size[0])
     return np.ascontiguousarray(arr)
+
+
+def _decode_l(path):
+    """Mask and label maps of the synthetic pairs: `.convert("L")`, as utils.py:566-568 (a `P` file goes through its
+    palette here, unlike _decode_mask's raw indices)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        arr = np.asarray(im.convert("L"), dtype=np.uint8)
+    return np.ascontiguousarray(arr)
+
+
+# mapping() of the reference (utils.py:1356-1366) on grey values: the simulator's label colours -> class indices; every
+# other grey value stays what it is.  csrc/image.hip (label_class) holds the same table.
+LABEL_CLASSES = {255: 8, 200: 7, 178: 6, 149: 5, 133: 4, 76: 3, 55: 2, 29: 1, 0: 0}
+LABEL_TABLE = tuple(LABEL_CLASSES.get(v, v) for v in range(256))
+
+KIND_MASK, KIND_LABEL = 0, 1         # munit_image_desc.kind as munit_label_preprocess reads it
 
 
 def pack_batch(arrays, masks, draws):
@@ -234,6 +254,95 @@ def transform_batch(arrays, masks, draws, device=None):
     return out
 
 
+def pack_synth_batch(images_a, images_b, masks, sems_a, sems_b, draws):
+    """Lay out one batch of synthetic pairs for the device.  Layout of the staging buffer:
+    [2B image descs: a..., b...][3B plane descs: masks..., semantic_a..., semantic_b...][pad to 256]
+    [a images][b images][masks][semantic_a maps][semantic_b maps] (every item 16-byte aligned).
+    draws[b] = (flip, rs_h, rs_w, crop_i, crop_j, out_h, out_w): ONE draw per sample, shared by its five descriptors;
+    the planes carry the resized IMAGE's (rs_h, rs_w), which munit_label_preprocess resizes them to.
+    Returns (descs, offsets in descriptor order, total)."""
+    B = len(images_a)
+    dsz = ctypes.sizeof(ImageDesc)
+    groups = [(images_a, 0), (images_b, 0), (masks, KIND_MASK), (sems_a, KIND_LABEL), (sems_b, KIND_LABEL)]
+    cur = (5 * B * dsz + 255) // 256 * 256
+    descs = (ImageDesc * (5 * B))()
+    offs = []
+    for g, (items, kind) in enumerate(groups):
+        for b, (a, dr) in enumerate(zip(items, draws)):
+            flip, rs_h, rs_w, i, j, _, _ = dr
+            descs[g * B + b] = ImageDesc(cur, a.shape[0], a.shape[1], rs_h, rs_w, i, j, flip, kind)
+            offs.append(cur)
+            cur += (a.nbytes + 15) // 16 * 16
+    return descs, offs, cur
+
+
+def launch_synth_transform(images_a, images_b, masks, sems_a, sems_b, draws, device, stream, ring=None):
+    """launch_transform for synthetic pairs: decoded uint8 images (H,W,3) of both domains and the three single-band
+    planes (h,w) of every sample go up in one staging buffer with one async copy; munit_image_preprocess runs once over
+    the 2B images and munit_label_preprocess once over the 3B planes.  Returns ((x_as, x_bs, mask_s, sem_a, sem_b),
+    ready event, buffers to keep alive): the images are the two halves of one (2B,3,h,w) channels_last batch, the other
+    three the thirds of one (3B,1,h,w) batch."""
+    lib = _lib.load()
+    B = len(images_a)
+    th, tw = draws[0][5], draws[0][6]
+    for a, b_, d in zip(images_a, images_b, draws):
+        for x in (a, b_):
+            if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
+                raise ValueError("images must be uint8 (H, W, 3) arrays")
+        if a.shape != b_.shape:
+            raise ValueError("the images of a synthetic pair differ in size: %s vs %s" % (a.shape[:2], b_.shape[:2]))
+        if (d[5], d[6]) != (th, tw):
+            raise ValueError("every sample of a batch needs the same crop size")
+        if d[3] < 0 or d[4] < 0 or d[3] + th > d[1] or d[4] + tw > d[2]:
+            raise ValueError("crop window (%d,%d,%d,%d) outside the resized image (%d,%d)" % (d[3], d[4], th, tw, d[1], d[2]))
+    for m in list(masks) + list(sems_a) + list(sems_b):
+        if m.dtype != np.uint8 or m.ndim != 2 or m.size == 0:
+            raise ValueError("masks and label maps must be non-empty uint8 (H, W) arrays")
+    descs, offs, total = pack_synth_batch(images_a, images_b, masks, sems_a, sems_b, draws)
+    slot = None
+    if ring is not None:
+        slot, stage = ring.take(total)
+    else:
+        stage = torch.empty(total, dtype=torch.uint8).pin_memory()
+    sv = stage.numpy()
+    ctypes.memmove(sv.ctypes.data, ctypes.addressof(descs), ctypes.sizeof(descs))
+    # copied here, in the calling (producer) thread, for the reason given in launch_transform
+    for a, o in zip(list(images_a) + list(images_b) + list(masks) + list(sems_a) + list(sems_b), offs):
+        sv[o:o + a.nbytes] = a.reshape(-1)
+    ksize = 3
+    for a, d in zip(images_a, draws):
+        ksize = max(ksize, lib.munit_image_ksize(a.shape[0], d[1]), lib.munit_image_ksize(a.shape[1], d[2]))
+    vp = ctypes.c_void_p
+    with torch.cuda.stream(stream):
+        dev = torch.empty(total, dtype=torch.uint8, device=device)
+        dev.copy_(stage[:total], non_blocking=True)     # the one H2D transfer of the batch
+        if slot is not None:
+            copied = torch.cuda.Event()
+            copied.record(stream)
+            ring.mark(slot, copied)
+        st = vp(stream.cuda_stream)
+        base = dev.data_ptr()
+        images = torch.empty((2 * B, 3, th, tw), device=device, dtype=torch.float32, memory_format=torch.channels_last)
+        nws = lib.munit_image_preprocess_workspace_bytes(2 * B, th, tw, ksize)
+        ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=device)
+        rc = lib.munit_image_preprocess(vp(base), vp(base), 2 * B, th, tw, ksize, vp(images.data_ptr()),
+                                        vp(ws.data_ptr()), ctypes.c_size_t(nws), st)
+        if rc:
+            raise RuntimeError("munit_image_preprocess: " + lib.munit_last_error().decode())
+        planes = torch.empty((3 * B, 1, th, tw), device=device, dtype=torch.float32)
+        nwl = lib.munit_label_preprocess_workspace_bytes(3 * B, th, tw)
+        wsl = torch.empty(max(nwl, 1), dtype=torch.uint8, device=device)
+        rc = lib.munit_label_preprocess(vp(base), vp(base + 2 * B * ctypes.sizeof(ImageDesc)), 3 * B, th, tw,
+                                        vp(planes.data_ptr()), vp(wsl.data_ptr()), ctypes.c_size_t(nwl), st)
+        if rc:
+            raise RuntimeError("munit_label_preprocess: " + lib.munit_last_error().decode())
+        keep = (dev, ws, wsl, images, planes) if slot is not None else (stage, dev, ws, wsl, images, planes)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+    out = (images[:B], images[B:], planes[:B], planes[B:2 * B], planes[2 * B:])
+    return out, ev, keep
+
+
 class _Dataset:
     """Indexable view used by scripts/train.py:133-143 (`loader.dataset[i]`): one transformed sample."""
 
@@ -312,6 +421,9 @@ class DeviceBatchLoader:
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=self.device)
 
+    def _files_per_sample(self):
+        return 2 if self.mask_paths is not None else 1
+
     def _submit_decodes(self, indices):
         """Hand the files of one batch to the decode threads; returns the futures (images, masks or None)."""
         futs = [self._pool.submit(_decode_rgb, self.image_paths[k]) for k in indices]
@@ -363,7 +475,7 @@ class DeviceBatchLoader:
         # threads while the producer packs and uploads the current one (round 2 decoded one batch at a time, so at most
         # batch_size of the threads ever worked and every batch also paid a fresh pinned allocation: 170 images/s whatever
         # the thread count).  The draws stay in batch order, so the random stream is unchanged.
-        ahead = max(2, (2 * self.num_workers) // max(1, self.batch_size * (2 if self.mask_paths is not None else 1)) + 1)
+        ahead = max(2, (2 * self.num_workers) // max(1, self.batch_size * self._files_per_sample()) + 1)
         ring = _StagingRing(self.prefetch + 3)
 
         def produce():
@@ -444,6 +556,86 @@ def get_data_loader_mask_and_im(file_list, mask_list, batch_size, train, new_siz
     if mpaths is None:
         return _WithEmptyMask(loader)
     return loader
+
+
+class _SyntheticDataset:
+    """`loader.dataset[i]`: the five transformed tensors of one sample, as MyDatasetSynthetic.__getitem__ returns them."""
+
+    def __init__(self, loader):
+        self._loader = loader
+
+    def __len__(self):
+        return len(self._loader.image_paths)
+
+    def __getitem__(self, index):
+        return tuple(t[0] for t in self._loader._run_batch([index], self._loader._rng))
+
+
+class SyntheticPairLoader(DeviceBatchLoader):
+    """Iterable of (x_as, x_bs, mask_s, sem_a, sem_b) device batches, like DataLoader(MyDatasetSynthetic): the images
+    (B,3,h,w) channels_last fp32 in [-1,1], the mask (0 / 1) and the two label maps (class indices) (B,1,h,w) fp32.
+    Every sample makes ONE draw -- the flip, whatever `train` says (utils.py:496), then the crop corner inside the resized
+    image_b -- shared by its five planes.  The prefetch thread, the staging ring and the sharding are the base class's."""
+
+    def __init__(self, paths_a, paths_b, mask_paths, sem_paths_a, sem_paths_b, batch_size, train, new_size, height, width,
+                 num_workers=4, device=None, seed=0, rank=None, world_size=None, prefetch=2):
+        names = ("file_list_a", "file_list_b", "mask_list", "sem_list_a", "sem_list_b")
+        lists = (paths_a, paths_b, mask_paths, sem_paths_a, sem_paths_b)
+        if len(set(len(p) for p in lists)) != 1:
+            raise ValueError("the five lists of the synthetic loader differ in length: "
+                             + ", ".join("%s %d" % (n, len(p)) for n, p in zip(names, lists)))
+        DeviceBatchLoader.__init__(self, paths_a, mask_paths, batch_size, train, new_size, height, width, num_workers,
+                                   True, device, seed, rank, world_size, prefetch, torch_flip=True)
+        self.pair_paths = list(paths_b)
+        self.sem_a_paths = list(sem_paths_a)
+        self.sem_b_paths = list(sem_paths_b)
+        self.dataset = _SyntheticDataset(self)
+
+    def _files_per_sample(self):
+        return 5
+
+    def sample_files(self, k):
+        return (self.image_paths[k], self.pair_paths[k], self.mask_paths[k], self.sem_a_paths[k], self.sem_b_paths[k])
+
+    def decode_sample(self, k):
+        """The five decoded planes of sample k (in the calling thread)."""
+        pa, pb, pm, sa, sb = self.sample_files(k)
+        return _decode_rgb(pa), _decode_rgb(pb), _decode_l(pm), _decode_l(sa), _decode_l(sb)
+
+    def draw_batch(self, indices, samples, rng):
+        """Host checks and draws of one batch, in sample order; no device work.  A pair whose two images differ in size is
+        refused: the reference would crop image_a with a window drawn for image_b and let PIL pad, which breaks the pixel
+        alignment the pair loss is defined on."""
+        draws = []
+        for k, (a, b_, _, _, _) in zip(indices, samples):
+            if a.shape != b_.shape:
+                raise ValueError("munit_amd.data: the images of synthetic pair %d differ in size: %s is %dx%d, %s is %dx%d"
+                                 % (k, self.image_paths[k], a.shape[1], a.shape[0], self.pair_paths[k], b_.shape[1],
+                                    b_.shape[0]))
+            draws.append(self.draw(b_.shape[1], b_.shape[0], rng))
+        return draws
+
+    def _submit_decodes(self, indices):
+        futs = [[self._pool.submit(_decode_rgb if n < 2 else _decode_l, p) for n, p in enumerate(self.sample_files(k))]
+                for k in indices]
+        return futs, list(indices)
+
+    def _finish_batch(self, futs, indices, rng, ring=None):
+        samples = [[f.result() for f in fs] for fs in futs]
+        draws = self.draw_batch(indices, samples, rng)
+        cols = list(zip(*samples))
+        return launch_synth_transform(cols[0], cols[1], cols[2], cols[3], cols[4], draws, self.device, self._stream, ring)
+
+
+def get_synthetic_data_loader(file_list_a, file_list_b, mask_list, sem_list_a, sem_list_b, batch_size, train,
+                              new_size=256, height=256, width=256, num_workers=4, crop=True, **kw):
+    """Synthetic paired loader (scripts/utils.py:583-635, MyDatasetSynthetic utils.py:458-580): yields
+    (x_as, x_bs, mask_s, sem_a, sem_b), what gen_update(..., synth=True, semantic_gt_a, semantic_gt_b) consumes.  Each of
+    the five lists holds one record per line, element 0 the path.  `crop` is accepted and ignored, as in the reference:
+    its dataset always crops.  Keyword extras: device, seed, rank, world_size, prefetch."""
+    lists = [[rec[0] for rec in default_txt_reader(f)] for f in (file_list_a, file_list_b, mask_list, sem_list_a, sem_list_b)]
+    return SyntheticPairLoader(lists[0], lists[1], lists[2], lists[3], lists[4], batch_size, train, new_size, height,
+                               width, num_workers, **kw)
 
 
 class _WithEmptyMask:

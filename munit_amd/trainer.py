@@ -19,7 +19,7 @@ The semantic-consistency loss (semantic_w > 0 with a semantic_ckpt_path) runs th
 the device (munit_amd/segmentation.py).  The synthetic-pair iteration of scripts/train.py:229-260 --
 gen_update(..., synth=True, semantic_gt_a, semantic_gt_b) -- adds the pair reconstruction loss (recon_synth_w) and takes
 the semantic loss against the simulator's label maps, the 19 logits merged into 10 classes inside the head kernel; the
-caller hands the pairs, masks and label maps in as tensors (the synthetic data loader is not part of this package).
+pairs, masks and label maps come in as tensors, as munit_amd.data.get_synthetic_data_loader yields them.
 
 Feature-level domain adaptation (adaptation.dfeat_lambda > 0, trainer.py:161-179): two domainClassifier(256) networks on the
 content codes, trained by domain_classifier_sr_update (training-mode BatchNorm2d, max-pool and 16x16 average are HIP kernels

@@ -101,3 +101,13 @@ def load_segmentation_model(ckpt_path, classes):
     """utils.py:974-983 under the reference's name (munit_amd/segmentation.py)."""
     from .segmentation import load_segmentation_model as load
     return load(ckpt_path, classes)
+
+
+def mapping(im):
+    """Simulator label colours -> class indices, in place on a tensor (utils.py:1356-1366): every element equal to a key
+    of munit_amd.data.LABEL_CLASSES becomes its class, in the reference's order; every other value is left alone.
+    Returns `im`.  (The synthetic loader applies the same table on the device, csrc/image.hip.)"""
+    from .data import LABEL_CLASSES
+    for grey, cls in LABEL_CLASSES.items():
+        im[im == grey] = cls
+    return im
