@@ -12,6 +12,11 @@ data_list_train_b_seg_synth, seg_list_a, seg_list_b; scripts/train.py:104-117) w
 restarted when it runs out.  Called from Python, main() also takes `synth_pairs`, an iterator of
 (x_as, x_bs, mask_s, sem_a, sem_b) batches, which then takes precedence (sem_a / sem_b may be None, the reference's
 `synthetic_seg_gt: 0`).  Without the lists and without `synth_pairs` no synthetic iteration runs.
+
+Output-level adaptation (adaptation.output_classifier_lambda and output_adv_lambda): every `output_classif_freq` iterations
+output_domain_classifier_sr_update runs on (x_a, x_as, x_b, x_bs), scripts/train.py:209-223, with the synthetic batch of
+that iteration (the one its synthetic-pair step uses too, when both fall on the same iteration).  A trainer that owns these
+classifiers cannot train without synthetic images: without the lists (or `synth_pairs`) the loop stops at start-up.
 """
 import argparse
 import os
@@ -98,6 +103,11 @@ def main(argv=None, synth_pairs=None):
         if lists is not None:
             synth_pairs = restarting(D.get_synthetic_data_loader(*lists, b, True, ns, h, w, nw, seed=3))
 
+    if trainer.use_output_classifier_sr and synth_pairs is None:
+        raise SystemExit("adaptation.output_classifier_lambda / output_adv_lambda train the output classifiers on synthetic "
+                         "images: give the synthetic lists (%s, or the config keys %s)"
+                         % (", ".join("--" + a.replace("_", "-") for a, _ in SYNTH_LISTS), ", ".join(k for _, k in SYNTH_LISTS)))
+
     if args.output and local_rank == 0:
         os.makedirs(args.output, exist_ok=True)   # the reference's prepare_sub_folder (utils.py:817-834)
     it, t0 = 0, time.perf_counter()
@@ -115,9 +125,13 @@ def main(argv=None, synth_pairs=None):
             cls_due = trainer.use_classifier_sr and (it + 1) % config["adaptation"]["classif_frequency"] == 0
             if cls_due:                                                 # scripts/train.py:193-207: real codes, target 1
                 trainer.domain_classifier_sr_update(x_a, x_b, False, config["adaptation"]["dfeat_lambda"], it + 1)
+            pair = None
+            if trainer.use_output_classifier_sr and (it + 1) % config["adaptation"]["output_classif_freq"] == 0:
+                pair = next(synth_pairs)                                # scripts/train.py:209-223: real a, synthetic a, real b, synthetic b
+                trainer.output_domain_classifier_sr_update(x_a, pair[0], x_b, pair[1], config, it + 1)
             freq = int(config.get("synthetic_frequency", 0))
             if synth_pairs is not None and freq > 0 and it % freq == 0:  # scripts/train.py:229-260
-                x_as, x_bs, mask_s, sem_a, sem_b = next(synth_pairs)
+                x_as, x_bs, mask_s, sem_a, sem_b = pair if pair is not None else next(synth_pairs)
                 if config.get("synthetic_seg_gt", 0) == 0:
                     sem_a = sem_b = None
                 trainer.dis_update(x_as, x_bs, config)

@@ -283,6 +283,17 @@ int munit_mse_const_fwd(const float* x, float target, size_t n, float* out, void
                         munit_stream_t stream);
 int munit_mse_const_bwd(const float* x, float target, size_t n, const float* gout, float* dx,
                         munit_stream_t stream);
+/* Multi-scale LSGAN loss in one launch pair (networks.py:117-162): nseg segments (1..8) of n[s] > 0 floats at x[s], each
+ * with its own target; x, n, target (and dx) are HOST arrays, handed to the kernels by value.  A segment may start at any
+ * 4-byte boundary (the second half of a batched output).  out[0] = sum_s mean((x_s - target_s)^2), the mean scaled in
+ * double and the segments added in index order; seg_out (nullable, nseg floats) gets each segment's mean.  No atomics:
+ * two calls on the same data are bitwise equal.  ws: munit_lsgan_workspace_bytes(nseg).  bwd writes every dx[s] in full:
+ * dx_s[i] = 2 * gout[0] / n_s * (x_s[i] - target_s).  Bad arguments return MUNIT_ERR_ARG before any launch. */
+size_t munit_lsgan_workspace_bytes(int nseg);
+int munit_lsgan_fwd(const float* const* x, const size_t* n, const float* target, int nseg, float* out, float* seg_out,
+                    void* ws, size_t ws_bytes, munit_stream_t stream);
+int munit_lsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
+                    float* const* dx, munit_stream_t stream);
 /* out = sum_i w[i] * *(terms[i]); n <= 32; terms are device scalars, w host floats. */
 int munit_weighted_sum(const float* const* terms, const float* w, int n, float* out,
                        munit_stream_t stream);

@@ -220,6 +220,70 @@ __global__ void mse_bwd_kernel(const float* __restrict__ x, float target, long l
     dx[i] = g * (x[i] - target);
 }
 
+// Multi-scale LSGAN loss (networks.py:117-162 and its callers): sum over segments s of mean((x_s - target_s)^2) in one launch
+// pair.  A segment is any run of floats -- a whole discriminator output or one half of a batched [sim; real] output, which may
+// start at any 4-byte boundary: every access below is a scalar one.  Segment s owns the blocks [start[s], start[s + 1]).
+constexpr int LSGAN_MAX_SEG = 8;
+struct LsganArgs {
+  const float* x[LSGAN_MAX_SEG];
+  float* dx[LSGAN_MAX_SEG];
+  unsigned long long n[LSGAN_MAX_SEG];
+  float target[LSGAN_MAX_SEG];
+  int start[LSGAN_MAX_SEG + 1];
+  int nseg;
+};
+
+__device__ inline int lsgan_segment(const LsganArgs& a, int block) {
+  int s = 0;
+  while (s + 1 < a.nseg && block >= a.start[s + 1]) ++s;
+  return s;
+}
+
+__global__ __launch_bounds__(NT) void lsgan_partial_kernel(LsganArgs a, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const int s = lsgan_segment(a, blockIdx.x);
+  const float* __restrict__ x = a.x[s];
+  const float target = a.target[s];
+  const unsigned long long n = a.n[s];
+  const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
+  float acc = 0.f;
+  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride) {
+    const float d = x[i] - target;
+    acc += d * d;
+  }
+  acc = block_sum256(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+// one block: every segment's partials in a fixed order, the mean in double, the segments added in index order
+__global__ __launch_bounds__(NT) void lsgan_finish_kernel(LsganArgs a, const float* __restrict__ partial,
+                                                          float* __restrict__ out, float* __restrict__ seg_out) {
+  __shared__ float red[4];
+  double total = 0.0;
+  for (int s = 0; s < a.nseg; ++s) {
+    float acc = 0.f;
+    for (int i = a.start[s] + threadIdx.x; i < a.start[s + 1]; i += NT) acc += partial[i];
+    acc = block_sum256(acc, red);
+    __syncthreads();  // red is written again by the next segment
+    const double mean = (double)acc * (1.0 / (double)a.n[s]);
+    if (threadIdx.x == 0 && seg_out != nullptr) seg_out[s] = (float)mean;
+    total += mean;
+  }
+  if (threadIdx.x == 0) out[0] = (float)total;
+}
+
+__global__ __launch_bounds__(NT) void lsgan_bwd_kernel(LsganArgs a, const float* __restrict__ gout) {
+  const int s = lsgan_segment(a, blockIdx.x);
+  const float* __restrict__ x = a.x[s];
+  float* __restrict__ dx = a.dx[s];
+  const float target = a.target[s];
+  const unsigned long long n = a.n[s];
+  const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
+  const float g = 2.f * gout[0] / (float)n;
+  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride)
+    dx[i] = g * (x[i] - target);
+}
+
 struct WsumArgs {
   const float* t[32];
   float w[32];
@@ -452,6 +516,56 @@ extern "C" int munit_mse_const_bwd(const float* x, float target, size_t n, const
   hipLaunchKernelGGL(mse_bwd_kernel, dim3(grid_for((long long)n, 4)), dim3(NT), 0, (hipStream_t)stream, x, target,
                      (long long)n, gout, dx);
   MUNIT_CHECK_LAUNCH("mse_bwd");
+  return MUNIT_OK;
+}
+
+namespace {
+// Blocks of segment s: one per 256 elements, at most an equal share of LOSS_PARTS (so the grid never exceeds LOSS_PARTS).
+int lsgan_fill(LsganArgs& a, const float* const* x, const size_t* n, const float* target, int nseg, float* const* dx) {
+  a.nseg = nseg;
+  a.start[0] = 0;
+  const long long cap = LOSS_PARTS / nseg;
+  for (int s = 0; s < nseg; ++s) {
+    a.x[s] = x[s];
+    a.dx[s] = dx ? dx[s] : nullptr;
+    a.n[s] = (unsigned long long)n[s];
+    a.target[s] = target[s];
+    const long long blocks = (long long)((n[s] + NT - 1) / NT);
+    a.start[s + 1] = a.start[s] + (int)std::min<long long>(cap, blocks);
+  }
+  return a.start[nseg];
+}
+}  // namespace
+
+extern "C" size_t munit_lsgan_workspace_bytes(int nseg) {
+  return (nseg >= 1 && nseg <= LSGAN_MAX_SEG) ? LOSS_PARTS * sizeof(float) : 0;
+}
+
+extern "C" int munit_lsgan_fwd(const float* const* x, const size_t* n, const float* target, int nseg, float* out,
+                               float* seg_out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x && n && target && out && ws, "lsgan_fwd: null pointer");
+  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "lsgan_fwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
+  for (int s = 0; s < nseg; ++s) MUNIT_CHECK_ARG(x[s] && n[s] > 0, "lsgan_fwd: segment %d is null or empty", s);
+  MUNIT_CHECK_ARG(ws_bytes >= munit_lsgan_workspace_bytes(nseg), "lsgan_fwd: workspace too small");
+  LsganArgs a{};
+  const int blocks = lsgan_fill(a, x, n, target, nseg, nullptr);
+  float* partial = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(lsgan_partial_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, partial);
+  MUNIT_CHECK_LAUNCH("lsgan_partial");
+  hipLaunchKernelGGL(lsgan_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, partial, out, seg_out);
+  MUNIT_CHECK_LAUNCH("lsgan_finish");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_lsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
+                               float* const* dx, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x && n && target && gout && dx, "lsgan_bwd: null pointer");
+  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "lsgan_bwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
+  for (int s = 0; s < nseg; ++s) MUNIT_CHECK_ARG(x[s] && dx[s] && n[s] > 0, "lsgan_bwd: segment %d is null or empty", s);
+  LsganArgs a{};
+  const int blocks = lsgan_fill(a, x, n, target, nseg, dx);
+  hipLaunchKernelGGL(lsgan_bwd_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, gout);
+  MUNIT_CHECK_LAUNCH("lsgan_bwd");
   return MUNIT_OK;
 }
 

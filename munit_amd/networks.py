@@ -600,6 +600,37 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
         return ops.scalar_sum([ops.mse_const(out0, 1.0) for out0 in outs0])
 
+    @staticmethod
+    def _lsgan(outs, targets):
+        """ops.lsgan_loss over all scales in one launch pair (in groups of 8 segments when there are more scales than that)"""
+        per = 2 if isinstance(targets[0], tuple) else 1
+        step = max(1, 8 // per)
+        if len(outs) <= step:
+            return ops.lsgan_loss(outs, targets)
+        return ops.scalar_sum([ops.lsgan_loss(outs[i:i + step], targets[i:i + step]) for i in range(0, len(outs), step)])
+
+    def calc_dis_loss_sr(self, input_sim, input_real):
+        """networks.py:117-139 (LSGAN): simulated -> 0, real -> 1, summed over the scales.  One pass over [sim; real] under
+        calc_dis_loss's condition; the loss of all scales and both halves is one kernel pair (ops.lsgan_loss)."""
+        assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
+        if BATCH_DIS_PAIR and input_sim.shape == input_real.shape and input_sim.dtype == input_real.dtype:
+            nb = input_sim.shape[0]
+            n0 = len(ops.MASK_SINK) if ops.MASK_SINK is not None else 0
+            outs = self.forward(torch.cat([ops.nhwc(input_sim), ops.nhwc(input_real)], 0))
+            if ops.MASK_SINK is not None:   # parity harness: the reference's order (the simulated pass, then the real pass)
+                rec = ops.MASK_SINK[n0:]
+                ops.MASK_SINK[n0:] = [m[:nb] for m in rec] + [m[nb:] for m in rec]
+            return self._lsgan(outs, [(0.0, 1.0)] * len(outs))
+        outs0 = self.forward(input_sim)
+        outs1 = self.forward(input_real)
+        return self._lsgan(outs0 + outs1, [0.0] * len(outs0) + [1.0] * len(outs1))
+
+    def calc_gen_loss_sr(self, input_fake):
+        """networks.py:141-162 (LSGAN; the reference's nsgan branch there names an undefined variable): target 0.5."""
+        outs0 = self.forward(input_fake)
+        assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
+        return self._lsgan(outs0, [0.5] * len(outs0))
+
 
 # --------------------------------------------------------------------------------------
 # feature classifier (adaptation.adv_lambda / dfeat_lambda)

@@ -870,6 +870,80 @@ def mse_const(x, target):
     return _MseConst.apply(x, float(target))
 
 
+def _lsgan_segments(xs, targets):
+    """(pointer, elements, target) of every segment: a number targets the whole tensor, a pair its two batch halves"""
+    segs = []
+    for x, t in zip(xs, targets):
+        if isinstance(t, (tuple, list)):
+            half = x.numel() // 2
+            segs += [(x.data_ptr(), half, float(t[0])), (x.data_ptr() + 4 * half, half, float(t[1]))]
+        else:
+            segs.append((x.data_ptr(), x.numel(), float(t)))
+    return segs
+
+
+def _lsgan_arrays(segs):
+    n = len(segs)
+    return ((c_void_p * n)(*[p for p, _, _ in segs]), (ctypes.c_size_t * n)(*[m for _, m, _ in segs]),
+            (c_float * n)(*[t for _, _, t in segs]))
+
+
+class _LsganLoss(Function):
+    """sum over the tensors (and, for a pair target, over the two batch halves of a tensor) of mean((x - target)^2): one
+    munit_lsgan_fwd, one munit_lsgan_bwd that writes every tensor's gradient whole.  No view of a tensor enters the tape."""
+
+    @staticmethod
+    def forward(ctx, targets, *xs):
+        lib = _lib.load()
+        if len(xs) == 0 or len(xs) != len(targets):
+            raise RuntimeError("munit_amd.lsgan_loss: one target per tensor expected (%d tensors, %d targets)"
+                               % (len(xs), len(targets)))
+        for i, (x, t) in enumerate(zip(xs, targets)):
+            _require(x, "lsgan_loss input %d" % i)
+            if x.numel() == 0:
+                raise RuntimeError("munit_amd.lsgan_loss: input %d is empty" % i)
+            if isinstance(t, (tuple, list)):
+                if len(t) != 2:
+                    raise RuntimeError("munit_amd.lsgan_loss: a pair target holds two numbers, got %r" % (t,))
+                if x.dim() == 0 or x.shape[0] % 2:
+                    raise RuntimeError("munit_amd.lsgan_loss: a pair target splits the batch in two halves; input %d has "
+                                       "batch %s" % (i, x.shape[0] if x.dim() else "()"))
+        nseg = sum(2 if isinstance(t, (tuple, list)) else 1 for t in targets)
+        if nseg > 8:
+            raise RuntimeError("munit_amd.lsgan_loss: at most 8 segments per call, got %d" % nseg)
+        _same_device(*xs)
+        xs = tuple(nhwc(x) if x.dim() == 4 else x.contiguous() for x in xs)
+        segs = _lsgan_segments(xs, targets)
+        out = torch.empty((), device=xs[0].device, dtype=torch.float32)
+        px, pn, pt = _lsgan_arrays(segs)
+        with _on(out):
+            ws = workspace(lib.munit_lsgan_workspace_bytes(len(segs)), out.device)
+            _lib.check(lib.munit_lsgan_fwd(px, pn, pt, len(segs), _p(out), None, _p(ws), ws.numel(), _stream()), "lsgan_fwd")
+        ctx.targets = targets
+        ctx.save_for_backward(*xs)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        xs = ctx.saved_tensors
+        gout = gout.contiguous()
+        dxs = tuple(torch.empty_like(x) for x in xs)
+        segs = _lsgan_segments(xs, ctx.targets)
+        px, pn, pt = _lsgan_arrays(segs)
+        pd = (c_void_p * len(segs))(*[p for p, _, _ in _lsgan_segments(dxs, ctx.targets)])
+        with _on(gout):
+            _lib.check(lib.munit_lsgan_bwd(px, pn, pt, len(segs), _p(gout), pd, _stream()), "lsgan_bwd")
+        return (None,) + dxs
+
+
+def lsgan_loss(outs, targets):
+    """Multi-scale LSGAN loss (networks.py:117-162): sum_i mean((outs[i] - targets[i])^2) over whole discriminator outputs.
+    targets[i]: one number, or a pair (t_first, t_second) that splits outs[i] at half its batch (the [sim; real] output of
+    a batched pass; NHWC, so both halves are contiguous).  At most 8 segments (a pair counts twice) per call."""
+    return _LsganLoss.apply(tuple(tuple(t) if isinstance(t, (tuple, list)) else float(t) for t in targets), *outs)
+
+
 class _ScalarSum(Function):
     """sum of device scalars with unit weights; backward hands the upstream gradient to every
     term unchanged (no kernel)."""

@@ -26,8 +26,19 @@ content codes, trained by domain_classifier_sr_update (training-mode BatchNorm2d
 of their own, dann.hip) under their own optimizer classif_opt_sr; adaptation.adv_lambda > 0 adds the fooling term
 (target 0.5) to gen_update, whose backward forms the gradient of the two content codes only -- the classifiers' weight
 gradients, which the reference computes and zeroes unused (trainer.py:1241), are skipped.  fp32 and one device only; like
-the reference, save / resume do not carry the classifiers.  The other aux losses (VGG, the a/b domain classifier of
-domain_adv_w, sem_seg_lambda, the output classifiers) raise NotImplementedError when their weight is non-zero.
+the reference, save / resume do not carry the classifiers.
+
+Output-level domain adaptation (adaptation.output_classifier_lambda > 0 and adaptation.output_adv_lambda > 0,
+trainer.py:181-201): two more MsImageDis, output_classifier_sr_a / _b, on the images themselves, trained by
+output_domain_classifier_sr_update (simulated -> 0, real -> 1) under their own optimizer output_classif_opt_sr, which takes
+the plain step() as the reference's update does; gen_update adds calc_gen_loss_sr (target 0.5) of the two translations
+with weight output_adv_lambda, forming no classifier weight gradient (the next update's zero_grad would discard it).  The
+multi-scale loss of a discriminator pass is one kernel pair (ops.lsgan_loss).  Either weight without the other is refused;
+fp32, one device, Adam only.  As in the reference, update_learning_rate does not step output_scheduler_sr and save / resume
+do not carry these classifiers either.
+
+The other aux losses (VGG, the a/b domain classifier of domain_adv_w, sem_seg_lambda) raise NotImplementedError when their
+weight is non-zero.
 """
 import os
 import warnings
@@ -476,6 +487,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.use_output_classifier_sr = hyperparameters["adaptation"]["output_classifier_lambda"] > 0
         self._check_aux(hyperparameters)
         self._check_featda(hyperparameters, self.use_classifier_sr)
+        self._check_outda(hyperparameters, self.use_output_classifier_sr)
 
         if self.gen_state == 0:
             self.gen_a = AdaINGen(hyperparameters["input_dim_a"], hyperparameters["gen"])
@@ -537,6 +549,18 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self.domain_classifier_sr_b.apply(weights_init("gaussian"))
             self.classif_sr_scheduler = get_scheduler(self.classif_opt_sr, hyperparameters)
 
+        # output classifiers of the simulated / real adaptation (trainer.py:181-201): both on input_dim_a, one optimizer over
+        # both, a scheduler that update_learning_rate never steps, nothing of them in save / resume
+        if self.use_output_classifier_sr:
+            self.output_classifier_sr_a = MsImageDis(hyperparameters["input_dim_a"], hyperparameters["dis"])
+            self.output_classifier_sr_b = MsImageDis(hyperparameters["input_dim_a"], hyperparameters["dis"])
+            dann_params = list(self.output_classifier_sr_a.parameters()) + list(self.output_classifier_sr_b.parameters())
+            self.output_classif_opt_sr = optimizer([p for p in dann_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
+                                                   weight_decay=hyperparameters["weight_decay"])
+            self.output_classifier_sr_a.apply(weights_init("gaussian"))
+            self.output_classifier_sr_b.apply(weights_init("gaussian"))
+            self.output_scheduler_sr = get_scheduler(self.output_classif_opt_sr, hyperparameters)
+
         self._consts = {}
         # deferred discriminator exchange + step (data parallel, _defer_dis_step)
         self._dis_pending, self._dis_event, self._dis_waited = None, None, set()
@@ -547,7 +571,9 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
 
     # ------------------------------------------------------------------------------------
     @staticmethod
-    def _check_aux(hp):
+    def _check_aux(hp, construct=True):
+        """construct False (gen_update): the both-weights rule of the output classifiers is a rule of construction -- a
+        trainer that owns them may be handed output_adv_lambda 0 for a step."""
         bad = []
         if hp.get("vgg_w", 0) > 0:
             bad.append("vgg_w")
@@ -555,9 +581,16 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             bad.append("semantic_w (without a semantic_ckpt_path)")
         if hp.get("domain_adv_w", 0) > 0:
             bad.append("domain_adv_w")
-        for k in ("sem_seg_lambda", "output_classifier_lambda", "output_adv_lambda"):
-            if hp["adaptation"].get(k, 0) > 0:
-                bad.append("adaptation." + k)
+        if hp["adaptation"].get("sem_seg_lambda", 0) > 0:
+            bad.append("adaptation.sem_seg_lambda")
+        ocl = hp["adaptation"].get("output_classifier_lambda", 0) > 0
+        oadv = hp["adaptation"].get("output_adv_lambda", 0) > 0
+        if construct and oadv and not ocl:
+            bad.append("adaptation.output_adv_lambda (without adaptation.output_classifier_lambda there are no classifiers "
+                       "to fool: set both)")
+        if construct and ocl and not oadv:
+            bad.append("adaptation.output_classifier_lambda (without adaptation.output_adv_lambda it trains classifiers that "
+                       "nothing reads: set both)")
         if bad:
             raise NotImplementedError(
                 "munit_amd covers the AdaINGen + MsImageDis training step only; set these weights to 0 "
@@ -587,6 +620,29 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         except ValueError as e:
             raise ValueError("munit_amd: adaptation.dfeat_lambda / adaptation.adv_lambda cannot run at crop %dx%d with "
                              "gen.n_downsample %d: %s" % (hp["crop_image_height"], hp["crop_image_width"], n, e)) from None
+
+    @staticmethod
+    def _check_outda(hp, built, update=False):
+        """Refusals of adaptation.output_adv_lambda / adaptation.output_classifier_lambda, before any device work.  built:
+        whether this trainer was constructed with both weights (it then owns the classifiers); update: the check of
+        output_domain_classifier_sr_update, which runs whatever the weights of `hp` are."""
+        adv = hp["adaptation"].get("output_adv_lambda", 0) > 0
+        if (adv or update) and not built:
+            raise ValueError("munit_amd: adaptation.output_adv_lambda > 0 needs a trainer constructed with "
+                             "adaptation.output_classifier_lambda > 0 and adaptation.output_adv_lambda > 0 (the classifiers "
+                             "the generator is to fool are built and trained under those)")
+        if not (adv or update or built):
+            return
+        keys = "adaptation.output_adv_lambda / adaptation.output_classifier_lambda"
+        if hp.get("precision", "f32") != "f32":
+            raise NotImplementedError("munit_amd: %s run in fp32 only (precision %r)" % (keys, hp["precision"]))
+        if dp_size() > 1:
+            raise NotImplementedError("munit_amd: %s are not implemented for data-parallel training (world size %d): the "
+                                      "classifiers' gradients are not exchanged" % (keys, dp_size()))
+        if "extra" in hp.get("optimizer", "adam"):
+            raise NotImplementedError("munit_amd: %s are not implemented for optimizer %r: the reference's update calls "
+                                      "step() without extrapolation(), on which its ExtraAdam raises"
+                                      % (keys, hp["optimizer"]))
 
     @staticmethod
     def _check_semantic(hp):
@@ -659,6 +715,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.gen_opt.bind(device)
         if self.use_classifier_sr:
             self.classif_opt_sr.bind(device)
+        if self.use_output_classifier_sr:
+            self.output_classif_opt_sr.bind(device)
         self._consts = {}
         # flat-gradient ranges of the decoders and MLPs (final before the first encodes' backward: GradExchange)
         gens = [self.gen] if self.gen_state == 1 else [self.gen_a, self.gen_b]
@@ -705,6 +763,13 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self.classif_opt_sr.extrapolation()
         else:
             self.classif_opt_sr.step()
+
+    def output_classif_opt_sr_step(self):
+        """trainer.py:234-241.  Exists as in the reference, whose update does not call it either."""
+        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
+            self.output_classif_opt_sr.extrapolation()
+        else:
+            self.output_classif_opt_sr.step()
 
     # ---- criteria (trainer.py:279-305) ------------------------------------------------
     def recon_criterion(self, input, target):
@@ -758,6 +823,31 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.classif_opt_sr_step()
         if comet_exp is not None and self.iterations % 100 == 0:
             comet_exp.log_metric("loss_classifier_sr", (lambda_classifier * self.loss_classifier_sr_update).cpu(), step=step)
+
+    # ---- simulated / real output classifiers (trainer.py:1267-1284) ----------------------
+    def output_domain_classifier_sr_update(self, x_ar, x_as, x_br, x_bs, hyperparameters, step, comet_exp=None):
+        """trainer.py:1267-1284: cls_b.calc_dis_loss_sr(x_bs, x_br) + cls_a.calc_dis_loss_sr(x_as, x_ar), times
+        output_classifier_lambda, then the optimizer's plain step() (never extrapolation(), as in the reference).
+        update_learning_rate, save and resume are unchanged by these classifiers, as in the reference."""
+        ops.set_compute(self.precision)
+        self._check_outda(self.hyperparameters, self.use_output_classifier_sr, update=True)
+        lam = hyperparameters["adaptation"]["output_classifier_lambda"]
+        self.output_classif_opt_sr.zero_grad()
+        dev = x_ar.device
+        x_ar, x_as, x_br, x_bs = ops.nhwc(x_ar), ops.nhwc(x_as), ops.nhwc(x_br), ops.nhwc(x_bs)
+        br = _Branches(dev)
+        br.adopt(x_ar, x_as, x_br, x_bs)
+        l_a = br.run(0, lambda: self.output_classifier_sr_a.calc_dis_loss_sr(x_as, x_ar))
+        l_b = br.run(1, lambda: self.output_classifier_sr_b.calc_dis_loss_sr(x_bs, x_br))
+        br.join(l_a, l_b)
+        loss = ops.scalar_sum([l_b, l_a])
+        self.loss_output_classifier_sr_update = loss.detach()      # unweighted; the reference logs lambda * loss
+        torch.autograd.backward([loss], [self._const(lam, dev)])
+        br.join()
+        ops.join_side_streams()
+        self.output_classif_opt_sr.step()
+        if comet_exp is not None and self.iterations % 100 == 0:
+            comet_exp.log_metric("loss_output_classifier_sr", (lam * self.loss_output_classifier_sr_update).cpu(), step=step)
 
     # ---- generator dispatch -----------------------------------------------------------
     def _enc(self, x, k):
@@ -825,9 +915,11 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         if gts is not None and x_a.device.type != "cuda":
             raise NotImplementedError("munit_amd: semantic_gt_a / semantic_gt_b run on the device only (there is no host "
                                       "path for any loss); move the trainer and the images to a HIP device")
-        self._check_aux(normalize_config(hp))
+        self._check_aux(normalize_config(hp), construct=False)
         self._check_featda(hp, self.use_classifier_sr)
+        self._check_outda(hp, self.use_output_classifier_sr)
         fool_sr = hp["adaptation"]["adv_lambda"] > 0
+        fool_out = hp["adaptation"]["output_adv_lambda"] > 0
         self.gen_opt.zero_grad()
         # the reference draws these even when guided == 1 leaves them unused (trainer.py:366-367)
         s_a = torch.randn(x_a.size(0), self.style_dim, 1, 1)
@@ -839,6 +931,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         world = dp_world()
         overlap = bool(world and OVERLAP_EXCHANGE)      # stages of the gradient exchange start inside backward (GradExchange)
         d_params = list(self.dis_a.parameters()) + list(self.dis_b.parameters())
+        if fool_out:        # ... and so would the output classifiers' (zeroed by the next update's zero_grad, trainer.py:1271)
+            d_params += list(self.output_classifier_sr_a.parameters()) + list(self.output_classifier_sr_b.parameters())
         for p in d_params:  # D weight gradients made here would be discarded (trainer.py:1145)
             p.requires_grad_(False)
         try:
@@ -891,6 +985,10 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             # that follow, measured 161.0-161.4 ms per step against 159.9-160.2 on the branch streams: not kept.)
             self.loss_gen_adv_a = br.run(0, lambda: self.dis_a.calc_gen_loss(x_ba))
             self.loss_gen_adv_b = br.run(1, lambda: self.dis_b.calc_gen_loss(x_ab))
+            osr_a = osr_b = None
+            if fool_out:   # the output classifiers' fooling term (trainer.py:527-532) on the same translations
+                osr_a = br.run(0, lambda: self.output_classifier_sr_a.calc_gen_loss_sr(x_ba))
+                osr_b = br.run(1, lambda: self.output_classifier_sr_b.calc_gen_loss_sr(x_ab))
             c_b_recon, s_a_recon = br.run(0, lambda: self._enc(x_ba, 1))
             c_a_recon, s_b_recon = br.run(1, lambda: self._enc(x_ab, 2))
             br.share(c_a_recon, c_b_recon)
@@ -919,8 +1017,9 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                 self.loss_gen_cycrecon_x_b = 0
             br.join(self.loss_gen_recon_x_a, self.loss_gen_recon_x_b, self.loss_gen_recon_s_a, self.loss_gen_recon_s_b,
                     self.loss_gen_recon_c_a, self.loss_gen_recon_c_b, self.loss_gen_cycrecon_x_a,
-                    self.loss_gen_cycrecon_x_b, self.loss_gen_adv_a, self.loss_gen_adv_b, sr_a, sr_b)
+                    self.loss_gen_cycrecon_x_b, self.loss_gen_adv_a, self.loss_gen_adv_b, sr_a, sr_b, osr_a, osr_b)
             self.loss_classifier_sr = ops.scalar_sum([sr_a, sr_b]) if fool_sr else 0
+            self.loss_output_classifier_sr = ops.scalar_sum([osr_a, osr_b]) if fool_out else 0
             if pair_term or self.semantic_w:
                 br.join(x_ab, x_ba)            # both translations on the caller's stream
             if pair_term:
@@ -934,7 +1033,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             for p in d_params:
                 p.requires_grad_(True)
         self.loss_gen_vgg_a = self.loss_gen_vgg_b = 0
-        self.domain_adv_loss = self.loss_output_classifier_sr = 0
+        self.domain_adv_loss = 0
 
         pairs = [(hp["gan_w"], self.loss_gen_adv_a), (hp["gan_w"], self.loss_gen_adv_b),
                  (hp["recon_x_w"], self.loss_gen_recon_x_a), (hp["recon_s_w"], self.loss_gen_recon_s_a),
@@ -949,6 +1048,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             pairs.append((hp["recon_synth_w"], self.loss_gen_recon_synth))
         if fool_sr:
             pairs.append((hp["adaptation"]["adv_lambda"], self.loss_classifier_sr))
+        if fool_out:
+            pairs.append((hp["adaptation"]["output_adv_lambda"], self.loss_output_classifier_sr))
         self.loss_gen_total = ops.weighted_sum([t.detach() for _, t in pairs], [w for w, _ in pairs])
         live = [(w, t) for w, t in pairs if w != 0 and t.requires_grad]
         xch = None
@@ -978,6 +1079,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                               "loss_gen_recon_c_b", "loss_gen_cycrecon_x_a", "loss_gen_cycrecon_x_b",
                               "loss_gen_total") + (("loss_sem_seg",) if self.semantic_w else ())
                   + (("loss_gen_recon_synth",) if synth else ()) + (("loss_classifier_sr",) if fool_sr else ()))
+        if fool_out and comet_exp is not None and self.iterations % 100 == 0:     # trainer.py:612-616
+            comet_exp.log_metric("loss_output_classifier_adv_sr", self.loss_output_classifier_sr.cpu().detach())
 
     # ---- dis_update (trainer.py:1133-1190) ---------------------------------------------
     def dis_update(self, x_a, x_b, hyperparameters, comet_exp=None):
