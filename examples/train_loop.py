@@ -57,6 +57,42 @@ def restarting(loader):
             raise RuntimeError("the synthetic loader yields no batch (fewer samples than one batch)")
 
 
+def run_iteration(trainer, config, it, real_batch, synth_pairs, on_call=None):
+    """Iteration `it` (counted from 0) in the order scripts/train.py:172-274 issues it: update_learning_rate, the real
+    dis_update, a gen_update when (it + 1) % ratio_disc_gen == 0, the classifier updates on their own cadences of it + 1,
+    then -- when it % synthetic_frequency == 0 -- a synthetic dis_update, a gen_update(synth=True) that ratio_disc_gen does
+    not gate, and the synthetic feature-classifier update.  real_batch: (x_a, x_b, mask_a, mask_b); synth_pairs: an iterator
+    of (x_as, x_bs, mask_s, sem_a, sem_b) or None.  on_call(name, args, run): called in place of every update with the
+    trainer method's name, its positional arguments and `run`, which performs the call (tests wrap the calls with it)."""
+    def call(name, *args):
+        run = lambda: getattr(trainer, name)(*args)
+        return run() if on_call is None else on_call(name, args, run)
+
+    x_a, x_b, m_a, m_b = real_batch
+    ad = config["adaptation"]
+    trainer.iterations = it
+    trainer.update_learning_rate()
+    call("dis_update", x_a, x_b, config)                                # scripts/train.py:182
+    if (it + 1) % int(config.get("ratio_disc_gen", 1)) == 0:
+        call("gen_update", x_a, x_b, config, m_a, m_b)                  # scripts/train.py:185-187
+    cls_due = trainer.use_classifier_sr and (it + 1) % ad["classif_frequency"] == 0
+    if cls_due:                                                         # scripts/train.py:193-207: real codes, target 1
+        call("domain_classifier_sr_update", x_a, x_b, False, ad["dfeat_lambda"], it + 1)
+    pair = None
+    if trainer.use_output_classifier_sr and (it + 1) % ad["output_classif_freq"] == 0:
+        pair = next(synth_pairs)                                        # scripts/train.py:209-223: real a, synthetic a, real b, synthetic b
+        call("output_domain_classifier_sr_update", x_a, pair[0], x_b, pair[1], config, it + 1)
+    freq = int(config.get("synthetic_frequency", 0))
+    if synth_pairs is not None and freq > 0 and it % freq == 0:         # scripts/train.py:229-260
+        x_as, x_bs, mask_s, sem_a, sem_b = pair if pair is not None else next(synth_pairs)
+        if config.get("synthetic_seg_gt", 0) == 0:
+            sem_a = sem_b = None
+        call("dis_update", x_as, x_bs, config)
+        call("gen_update", x_as, x_bs, config, mask_s, mask_s, None, True, sem_a, sem_b)
+        if cls_due:                                                     # scripts/train.py:261-274: synthetic codes, target 0
+            call("domain_classifier_sr_update", x_as, x_bs, True, ad["dfeat_lambda"], it + 1)
+
+
 def main(argv=None, synth_pairs=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
@@ -111,33 +147,12 @@ def main(argv=None, synth_pairs=None):
     if args.output and local_rank == 0:
         os.makedirs(args.output, exist_ok=True)   # the reference's prepare_sub_folder (utils.py:817-834)
     it, t0 = 0, time.perf_counter()
-    ratio = int(config.get("ratio_disc_gen", 1))
     while it < args.iters:
         for batch_a, batch_b in zip(loader_a, loader_b):
             (x_a, m_a), (x_b, m_b) = [(t if isinstance(t, tuple) else (t, None)) for t in (batch_a, batch_b)]
             if m_a is None and config.get("recon_mask", 0) == 1:      # no mask files: everything counts
                 m_a, m_b = torch.ones_like(x_a[:, :1]), torch.ones_like(x_b[:, :1])
-            trainer.iterations = it
-            trainer.update_learning_rate()
-            trainer.dis_update(x_a, x_b, config)                        # scripts/train.py:182
-            if (it + 1) % ratio == 0:
-                trainer.gen_update(x_a, x_b, config, m_a, m_b)          # scripts/train.py:185-187
-            cls_due = trainer.use_classifier_sr and (it + 1) % config["adaptation"]["classif_frequency"] == 0
-            if cls_due:                                                 # scripts/train.py:193-207: real codes, target 1
-                trainer.domain_classifier_sr_update(x_a, x_b, False, config["adaptation"]["dfeat_lambda"], it + 1)
-            pair = None
-            if trainer.use_output_classifier_sr and (it + 1) % config["adaptation"]["output_classif_freq"] == 0:
-                pair = next(synth_pairs)                                # scripts/train.py:209-223: real a, synthetic a, real b, synthetic b
-                trainer.output_domain_classifier_sr_update(x_a, pair[0], x_b, pair[1], config, it + 1)
-            freq = int(config.get("synthetic_frequency", 0))
-            if synth_pairs is not None and freq > 0 and it % freq == 0:  # scripts/train.py:229-260
-                x_as, x_bs, mask_s, sem_a, sem_b = pair if pair is not None else next(synth_pairs)
-                if config.get("synthetic_seg_gt", 0) == 0:
-                    sem_a = sem_b = None
-                trainer.dis_update(x_as, x_bs, config)
-                trainer.gen_update(x_as, x_bs, config, mask_s, mask_s, None, True, sem_a, sem_b)
-                if cls_due:                                             # scripts/train.py:261-274: synthetic codes, target 0
-                    trainer.domain_classifier_sr_update(x_as, x_bs, True, config["adaptation"]["dfeat_lambda"], it + 1)
+            run_iteration(trainer, config, it, (x_a, x_b, m_a, m_b), synth_pairs)
             it += 1
             if args.output and args.save_every and it % args.save_every == 0 and local_rank == 0:
                 trainer.save(args.output, it - 1)      # file names carry iterations + 1 (trainer.py:1337-1344)

@@ -1,7 +1,8 @@
 """fp64 torch-CPU restatement of the simulated / real feature classifier (scripts/utils.py:1277-1327, 1370-1392), its
 training-mode BatchNorm2d with the running statistics, the three targets of compute_classifier_sr_loss
 (scripts/trainer.py:638-667) and the two updates that use it (the fooling term of gen_update, trainer.py:521-525, and
-domain_classifier_sr_update, trainer.py:1237-1265).  The optimizer arithmetic is oracle.munit_oracle's.
+domain_classifier_sr_update, trainer.py:1237-1265), and the step oracle that adds the fooling term (oracle_trainer_class).
+The optimizer arithmetic is oracle.munit_oracle's.
 
 A classifier is a dict of tensors under the reference's state_dict keys.  `pins` (optional): what ops.DANN_SINK recorded
 from a HIP run of the same classifier call -- per call the first max-pool's winners, the ReLU sign pattern behind bn1 and
@@ -207,6 +208,36 @@ def fool_term(sd_a, sd_b, c_a, c_b, pins=None):
     loss = sr_loss(sd_a, sd_b, c_a, c_b, fool=True, pins=pins)
     g_a, g_b = torch.autograd.grad(loss, [c_a, c_b])
     return loss.detach(), g_a, g_b
+
+
+def trainer_pins(sink):
+    """ops.DANN_SINK of one trainer call.  The two classifiers run on two streams but are issued a-first by the host: the
+    first six records are a's."""
+    shapes = [tuple(t.shape) for t in sink]
+    assert len(sink) == 2 * PINS_PER_CALL and shapes[:PINS_PER_CALL] == shapes[PINS_PER_CALL:]
+    return Pins(sink)
+
+
+def oracle_trainer_class(shared, base=None):
+    """An OracleTrainer (or `base`, a subclass of it) whose gen_losses adds, after the base terms, adv_lambda *
+    compute_classifier_sr_loss(c_a, c_b, fool=True) on ITS OWN content codes, with the classifiers as the HIP trainer held
+    them when its gen_update began (`shared["sd"]`) and the max-pool winners / ReLU signs its gen_update recorded
+    (`shared["sink"]`) pinned."""
+    class FeatdaOracleTrainer(base or O.OracleTrainer):
+        def gen_losses(self, x_a, x_b, mask_a=None, mask_b=None, s_a=None, s_b=None):
+            L = super().gen_losses(x_a, x_b, mask_a, mask_b, s_a, s_b)
+            lam = self.hp["adaptation"]["adv_lambda"]
+            sd_a, sd_b = shared["sd"]
+            pins = None if shared.get("sink") is None else trainer_pins(shared["sink"])      # None: unpinned
+            L["loss_classifier_sr"] = sr_loss(sd_a, sd_b, self._last["c_a"], self._last["c_b"], fool=True, pins=pins)
+            if pins is not None:
+                assert pins.done()
+                shared["worst"] = max(shared.get("worst", 0.0), pins.worst)
+            L["loss_gen_total"] = L["loss_gen_total"] + lam * L["loss_classifier_sr"]
+            shared["after"] = (sd_a, sd_b)
+            return L
+
+    return FeatdaOracleTrainer
 
 
 def load_into(module, sd):

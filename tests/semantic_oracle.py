@@ -190,36 +190,45 @@ def audit(kinks, pins, rel=1e-5):
     return bad
 
 
-def oracle_trainer_class(seg_model, sink):
-    """An OracleTrainer whose gen_losses adds the semantic term (trainer.py:504-509, 552) on its own translations
-    self._last["x_ab"] / ["x_ba"].  `sink`: a callable returning ops.SEG_SINK as the HIP gen_update left it (label pass
-    kinks, labels, logits pass kinks); the oracle takes the device's labels and kink branches and audits them
-    (`audit` allows a disagreement only at rounding-noise margins; labels only where the top-2 gap is that small)."""
+def oracle_trainer_class(seg_model, sink, base=None):
+    """An OracleTrainer (or `base`, a subclass of it) whose gen_losses adds the semantic term (trainer.py:504-509, 552) on
+    its own translations self._last["x_ab"] / ["x_ba"].  `sink`: a callable returning ops.SEG_SINK as the HIP gen_update
+    left it (label pass kinks, labels, logits pass kinks); the oracle takes the device's labels and kink branches and audits
+    them (`audit` allows a disagreement only at rounding-noise margins; labels only where the top-2 gap is that small).
+    Stacked under tests/synth_oracle.py's class for a whole iteration: an instance whose `synth_call` is True (the call
+    being replayed is gen_update(synth=True) with a ground truth) leaves the term to that class."""
     from oracle import munit_oracle as O
     n_k = 2 + 2 * sum(n for n, _, _ in LAYERS)       # kinks recorded per network forward
 
-    class SemanticOracleTrainer(O.OracleTrainer):
+    class SemanticOracleTrainer(base or O.OracleTrainer):
         audit_bad = None
+        synth_call = None
 
         def gen_losses(self, x_a, x_b, mask_a=None, mask_b=None, s_a=None, s_b=None):
             L = super().gen_losses(x_a, x_b, mask_a, mask_b, s_a, s_b)
             hp = self.hp
-            if not hp.get("semantic_w", 0) > 0:
+            if not hp.get("semantic_w", 0) > 0 or self.synth_call is True:
                 return L
             sd = state(seg_model, x_a.dtype)
             rec = sink()
-            assert len(rec) == 2 * n_k + 1, len(rec)
-            pin_lab, labels, pin_log = seg_pins(rec[:n_k]), rec[n_k].cpu().long(), seg_pins(rec[n_k + 1:])
             b = x_a.shape[0]
-            kinks = []
-            with torch.no_grad():
-                up = logits(sd, torch.cat([x_a, x_b]), kinks=kinks, pins=pin_lab)
-            bad = audit(kinks, pin_lab)
-            top = up.topk(2, 1).values
-            bad += int(((up.argmax(1) != labels) & ((top[:, 0] - top[:, 1]) > 1e-5 * up.abs().max())).sum())
-            kinks = []
-            out = logits(sd, torch.cat([self._last["x_ab"], self._last["x_ba"]]), kinks=kinks, pins=pin_log)
-            bad += audit(kinks, pin_log)
+            if rec is None:                      # unpinned: the oracle's own labels and branches
+                with torch.no_grad():
+                    labels = logits(sd, torch.cat([x_a, x_b])).argmax(1)
+                out = logits(sd, torch.cat([self._last["x_ab"], self._last["x_ba"]]))
+                bad = 0
+            else:
+                assert len(rec) == 2 * n_k + 1, len(rec)
+                pin_lab, labels, pin_log = seg_pins(rec[:n_k]), rec[n_k].cpu().long(), seg_pins(rec[n_k + 1:])
+                kinks = []
+                with torch.no_grad():
+                    up = logits(sd, torch.cat([x_a, x_b]), kinks=kinks, pins=pin_lab)
+                bad = audit(kinks, pin_lab)
+                top = up.topk(2, 1).values
+                bad += int(((up.argmax(1) != labels) & ((top[:, 0] - top[:, 1]) > 1e-5 * up.abs().max())).sum())
+                kinks = []
+                out = logits(sd, torch.cat([self._last["x_ab"], self._last["x_ba"]]), kinks=kinks, pins=pin_log)
+                bad += audit(kinks, pin_log)
             type(self).audit_bad = bad
             masked = not hp["adaptation"]["full_adaptation"] and mask_a is not None
             L["loss_sem_seg"] = (ce_loss(out[:b], labels[:b], mask_a if masked else None)

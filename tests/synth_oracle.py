@@ -78,20 +78,25 @@ def gt_maps(b, size, seed, block=8):
     return lo.repeat_interleave(block, 1).repeat_interleave(block, 2)[:, :h, :w].double().contiguous()
 
 
-def oracle_trainer_class(seg_model, sink, gts):
-    """An OracleTrainer whose gen_losses adds, after the base terms, the pair reconstruction term (recon_synth_w, through
-    oracle.munit_oracle.l1_masked so that the step's last two pinned L1 sign patterns are consumed) and the semantic term
-    against the ground truth `gts` = (gt_a, gt_b) (semantic_w) on its own translations.  `sink`: a callable returning
-    ops.SEG_SINK as the HIP gen_update left it -- with a ground truth only the logits pass records; its kinks are pinned
-    and audited as tests/semantic_oracle.py does."""
+def oracle_trainer_class(seg_model, sink, gts, base=None):
+    """An OracleTrainer (or `base`, a subclass of it) whose gen_losses adds, after the base terms, the pair reconstruction
+    term (recon_synth_w, through oracle.munit_oracle.l1_masked so that the step's last two pinned L1 sign patterns are
+    consumed) and the semantic term against the ground truth `gts` = (gt_a, gt_b) (semantic_w) on its own translations.
+    `sink`: a callable returning ops.SEG_SINK as the HIP gen_update left it -- with a ground truth only the logits pass
+    records; its kinks are pinned and audited as tests/semantic_oracle.py does.
+    Stacked over tests/semantic_oracle.py's class for a whole iteration: an instance whose `synth_call` is False (the call
+    being replayed is the real gen_update) adds neither term and leaves the semantic one to that class."""
     from oracle import munit_oracle as O
     n_k = 2 + 2 * sum(n for n, _, _ in S.LAYERS)
 
-    class SynthOracleTrainer(O.OracleTrainer):
+    class SynthOracleTrainer(base or O.OracleTrainer):
         audit_bad = None
+        synth_call = None
 
         def gen_losses(self, x_a, x_b, mask_a=None, mask_b=None, s_a=None, s_b=None):
             L = super().gen_losses(x_a, x_b, mask_a, mask_b, s_a, s_b)
+            if self.synth_call is False:
+                return L
             hp = self.hp
             x_ab, x_ba = self._last["x_ab"], self._last["x_ba"]
             if hp.get("recon_synth_w", 0) > 0:
@@ -99,15 +104,19 @@ def oracle_trainer_class(seg_model, sink, gts):
                 L["loss_gen_total"] = L["loss_gen_total"] + hp["recon_synth_w"] * L["loss_gen_recon_synth"]
             rec = sink()
             if not hp.get("semantic_w", 0) > 0:
-                assert len(rec) == 0, len(rec)
+                assert not rec, len(rec)
                 type(self).audit_bad = 0
                 return L
-            assert len(rec) == n_k, len(rec)
             sd = S.state(seg_model, x_a.dtype)
-            pins = S.seg_pins(rec)
-            kinks = []
-            out = S.logits(sd, torch.cat([x_ab, x_ba]), kinks=kinks, pins=pins)
-            type(self).audit_bad = S.audit(kinks, pins)
+            if rec is None:                      # unpinned: the oracle's own branches
+                out = S.logits(sd, torch.cat([x_ab, x_ba]))
+                type(self).audit_bad = 0
+            else:
+                assert len(rec) == n_k, len(rec)
+                pins = S.seg_pins(rec)
+                kinks = []
+                out = S.logits(sd, torch.cat([x_ab, x_ba]), kinks=kinks, pins=pins)
+                type(self).audit_bad = S.audit(kinks, pins)
             b = x_a.shape[0]
             masked = not hp["adaptation"]["full_adaptation"] and mask_a is not None
             L["loss_sem_seg"] = (ce_gt_loss(out[:b], gts[0], mask_a if masked else None)

@@ -456,11 +456,7 @@ def _compare_classifiers(tr, sd_a, sd_b, what, lr, opt=None):
     return worst
 
 
-def _pins(sink):
-    """The two classifiers run on two streams but are issued a-first by the host: the first six records are a's."""
-    shapes = [tuple(t.shape) for t in sink]
-    assert len(sink) == 2 * D.PINS_PER_CALL and shapes[:D.PINS_PER_CALL] == shapes[D.PINS_PER_CALL:]
-    return D.Pins(sink)
+_pins = D.trainer_pins
 
 
 @pytest.mark.parametrize("optimizer", ["adam", "extraadam"])
@@ -521,26 +517,6 @@ def test_the_sequence_of_updates_against_the_oracle(optimizer):
         assert tr.classif_opt_sr._step == 2
 
 
-def _featda_oracle_trainer(shared):
-    """An OracleTrainer whose gen_losses adds, after the base terms, adv_lambda * compute_classifier_sr_loss(c_a, c_b,
-    fool=True) on ITS OWN content codes, with the classifiers as the HIP trainer held them when its gen_update began
-    (`shared["sd"]`) and the max-pool winners / ReLU signs its gen_update recorded (`shared["sink"]`) pinned."""
-    class FeatdaOracleTrainer(O.OracleTrainer):
-        def gen_losses(self, x_a, x_b, mask_a=None, mask_b=None, s_a=None, s_b=None):
-            L = super().gen_losses(x_a, x_b, mask_a, mask_b, s_a, s_b)
-            lam = self.hp["adaptation"]["adv_lambda"]
-            sd_a, sd_b = shared["sd"]
-            pins = _pins(shared["sink"])
-            L["loss_classifier_sr"] = D.sr_loss(sd_a, sd_b, self._last["c_a"], self._last["c_b"], fool=True, pins=pins)
-            assert pins.done()
-            shared["worst"] = max(shared.get("worst", 0.0), pins.worst)
-            L["loss_gen_total"] = L["loss_gen_total"] + lam * L["loss_classifier_sr"]
-            shared["after"] = (sd_a, sd_b)
-            return L
-
-    return FeatdaOracleTrainer
-
-
 def _step_parity(monkeypatch, iters, **over):
     """tests/parity.run_step_parity (every loss 1e-5 relative, every generator gradient 5e-5 normalised max and relative L2
     with the kinks pinned, Adam moments, the weight step) at crop 256, batch 2, n_res 1, num_scales 1 with adv_lambda: 6 /
@@ -550,7 +526,7 @@ def _step_parity(monkeypatch, iters, **over):
     from munit_amd.trainer import MUNIT_Trainer
     from tests.parity import run_step_parity
     shared = {"reused": [], "n": 0}
-    monkeypatch.setattr(O, "OracleTrainer", _featda_oracle_trainer(shared))
+    monkeypatch.setattr(O, "OracleTrainer", D.oracle_trainer_class(shared))
     plain = MUNIT_Trainer.gen_update
 
     def gen_update(self, xa, xb, hp, mask_a=None, mask_b=None):
