@@ -439,6 +439,36 @@ int munit_batchnorm_fwd(const float* x, float* y, float* mean, float* rstd, floa
 int munit_batchnorm_bwd(const float* x, const float* dy, const float* y, const float* gamma, const float* mean,
                         const float* rstd, float* dx, float* dgamma, float* dbeta, float acc, long long R, int C,
                         int relu, void* ws, size_t ws_bytes, munit_stream_t stream);
+/* Batch norm whose statistics span W data-parallel ranks of R_local rows each (equal on all ranks; N = W * R_local >= 2,
+ * refused by stats_local and the backward halves; W in 1..64): W ranks compute what one process computes on the joined batch.  Each pass has a
+ * local half, which writes the rank's partial results into row `rank` of an exchange buffer xch of W rows and ZEROES the
+ * other rows, and a finishing half, which expects xch summed over all ranks (one all-reduce(SUM) issued by the host between
+ * the two; adding zeros is exact, so every rank then holds bitwise the same rows) and merges the rows in rank order, in
+ * double.  xch_floats: the size of the buffer, at least W * 3 * C (forward) or W * 4 * C (backward).
+ *   stats_local: row = the local mean as two floats [2][C] and M2 = sum (x - local mean)^2 [C].
+ *   fwd_apply:   mean = sum mean_r / W, M2 = sum M2_r + R_local * sum (mean_r - mean)^2; writes mean [2][C], rstd [2][C] =
+ *                1 / sqrt(M2 / N + eps) as two floats like the mean (high parts, then low parts), moves running_mean /
+ *                running_var (unbiased M2 / (N - 1)) and writes y.
+ *   bwd_local:   row = the local sum of g [C] and of g * xhat [C] (g = dy gated by y > 0 behind a ReLU), accumulated in
+ *                double and written as two floats each: the high parts [2][C], then the low parts [2][C].  With few rows
+ *                per channel (two ranks of batch 1 after the average pool) xhat^2 is close to 1 and dx below cancels to
+ *                eps * rstd^2 of its terms, so a sum or an rstd rounded to fp32 would be wrong in dx's second digit.
+ *   bwd_finish:  dx = gamma * rstd * (g - S_g / N - xhat * S_gx / N) in double with the totals over all ranks; dgamma / dbeta =
+ *                acc * old + the LOCAL sums (row `rank`) when not NULL: the optimizer's gradient exchange averages them.
+ * ws: munit_batchnorm_dp_workspace_bytes(C) for stats_local, bwd_local and bwd_finish. */
+size_t munit_batchnorm_dp_workspace_bytes(int C);
+int munit_batchnorm_dp_stats_local(const float* x, long long R_local, int C, int W, int rank, float* xch, size_t xch_floats,
+                                   void* ws, size_t ws_bytes, munit_stream_t stream);
+int munit_batchnorm_dp_fwd_apply(const float* x, float* y, float* mean, float* rstd, float* running_mean, float* running_var,
+                                 long long R_local, int C, int W, const float* xch, size_t xch_floats, const float* gamma,
+                                 const float* beta, int relu, float eps, float momentum, munit_stream_t stream);
+int munit_batchnorm_dp_bwd_local(const float* x, const float* dy, const float* y, const float* mean, const float* rstd,
+                                 long long R_local, int C, int relu, int W, int rank, float* xch, size_t xch_floats, void* ws,
+                                 size_t ws_bytes, munit_stream_t stream);
+int munit_batchnorm_dp_bwd_finish(const float* x, const float* dy, const float* y, const float* gamma, const float* mean,
+                                  const float* rstd, float* dx, float* dgamma, float* dbeta, float acc, long long R_local,
+                                  int C, int relu, int W, int rank, const float* xch, size_t xch_floats, void* ws,
+                                  size_t ws_bytes, munit_stream_t stream);
 /* nn.MaxPool2d(2): y [B][H/2][W/2][C] (floor: an odd trailing row / column is dropped; H, W >= 2).  idx (one byte per
  * output) receives the window position kh*2 + kw of the winner: the FIRST maximal element in window order, torch's tie
  * rule (a NaN counts as maximal).  bwd writes every dx element exactly once: dy at the winners, 0 at the losers and in the

@@ -133,6 +133,14 @@ SIGNATURES = {
                                     _P, c_size_t, _P]),
     "munit_batchnorm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, ctypes.c_longlong, c_int, c_int, _P,
                                     c_size_t, _P]),
+    "munit_batchnorm_dp_workspace_bytes": (c_size_t, [c_int]),
+    "munit_batchnorm_dp_stats_local": (c_int, [_P, ctypes.c_longlong, c_int, c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),
+    "munit_batchnorm_dp_fwd_apply": (c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, c_int, _P, c_size_t, _P, _P,
+                                             c_int, c_float, c_float, _P]),
+    "munit_batchnorm_dp_bwd_local": (c_int, [_P, _P, _P, _P, _P, ctypes.c_longlong, c_int, c_int, c_int, c_int, _P, c_size_t,
+                                             _P, c_size_t, _P]),
+    "munit_batchnorm_dp_bwd_finish": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, ctypes.c_longlong, c_int, c_int,
+                                              c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),
     "munit_maxpool2_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "munit_maxpool2_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "munit_avgpool16_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),

@@ -177,6 +177,194 @@ int bn_check(long long R, int C, const char* what) {
   return MUNIT_OK;
 }
 
+// ---- batch norm across data-parallel ranks ---------------------------------------------------------------------------------
+// W ranks hold R_local rows each of one joined batch of N = W * R_local rows.  Every rank reduces its own rows with the
+// kernels above and writes the result into ITS row of an exchange buffer whose other rows it zeroes; the host sums the
+// buffers of all ranks (an all-reduce: adding zeros is exact, so every rank then holds bitwise the same W rows, whatever
+// order the collective adds in), and a finishing kernel merges the rows in rank order, in double.
+
+// forward rows: xch[r][0..2C) = the local mean (high parts, low parts), xch[r][2C..3C) = M2 = sum of (x - local mean)^2
+__global__ void bn_dp_stats_row_kernel(const float* __restrict__ part, int nb, int C, int W, int rank,
+                                       const float* __restrict__ mean_local, float* __restrict__ xch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= W * 3 * C) return;
+  const int row = i / (3 * C), j = i % (3 * C);
+  float v = 0.f;
+  if (row == rank) {
+    if (j < 2 * C) {
+      v = mean_local[j];
+    } else {
+      double s = 0.0;
+      for (int b = 0; b < nb; ++b) s += (double)part[(long long)b * C + (j - 2 * C)];
+      v = (float)s;
+    }
+  }
+  xch[i] = v;
+}
+
+// the pairwise merge of W equal-sized parts (Chan et al.): mean = sum of the means / W, M2 = sum of the M2 + R_local * sum of
+// (mean_r - mean)^2; rstd with the biased variance M2 / N, the running statistics with the unbiased M2 / (N - 1).  rstd is
+// kept as two floats like the mean, rstd[c] + rstd[C + c]: with few rows per channel xhat^2 is close to 1, the backward's
+// g - sum_g / N - xhat * sum_gx / N cancels to eps * rstd^2 of its terms, and a rounding of rstd to fp32 would be 1e-2 of dx
+__global__ void bn_dp_combine_kernel(const float* __restrict__ xch, int W, long long R_local, int C, float eps, float momentum,
+                                     float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ run_mean,
+                                     float* __restrict__ run_var) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double ms = 0.0;
+  for (int r = 0; r < W; ++r) {
+    const float* row = xch + (long long)r * 3 * C;
+    ms += (double)row[c] + (double)row[C + c];
+  }
+  const double mu = ms / (double)W;
+  double m2 = 0.0, d2 = 0.0;
+  for (int r = 0; r < W; ++r) {
+    const float* row = xch + (long long)r * 3 * C;
+    const double d = ((double)row[c] + (double)row[C + c]) - mu;
+    m2 += (double)row[2 * C + c];
+    d2 += d * d;
+  }
+  const double n = (double)W * (double)R_local;
+  const double M2 = m2 + (double)R_local * d2;
+  const float hi = (float)mu;
+  mean[c] = hi;
+  mean[C + c] = (float)(mu - (double)hi);
+  const double rs = 1.0 / sqrt(M2 / n + (double)eps);
+  const float rhi = (float)rs;
+  rstd[c] = rhi;
+  rstd[C + c] = (float)(rs - (double)rhi);
+  run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)mu;
+  if (n > 1.0) run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)(M2 / (n - 1.0));
+}
+
+// The backward of the joined batch in double.  With two rows per channel (one per rank) xhat is +-1 / sqrt(1 + eps / var) and
+// g - sum_g / N - xhat * sum_gx / N cancels to eps * rstd^2 of its terms, so every fp32 rounding on the way (of xhat, of a
+// partial sum, of a total in the exchange buffer) would show 1e3 to 1e5 times larger in dx.  The local sums therefore
+// accumulate in double and cross the ranks as two floats each (high part, low part), like the mean.
+
+// part[b][0][c] = sum of g, part[b][1][c] = sum of g * xhat over the block's rows, in double; g = dy gated by y > 0
+__global__ void bn_dp_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ y,
+                                         const float* __restrict__ mean, const float* __restrict__ rstd, long long R, int C,
+                                         int relu, double* __restrict__ part) {
+  __shared__ double red[2 * 4 * NT];
+  const int C4 = C >> 2, rl = NT / C4;
+  const int c4 = threadIdx.x % C4, lane = threadIdx.x / C4;
+  const long long per = (R + gridDim.x - 1) / gridDim.x;
+  const long long r0 = (long long)blockIdx.x * per, r1 = r0 + per < R ? r0 + per : R;
+  const f32x4 m = ld4(mean + 4 * c4), lo = ld4(mean + C + 4 * c4), rh = ld4(rstd + 4 * c4), rlo = ld4(rstd + C + 4 * c4);
+  double sg[4] = {0.0, 0.0, 0.0, 0.0}, sgx[4] = {0.0, 0.0, 0.0, 0.0};
+  for (long long r = r0 + lane; r < r1; r += rl) {
+    const long long o = r * C + 4 * c4;
+    const f32x4 g = ld4(dy + o), xx = ld4(x + o);
+    const f32x4 yy = relu ? ld4(y + o) : f32x4{1.f, 1.f, 1.f, 1.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double gk = yy[k] > 0.f ? (double)g[k] : 0.0;
+      const double xh = (((double)xx[k] - (double)m[k]) - (double)lo[k]) * ((double)rh[k] + (double)rlo[k]);
+      sg[k] += gk;
+      sgx[k] += gk * xh;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    red[(0 * NT + lane * C4 + c4) * 4 + k] = sg[k];
+    red[(1 * NT + lane * C4 + c4) * 4 + k] = sgx[k];
+  }
+  __syncthreads();
+  if (lane == 0) {   // the row lanes in lane order
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      double a = 0.0, b = 0.0;
+      for (int l = 0; l < rl; ++l) {
+        a += red[(0 * NT + l * C4 + c4) * 4 + k];
+        b += red[(1 * NT + l * C4 + c4) * 4 + k];
+      }
+      part[((long long)blockIdx.x * 2 + 0) * C + 4 * c4 + k] = a;
+      part[((long long)blockIdx.x * 2 + 1) * C + 4 * c4 + k] = b;
+    }
+  }
+}
+
+// backward rows of 4C floats: xch[r][0..C) = the local sum of g, xch[r][C..2C) = the local sum of g * xhat (high parts),
+// xch[r][2C..4C) = their low parts
+__global__ void bn_dp_bwd_row_kernel(const double* __restrict__ part, int nb, int C, int W, int rank, float* __restrict__ xch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= W * 4 * C) return;
+  const int row = i / (4 * C), j = i % (4 * C);
+  float v = 0.f;
+  if (row == rank) {
+    const int k = (j / C) & 1, c = j % C;
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += part[((long long)b * 2 + k) * C + c];
+    const float hi = (float)s;
+    v = j < 2 * C ? hi : (float)(s - (double)hi);
+  }
+  xch[i] = v;
+}
+
+// sums = the totals over all ranks in double (for dx); dbeta / dgamma = acc * old + the LOCAL sums (the optimizer's gradient
+// exchange averages them like every other weight gradient)
+__global__ void bn_dp_bwd_finish_kernel(const float* __restrict__ xch, int W, int rank, int C, float acc, double* __restrict__ sums,
+                                        float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double a = 0.0, b = 0.0;
+  for (int r = 0; r < W; ++r) {
+    const float* row = xch + (long long)r * 4 * C;
+    a += (double)row[c] + (double)row[2 * C + c];
+    b += (double)row[C + c] + (double)row[3 * C + c];
+  }
+  sums[c] = a;
+  sums[C + c] = b;
+  const float* own = xch + (long long)rank * 4 * C;   // the high part IS the sum rounded to fp32
+  if (dbeta) dbeta[c] = (acc != 0.f ? acc * dbeta[c] : 0.f) + own[c];
+  if (dgamma) dgamma[c] = (acc != 0.f ? acc * dgamma[c] : 0.f) + own[C + c];
+}
+
+// dx = gamma * rstd * (g - sum_g / N - xhat * sum_gx / N), in double, rounded once
+__global__ void bn_dp_bwd_dx_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ y,
+                                    const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                    const double* __restrict__ sums, long long R, int C, int relu, double inv_n,
+                                    float* __restrict__ dx) {
+  const int C4 = C >> 2;
+  const long long total = R * C4;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int c = 4 * (int)(i % C4);
+    const f32x4 g = ld4(dy + 4 * i), xx = ld4(x + 4 * i), ga = ld4(gamma + c);
+    const f32x4 yy = relu ? ld4(y + 4 * i) : f32x4{1.f, 1.f, 1.f, 1.f};
+    const f32x4 m = ld4(mean + c), lo = ld4(mean + C + c), rh = ld4(rstd + c), rlo = ld4(rstd + C + c);
+    f32x4 out;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double rs = (double)rh[k] + (double)rlo[k];
+      const double xh = (((double)xx[k] - (double)m[k]) - (double)lo[k]) * rs;
+      const double gk = yy[k] > 0.f ? (double)g[k] : 0.0;
+      out[k] = (float)((double)ga[k] * rs * (gk - sums[c + k] * inv_n - xh * (sums[C + c + k] * inv_n)));
+    }
+    st4(dx + 4 * i, out);
+  }
+}
+
+// the workspace of the cross-rank entry points: the partials (in double in the backward), then 2C doubles (the local mean of
+// the forward as floats, the totals of the backward)
+size_t bn_dp_part_bytes(int C) { return 2 * bn_part_bytes(C); }
+
+constexpr int BN_DP_MAX_W = 64;
+
+int bn_dp_check(long long R_local, int C, int W, int rank, const void* xch, size_t xch_floats, int per_row, const char* what,
+                bool joined = true) {
+  int rc = bn_check(R_local, C, what);
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(W >= 1 && W <= BN_DP_MAX_W && rank >= 0 && rank < W, "%s: W = %d ranks (1..%d), rank %d", what, W,
+                  BN_DP_MAX_W, rank);
+  MUNIT_CHECK_ARG(!joined || (long long)W * R_local >= 2, "%s: the joined batch needs more than one value per channel (W * R_local = %lld)",
+                  what, (long long)W * R_local);
+  MUNIT_CHECK_ARG(xch != nullptr, "%s: null pointer (exchange buffer)", what);
+  MUNIT_CHECK_ARG(xch_floats >= (size_t)W * per_row * C, "%s: exchange buffer of %zu floats < W * %d * C = %zu", what,
+                  xch_floats, per_row, (size_t)W * per_row * C);
+  return MUNIT_OK;
+}
+
 // ---- 2x2 / stride-2 max-pool -------------------------------------------------------------------------------------------
 // one thread: one output pixel x 4 channels.  The first maximum in window order (0,0) (0,1) (1,0) (1,1) wins; a NaN counts as
 // a maximum, as in torch's kernels.
@@ -336,6 +524,103 @@ extern "C" int munit_batchnorm_bwd(const float* x, const float* dy, const float*
   hipLaunchKernelGGL(bn_bwd_dx_kernel, dim3(grid_for(R * (C / 4))), dim3(NT), 0, st, x, dy, y, gamma, mean, rstd,
                      (const float*)sums, R, C, relu, (float)(1.0 / (double)R), dx);
   MUNIT_CHECK_LAUNCH("batchnorm_bwd (dx)");
+  return MUNIT_OK;
+}
+
+extern "C" size_t munit_batchnorm_dp_workspace_bytes(int C) {
+  if (C <= 0) return 0;
+  return bn_dp_part_bytes(C) + align_up((size_t)2 * C * sizeof(double), 256);
+}
+
+extern "C" int munit_batchnorm_dp_stats_local(const float* x, long long R_local, int C, int W, int rank, float* xch,
+                                              size_t xch_floats, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  int rc = bn_dp_check(R_local, C, W, rank, xch, xch_floats, 3, "batchnorm_dp_stats_local");
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(x && ws, "batchnorm_dp_stats_local: null pointer");
+  if (ws_bytes < munit_batchnorm_dp_workspace_bytes(C)) {
+    munit_set_error("batchnorm_dp_stats_local: workspace %zu < %zu", ws_bytes, munit_batchnorm_dp_workspace_bytes(C));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* part = reinterpret_cast<float*>(ws);
+  float* mean_local = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + bn_dp_part_bytes(C));
+  const int nb = bn_blocks(R_local, C);
+  hipLaunchKernelGGL(bn_partial_kernel, dim3(nb), dim3(NT), 0, st, x, (const float*)nullptr, R_local, C, 0, part);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_stats_local (sum)");
+  hipLaunchKernelGGL(bn_finish_kernel, dim3((C + NT - 1) / NT), dim3(NT), 0, st, x, (const float*)part, nb, R_local, C, 0, 0.f,
+                     0.f, mean_local, (float*)nullptr, (float*)nullptr, (float*)nullptr);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_stats_local (mean)");
+  hipLaunchKernelGGL(bn_partial_kernel, dim3(nb), dim3(NT), 0, st, x, (const float*)mean_local, R_local, C, 1, part);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_stats_local (squares)");
+  hipLaunchKernelGGL(bn_dp_stats_row_kernel, dim3((W * 3 * C + NT - 1) / NT), dim3(NT), 0, st, (const float*)part, nb, C, W, rank,
+                     (const float*)mean_local, xch);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_stats_local (row)");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_batchnorm_dp_fwd_apply(const float* x, float* y, float* mean, float* rstd, float* running_mean,
+                                            float* running_var, long long R_local, int C, int W, const float* xch,
+                                            size_t xch_floats, const float* gamma, const float* beta, int relu, float eps,
+                                            float momentum, munit_stream_t stream) {
+  // N >= 2 is stats_local's to refuse (every pass begins there); one row merges to M2 = 0 and leaves running_var alone
+  int rc = bn_dp_check(R_local, C, W, 0, xch, xch_floats, 3, "batchnorm_dp_fwd_apply", false);
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(x && y && mean && rstd && gamma && beta && running_mean && running_var, "batchnorm_dp_fwd_apply: null pointer");
+  MUNIT_CHECK_ARG((relu == 0 || relu == 1) && eps > 0.f, "batchnorm_dp_fwd_apply: bad relu / eps");
+  MUNIT_CHECK_ARG(momentum >= 0.f && momentum <= 1.f, "batchnorm_dp_fwd_apply: momentum %g", (double)momentum);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(bn_dp_combine_kernel, dim3((C + NT - 1) / NT), dim3(NT), 0, st, xch, W, R_local, C, eps, momentum, mean, rstd,
+                     running_mean, running_var);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_fwd_apply (combine)");
+  // y takes the high part of rstd alone (6e-8 of y, inside the forward's bound); the low part is for the backward's xhat
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(R_local * (C / 4))), dim3(NT), 0, st, x, (const float*)mean,
+                     (const float*)rstd, gamma, beta, R_local, C, relu, 0, eps, y);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_fwd_apply (apply)");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_batchnorm_dp_bwd_local(const float* x, const float* dy, const float* y, const float* mean,
+                                            const float* rstd, long long R_local, int C, int relu, int W, int rank, float* xch,
+                                            size_t xch_floats, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  int rc = bn_dp_check(R_local, C, W, rank, xch, xch_floats, 4, "batchnorm_dp_bwd_local");
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(x && dy && mean && rstd && ws, "batchnorm_dp_bwd_local: null pointer");
+  MUNIT_CHECK_ARG(relu == 0 || (relu == 1 && y), "batchnorm_dp_bwd_local: the ReLU branch needs y");
+  if (ws_bytes < munit_batchnorm_dp_workspace_bytes(C)) {
+    munit_set_error("batchnorm_dp_bwd_local: workspace %zu < %zu", ws_bytes, munit_batchnorm_dp_workspace_bytes(C));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(ws);
+  const int nb = bn_blocks(R_local, C);
+  hipLaunchKernelGGL(bn_dp_bwd_partial_kernel, dim3(nb), dim3(NT), 0, st, x, dy, y, mean, rstd, R_local, C, relu, part);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_bwd_local (sums)");
+  hipLaunchKernelGGL(bn_dp_bwd_row_kernel, dim3((W * 4 * C + NT - 1) / NT), dim3(NT), 0, st, (const double*)part, nb, C, W, rank,
+                     xch);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_bwd_local (row)");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_batchnorm_dp_bwd_finish(const float* x, const float* dy, const float* y, const float* gamma,
+                                             const float* mean, const float* rstd, float* dx, float* dgamma, float* dbeta,
+                                             float acc, long long R_local, int C, int relu, int W, int rank, const float* xch,
+                                             size_t xch_floats, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  int rc = bn_dp_check(R_local, C, W, rank, xch, xch_floats, 4, "batchnorm_dp_bwd_finish");
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(x && dy && gamma && mean && rstd && dx && ws, "batchnorm_dp_bwd_finish: null pointer");
+  MUNIT_CHECK_ARG(relu == 0 || (relu == 1 && y), "batchnorm_dp_bwd_finish: the ReLU branch needs y");
+  MUNIT_CHECK_ARG(acc == 0.f || acc == 1.f, "batchnorm_dp_bwd_finish: acc must be 0 or 1");
+  if (ws_bytes < munit_batchnorm_dp_workspace_bytes(C)) {
+    munit_set_error("batchnorm_dp_bwd_finish: workspace %zu < %zu", ws_bytes, munit_batchnorm_dp_workspace_bytes(C));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  double* sums = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + bn_dp_part_bytes(C));
+  hipLaunchKernelGGL(bn_dp_bwd_finish_kernel, dim3((C + NT - 1) / NT), dim3(NT), 0, st, xch, W, rank, C, acc, sums, dgamma, dbeta);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_bwd_finish (finish)");
+  hipLaunchKernelGGL(bn_dp_bwd_dx_kernel, dim3(grid_for(R_local * (C / 4))), dim3(NT), 0, st, x, dy, y, gamma, mean, rstd,
+                     (const double*)sums, R_local, C, relu, 1.0 / ((double)W * (double)R_local), dx);
+  MUNIT_CHECK_LAUNCH("batchnorm_dp_bwd_finish (dx)");
   return MUNIT_OK;
 }
 

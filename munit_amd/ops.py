@@ -34,6 +34,10 @@ SEG_SINK = None
 # likewise for the feature classifiers of adv_lambda / dfeat_lambda (networks.domainClassifier): the max-pool winners, the
 # ReLU sign patterns behind batch_norm and the block tails, in call order
 DANN_SINK = None
+# Data-parallel batch norm (adaptation.data_parallel: 1): the world size of the process group whose ranks share the batch
+# statistics of training-mode batch_norm, 0 = every process normalises its own batch.  Set by the trainer around the feature
+# classifiers' forward passes (bn_world); a backward pass takes the value its forward ran with.
+BN_WORLD = 0
 # bench.py sets this to {"alg": 0.0, "exec": 0.0} to add up, over one step, the algorithmic FLOPs of every convolution /
 # linear pass (SURVEY.md section 8d's definition) and the FLOPs the kernels actually issue (sub-pixel and box-sum
 # forms execute fewer).
@@ -1335,6 +1339,102 @@ def seg_labels(logits, scale=8):
 # ------------------------------------------------------------------------------------------
 # feature classifier of adaptation.adv_lambda / dfeat_lambda (networks.domainClassifier; include/munit_hip.h, dann.hip)
 # ------------------------------------------------------------------------------------------
+class bn_world(object):
+    """`with bn_world(w):` -- training-mode batch_norm calls inside take their statistics over the w ranks of the default
+    process group (w <= 1: over the process's own batch)."""
+
+    def __init__(self, world):
+        self.world = int(world) if world and world > 1 else 0
+
+    def __enter__(self):
+        global BN_WORLD
+        self.saved, BN_WORLD = BN_WORLD, self.world
+        return self
+
+    def __exit__(self, *exc):
+        global BN_WORLD
+        BN_WORLD = self.saved
+        return False
+
+
+def _xch_all_reduce(xch):
+    """The one collective of a cross-rank batch-norm pass: SUM of the one-hot-row exchange buffers, issued from the host in
+    program order on the stream the op runs on (the collective is ordered behind, and hands back to, the current stream).
+    Every rank issues the same collectives in the same order: the trainer runs the a and the b classifier one after the
+    other on the host (on two streams, but from one thread), and the backward passes run in the autograd engine's order,
+    which is a function of the graph -- the argument of trainer.GradExchange, whose staged all-reduces these interleave
+    with inside gen_update's backward."""
+    import torch.distributed as dist
+    dist.all_reduce(xch)
+
+
+class _BatchNormDP(Function):
+    """_BatchNorm with statistics over `world` ranks of equal batches (include/munit_hip.h, munit_batchnorm_dp_*): local
+    reduction into the rank's row of the exchange buffer, all-reduce, merge + apply; the backward likewise.  dgamma / dbeta
+    receive the LOCAL sums: the optimizer's gradient exchange averages them like every other weight gradient."""
+    @staticmethod
+    @_guarded
+    def forward(ctx, x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads, world, rank):
+        _require(x, "batch-norm input")
+        lib = _lib.load()
+        x = nhwc(x)
+        b, c, h, w = x.shape
+        for t, nm in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+            _require(t, "batch-norm " + nm)
+            if tuple(t.shape) != (c,) or not t.is_contiguous():
+                raise RuntimeError("munit_amd.batch_norm: %s must be a contiguous (%d,) tensor" % (nm, c))
+        _same_device(x, gamma, beta, running_mean, running_var)
+        y = torch.empty_like(x)
+        mean = torch.empty(2 * c, device=x.device, dtype=torch.float32)      # high parts, then low parts
+        rstd = torch.empty(2 * c, device=x.device, dtype=torch.float32)      # likewise: the backward cancels with few rows
+        xch = torch.empty(world * 3 * c, device=x.device, dtype=torch.float32)
+        ws = workspace(lib.munit_batchnorm_dp_workspace_bytes(c), x.device)
+        relu = int(bool(relu))
+        _lib.check(lib.munit_batchnorm_dp_stats_local(_p(x), b * h * w, c, world, rank, _p(xch), xch.numel(), _p(ws),
+                                                      ws.numel(), _stream()), "batchnorm_dp_stats_local")
+        _xch_all_reduce(xch)
+        _lib.check(lib.munit_batchnorm_dp_fwd_apply(_p(x), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
+                                                    b * h * w, c, world, _p(xch), xch.numel(), _p(gamma), _p(beta), relu,
+                                                    c_float(eps), c_float(momentum), _stream()), "batchnorm_dp_fwd_apply")
+        ctx.relu, ctx.world, ctx.rank = relu, world, rank
+        ctx.want = bool(need_weight_grads)
+        ctx.gbuf = getattr(gamma, "_munit_grad", None)
+        ctx.bbuf = getattr(beta, "_munit_grad", None)
+        ctx.save_for_backward(x, y if relu else None, gamma, mean, rstd)
+        if DANN_SINK is not None and relu:
+            DANN_SINK.append(y > 0)
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, y, gamma, mean, rstd = ctx.saved_tensors
+        dy = nhwc(dy)
+        b, c, h, w = x.shape
+        dx = torch.empty_like(x)
+        want = ctx.want and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        into = want and ctx.gbuf is not None and ctx.bbuf is not None
+        dgamma = dbeta = None
+        if want:
+            dgamma = ctx.gbuf if into else torch.empty_like(gamma)
+            dbeta = ctx.bbuf if into else torch.empty_like(gamma)
+        xch = torch.empty(ctx.world * 4 * c, device=x.device, dtype=torch.float32)     # two sums, each as two floats
+        ws = workspace(lib.munit_batchnorm_dp_workspace_bytes(c), x.device)
+        _lib.check(lib.munit_batchnorm_dp_bwd_local(_p(x), _p(dy), _p(y), _p(mean), _p(rstd), b * h * w, c, ctx.relu,
+                                                    ctx.world, ctx.rank, _p(xch), xch.numel(), _p(ws), ws.numel(), _stream()),
+                   "batchnorm_dp_bwd_local")
+        _xch_all_reduce(xch)       # need_weight_grads False forms dx only, but still takes part in the exchange
+        _lib.check(lib.munit_batchnorm_dp_bwd_finish(_p(x), _p(dy), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma),
+                                                     _p(dbeta), c_float(1.0 if into else 0.0), b * h * w, c, ctx.relu,
+                                                     ctx.world, ctx.rank, _p(xch), xch.numel(), _p(ws), ws.numel(), _stream()),
+                   "batchnorm_dp_bwd_finish")
+        tail = (None,) * 8
+        if into or not want:
+            return (dx, None, None) + tail
+        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None) + tail
+
+
 class _BatchNorm(Function):
     """Training-mode nn.BatchNorm2d (+ReLU).  running_mean / running_var are updated in place by the forward kernel.
     need_weight_grads False: backward forms dx only (gen_update: the classifier's weight gradients would be zeroed unused)."""
@@ -1392,10 +1492,18 @@ class _BatchNorm(Function):
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, relu=False, eps=1e-5, momentum=0.1, training=True,
-               need_weight_grads=True):
+               need_weight_grads=True, world=None):
     """nn.BatchNorm2d (scripts/utils.py:1293) [+ReLU].  training: normalise with the batch statistics (biased variance) and
     move the running statistics in place (unbiased variance); else normalise with the running statistics (no gradient
-    is defined for that form: it completes the module, the classifier never takes it)."""
+    is defined for that form: it completes the module, the classifier never takes it).  world (default: BN_WORLD) > 1: the
+    training-mode statistics span that many ranks of the default process group, each with a batch of this size."""
+    world = BN_WORLD if world is None else world
+    if training and world > 1:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() != world:
+            raise RuntimeError("munit_amd.batch_norm: world %d needs a process group of that size" % world)
+        return _BatchNormDP.apply(x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads,
+                                  int(world), dist.get_rank())
     if training:
         return _BatchNorm.apply(x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads)
     _require(x, "batch-norm input")

@@ -25,8 +25,8 @@ Feature-level domain adaptation (adaptation.dfeat_lambda > 0, trainer.py:161-179
 content codes, trained by domain_classifier_sr_update (training-mode BatchNorm2d, max-pool and 16x16 average are HIP kernels
 of their own, dann.hip) under their own optimizer classif_opt_sr; adaptation.adv_lambda > 0 adds the fooling term
 (target 0.5) to gen_update, whose backward forms the gradient of the two content codes only -- the classifiers' weight
-gradients, which the reference computes and zeroes unused (trainer.py:1241), are skipped.  fp32 and one device only; like
-the reference, save / resume do not carry the classifiers.
+gradients, which the reference computes and zeroes unused (trainer.py:1241), are skipped.  fp32 only; like the reference,
+save / resume do not carry the classifiers.
 
 Output-level domain adaptation (adaptation.output_classifier_lambda > 0 and adaptation.output_adv_lambda > 0,
 trainer.py:181-201): two more MsImageDis, output_classifier_sr_a / _b, on the images themselves, trained by
@@ -34,8 +34,17 @@ output_domain_classifier_sr_update (simulated -> 0, real -> 1) under their own o
 the plain step() as the reference's update does; gen_update adds calc_gen_loss_sr (target 0.5) of the two translations
 with weight output_adv_lambda, forming no classifier weight gradient (the next update's zero_grad would discard it).  The
 multi-scale loss of a discriminator pass is one kernel pair (ops.lsgan_loss).  Either weight without the other is refused;
-fp32, one device, Adam only.  As in the reference, update_learning_rate does not step output_scheduler_sr and save / resume
-do not carry these classifiers either.
+fp32, Adam only.  As in the reference, update_learning_rate does not step output_scheduler_sr and save / resume do not carry
+these classifiers either.
+
+Both adaptation levels train data-parallel under the build extension adaptation.data_parallel: 1 (default 0: a process
+group of more than one rank is refused, as a change of the batch statistics should be a visible decision).  The two
+classifier updates all-reduce their optimizers' flat gradients in line before the step, and the feature classifiers'
+training-mode batch norms take their statistics over all ranks, forward and backward, in the classifier update and in
+gen_update's fooling term (ops.bn_world, munit_batchnorm_dp_*): W ranks on W equal part-batches compute what one process
+computes on the joined batch, and all ranks end every update with bitwise identical weights and running statistics.  The
+output classifiers have no batch statistics; their fooling term lands in the generator's flat gradient and needs no
+exchange of its own.
 
 The other aux losses (VGG, the a/b domain classifier of domain_adv_w, sem_seg_lambda) raise NotImplementedError when their
 weight is non-zero.
@@ -610,10 +619,11 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         if hp.get("precision", "f32") != "f32":
             raise NotImplementedError("munit_amd: adaptation.adv_lambda / adaptation.dfeat_lambda run in fp32 only "
                                       "(precision %r)" % hp["precision"])
-        if dp_size() > 1:
+        if dp_size() > 1 and not ad.get("data_parallel", 0):
             raise NotImplementedError("munit_amd: adaptation.adv_lambda / adaptation.dfeat_lambda are not implemented for "
                                       "data-parallel training (world size %d): the classifiers' gradients and batch "
-                                      "statistics are not exchanged" % dp_size())
+                                      "statistics are not exchanged; set adaptation.data_parallel: 1 to exchange them (the "
+                                      "classifiers' batch norms then take their statistics over all ranks)" % dp_size())
         n = hp["gen"]["n_downsample"]
         try:
             domainClassifier.check_code_hw(hp["crop_image_height"] >> n, hp["crop_image_width"] >> n)
@@ -636,9 +646,10 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         keys = "adaptation.output_adv_lambda / adaptation.output_classifier_lambda"
         if hp.get("precision", "f32") != "f32":
             raise NotImplementedError("munit_amd: %s run in fp32 only (precision %r)" % (keys, hp["precision"]))
-        if dp_size() > 1:
+        if dp_size() > 1 and not hp["adaptation"].get("data_parallel", 0):
             raise NotImplementedError("munit_amd: %s are not implemented for data-parallel training (world size %d): the "
-                                      "classifiers' gradients are not exchanged" % (keys, dp_size()))
+                                      "classifiers' gradients are not exchanged; set adaptation.data_parallel: 1 to exchange "
+                                      "them" % (keys, dp_size()))
         if "extra" in hp.get("optimizer", "adam"):
             raise NotImplementedError("munit_amd: %s are not implemented for optimizer %r: the reference's update calls "
                                       "step() without extrapolation(), on which its ExtraAdam raises"
@@ -783,14 +794,24 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
     def _sr_target(domain_synth, fool):
         return 0.5 if fool else (0.0 if domain_synth else 1.0)
 
+    @staticmethod
+    def _bn_world(hp):
+        """World size over which the feature classifiers' batch norms take their statistics (ops.bn_world): the process
+        group's under adaptation.data_parallel: 1 with more than one rank, else 0 (the process's own batch).  The ranks start
+        from identical classifiers the way they start from identical generators: every rank constructs its trainer under
+        the same seed (bench.py, tests/test_gpu_dp.py); the batch-norm buffers start at 0 / 1 and move by the joined
+        statistics, which are bitwise the same on every rank."""
+        return dp_size() if (hp["adaptation"].get("data_parallel", 0) and dp_size() > 1) else 0
+
     def compute_classifier_sr_loss(self, c_a, c_b, domain_synth=False, fool=False, need_weight_grads=True):
         """mean((cls_a(c_a) - t)^2) + mean((cls_b(c_b) - t)^2), t = 0.5 to fool, else 0 for synthetic and 1 for real codes.
         need_weight_grads False (build extension): the backward pass forms the gradients of c_a / c_b only."""
         if not self.use_classifier_sr:
             raise ValueError("munit_amd: compute_classifier_sr_loss needs a trainer built with adaptation.dfeat_lambda > 0")
         t = self._sr_target(domain_synth, fool)
-        output_a = self.domain_classifier_sr_a(c_a, need_weight_grads)
-        output_b = self.domain_classifier_sr_b(c_b, need_weight_grads)
+        with ops.bn_world(self._bn_world(self.hyperparameters)):
+            output_a = self.domain_classifier_sr_a(c_a, need_weight_grads)
+            output_b = self.domain_classifier_sr_b(c_b, need_weight_grads)
         return ops.scalar_sum([ops.mse_const(output_a, t), ops.mse_const(output_b, t)])
 
     def domain_classifier_sr_update(self, x_a, x_b, domain_synth, lambda_classifier, step, comet_exp=None):
@@ -812,14 +833,18 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                 c = self._content_enc(k)(x)
             return ops.mse_const(cls(c.detach()), t)
 
-        l_a = br.run(0, lambda: half(x_a, 1, self.domain_classifier_sr_a))
-        l_b = br.run(1, lambda: half(x_b, 2, self.domain_classifier_sr_b))
+        # data parallel: the batch norms exchange their statistics inside both passes -- a before b in the forward (the host
+        # issues the two halves one after the other), the engine's order in the backward: the same sequence on every rank
+        with ops.bn_world(self._bn_world(self.hyperparameters)):
+            l_a = br.run(0, lambda: half(x_a, 1, self.domain_classifier_sr_a))
+            l_b = br.run(1, lambda: half(x_b, 2, self.domain_classifier_sr_b))
         br.join(l_a, l_b)
         loss = ops.scalar_sum([l_a, l_b])
         self.loss_classifier_sr_update = loss.detach()      # unweighted; the reference logs lambda_classifier * loss
         torch.autograd.backward([loss], [self._const(lambda_classifier, dev)])
         br.join()
         ops.join_side_streams()
+        self._all_reduce_mean(self.classif_opt_sr.flat_g)   # in line on the caller's stream: 4.8 MB, nothing to overlap with
         self.classif_opt_sr_step()
         if comet_exp is not None and self.iterations % 100 == 0:
             comet_exp.log_metric("loss_classifier_sr", (lambda_classifier * self.loss_classifier_sr_update).cpu(), step=step)
@@ -845,6 +870,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         torch.autograd.backward([loss], [self._const(lam, dev)])
         br.join()
         ops.join_side_streams()
+        self._all_reduce_mean(self.output_classif_opt_sr.flat_g)      # in line on the caller's stream
         self.output_classif_opt_sr.step()
         if comet_exp is not None and self.iterations % 100 == 0:
             comet_exp.log_metric("loss_output_classifier_sr", (lam * self.loss_output_classifier_sr_update).cpu(), step=step)
@@ -973,8 +999,12 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             if fool_sr:
                 # the fooling term (trainer.py:521-525) on the step's own codes; the classifiers' weight gradients would be
                 # zeroed unused by domain_classifier_sr_update (trainer.py:1241): only the codes' gradients are formed
-                sr_a = br.run(0, lambda: ops.mse_const(self.domain_classifier_sr_a(c_a, False), 0.5))
-                sr_b = br.run(1, lambda: ops.mse_const(self.domain_classifier_sr_b(c_b, False), 0.5))
+                # data parallel: the batch norms' statistics span the ranks; their backward exchanges are issued from inside
+                # the generator's backward, between the staged all-reduces of GradExchange -- all from the host in the
+                # engine's order, the same on every rank
+                with ops.bn_world(self._bn_world(hp)):
+                    sr_a = br.run(0, lambda: ops.mse_const(self.domain_classifier_sr_a(c_a, False), 0.5))
+                    sr_b = br.run(1, lambda: ops.mse_const(self.domain_classifier_sr_b(c_b, False), 0.5))
             if reuse:
                 x_ba, x_ab = x_ba_kept, x_ab_kept
             else:

@@ -9,7 +9,10 @@ from torch.optim import lr_scheduler
 
 ADAPTATION_DEFAULTS = dict(full_adaptation=0, output_classifier_lambda=0, output_adv_lambda=0,
                            output_classif_freq=1, adv_lambda=0, dfeat_lambda=0, classif_frequency=15,
-                           sem_seg_lambda=0)
+                           sem_seg_lambda=0,
+                           # build extension (no reference counterpart): 1 lets the adaptation terms train data-parallel,
+                           # with the feature classifiers' batch-norm statistics taken over all ranks (trainer.py)
+                           data_parallel=0)
 
 
 def get_config(config):
