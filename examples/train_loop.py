@@ -61,7 +61,8 @@ def run_iteration(trainer, config, it, real_batch, synth_pairs, on_call=None):
     """Iteration `it` (counted from 0) in the order scripts/train.py:172-274 issues it: update_learning_rate, the real
     dis_update, a gen_update when (it + 1) % ratio_disc_gen == 0, the classifier updates on their own cadences of it + 1,
     then -- when it % synthetic_frequency == 0 -- a synthetic dis_update, a gen_update(synth=True) that ratio_disc_gen does
-    not gate, and the synthetic feature-classifier update.  real_batch: (x_a, x_b, mask_a, mask_b); synth_pairs: an iterator
+    not gate, and the synthetic feature-classifier update; last, in every iteration with synthetic_frequency > 0, the
+    segmentation_head_update of a trainer with train_seg (scripts/train.py:275-283).  real_batch: (x_a, x_b, mask_a, mask_b); synth_pairs: an iterator
     of (x_as, x_bs, mask_s, sem_a, sem_b) or None.  on_call(name, args, run): called in place of every update with the
     trainer method's name, its positional arguments and `run`, which performs the call (tests wrap the calls with it)."""
     def call(name, *args):
@@ -84,13 +85,19 @@ def run_iteration(trainer, config, it, real_batch, synth_pairs, on_call=None):
         call("output_domain_classifier_sr_update", x_a, pair[0], x_b, pair[1], config, it + 1)
     freq = int(config.get("synthetic_frequency", 0))
     if synth_pairs is not None and freq > 0 and it % freq == 0:         # scripts/train.py:229-260
-        x_as, x_bs, mask_s, sem_a, sem_b = pair if pair is not None else next(synth_pairs)
+        pair = pair if pair is not None else next(synth_pairs)
+        x_as, x_bs, mask_s, sem_a, sem_b = pair
         if config.get("synthetic_seg_gt", 0) == 0:
             sem_a = sem_b = None
         call("dis_update", x_as, x_bs, config)
         call("gen_update", x_as, x_bs, config, mask_s, mask_s, None, True, sem_a, sem_b)
         if cls_due:                                                     # scripts/train.py:261-274: synthetic codes, target 0
             call("domain_classifier_sr_update", x_as, x_bs, True, ad["dfeat_lambda"], it + 1)
+    if synth_pairs is not None and freq > 0 and getattr(trainer, "train_seg", False):
+        # scripts/train.py:275-283: in every iteration, on the iteration's synthetic pair (the one the steps above used when
+        # they ran; the reference's loop loads a pair in every iteration) and its label maps, whatever synthetic_seg_gt says
+        x_as, x_bs, _, sem_a, sem_b = pair if pair is not None else next(synth_pairs)
+        call("segmentation_head_update", x_as, x_bs, sem_a, sem_b, ad["sem_seg_lambda"], None)
 
 
 def main(argv=None, synth_pairs=None):

@@ -416,6 +416,25 @@ int munit_seg_ce_gt_fwd(const float* logits, const float* gt, const float* mask,
                         float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
 int munit_seg_ce_gt_bwd(const float* logits, const float* gt, const float* mask, int B, int h, int w, int S, float norm,
                         const float* gout, float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream);
+
+/* The plain K-class head of the trainable segmentation head (adaptation.sem_seg_lambda, trainer.py:1303-1318): logits
+ * [B][h][w][K], K in 2..32, up-sampled bilinearly by S in {1, 2, 4, 8} on the fly with the tap order of munit_seg_ce_*;
+ * nn.CrossEntropyLoss over the K classes against gt [B][h*S][w*S] FLOAT32 truncated toward zero; no mask, no class merge.
+ * out = (sum of the pixel losses) / norm.  bwd writes the pixel gradients to the workspace, then gathers them through
+ * the up-sample's adjoint: dlogits [B][h][w][K]; deterministic.  A label outside 0..K-1, NaN or infinite is never used as
+ * an index: that pixel's loss is NaN and its gradient 0; both calls still return MUNIT_OK.  Each pass refuses a
+ * workspace short of its own need (fwd: one float per block, bwd: the gradient at the up-sampled resolution);
+ * _workspace_bytes covers both. */
+size_t munit_seg_ce_direct_workspace_bytes(int B, int h, int w, int S, int K);
+int munit_seg_ce_direct_fwd(const float* logits, const float* gt, int B, int h, int w, int S, int K, float norm, float* out,
+                            void* ws, size_t ws_bytes, munit_stream_t stream);
+int munit_seg_ce_direct_bwd(const float* logits, const float* gt, int B, int h, int w, int S, int K, float norm,
+                            const float* gout, float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream);
+/* nn.AvgPool2d(7, stride=1, padding=3) with the padding counted: y[b][i][j][c] = (sum of x over the 7x7 window clipped to
+ * the map) / 49; x, y [B][H][W][C], C % 4 == 0, any H, W >= 1, x != y.  The operator is its own adjoint: bwd computes
+ * dx from dy the same way.  Fixed summation order; deterministic. */
+int munit_avgpool7_fwd(const float* x, float* y, int B, int H, int W, int C, munit_stream_t stream);
+int munit_avgpool7_bwd(const float* dy, float* dx, int B, int H, int W, int C, munit_stream_t stream);
 /* labels = argmax over the 19 up-sampled logits (first maximal class on ties: torch's max(1)[1]). */
 int munit_seg_labels(const float* logits, int B, int h, int w, int S, int* labels, munit_stream_t stream);
 

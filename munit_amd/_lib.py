@@ -128,6 +128,11 @@ SIGNATURES = {
     "munit_seg_ce_gt_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
     "munit_seg_ce_gt_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
     "munit_seg_labels": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "munit_seg_ce_direct_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "munit_seg_ce_direct_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
+    "munit_seg_ce_direct_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
+    "munit_avgpool7_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "munit_avgpool7_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "munit_batchnorm_workspace_bytes": (c_size_t, [c_int]),
     "munit_batchnorm_fwd": (c_int, [_P, _P, _P, _P, _P, _P, ctypes.c_longlong, c_int, _P, _P, c_int, c_int, c_float, c_float,
                                     _P, c_size_t, _P]),

@@ -332,7 +332,9 @@ __global__ void seg_ce_gt_grad_kernel(const float* __restrict__ lg, const float*
 
 // adjoint of the bilinear up-sample as a gather: dl[b][i][j][k] = sum over the output pixels whose taps touch (i, j), in
 // fixed row / column order (the taps of row y reach i0(y) <= i <= i0(y) + 1, so y lies within S rows of [i*S, (i+1)*S))
-__global__ void seg_up_adjoint_kernel(const float* __restrict__ g, int B, int h, int w, int S, float* __restrict__ dl) {
+template <int KC>   // KC: the class count when it is a compile-time constant, 0: the run-time value Krt
+__global__ void seg_up_adjoint_kernel(const float* __restrict__ g, int B, int h, int w, int S, int Krt, float* __restrict__ dl) {
+  const int NCLS = KC ? KC : Krt;
   const int H = h * S, W = w * S;
   const float sy = (float)h / (float)H, sx = (float)w / (float)W;
   const long long total = (long long)B * h * w * NCLS;
@@ -359,6 +361,118 @@ __global__ void seg_up_adjoint_kernel(const float* __restrict__ g, int B, int h,
       acc += wy * row;
     }
     dl[o] = acc;
+  }
+}
+
+// ---- K-class head of the trainable segmentation head (trainer.py:1303-1318): plain cross-entropy, no mask, no merge ----
+// One class at a time, recomputing the up-sampled logit in each of the passes (no K-entry array: K is a run-time value and
+// the kernel stays free of scratch); tap order as up_logits.
+struct Taps4 {
+  const float *p00, *p01, *p10, *p11;
+  float y0, y1, x0, x1;
+  __device__ inline float at(int k) const { return y0 * (x0 * p00[k] + x1 * p01[k]) + y1 * (x0 * p10[k] + x1 * p11[k]); }
+};
+__device__ inline Taps4 taps_of(const float* __restrict__ lg, long long b, int h, int w, int K, const Tap& ty, const Tap& tx) {
+  Taps4 t;
+  t.p00 = lg + ((b * h + ty.i0) * w + tx.i0) * K;
+  t.p01 = lg + ((b * h + ty.i0) * w + tx.i1) * K;
+  t.p10 = lg + ((b * h + ty.i1) * w + tx.i0) * K;
+  t.p11 = lg + ((b * h + ty.i1) * w + tx.i1) * K;
+  t.y0 = ty.l0, t.y1 = ty.l1, t.x0 = tx.l0, t.x1 = tx.l1;
+  return t;
+}
+// log-sum-exp of the K up-sampled logits and the target's logit.  gt: the loader's float label, truncated like
+// .type(torch.long) and never used as an index; ok is false for a label outside 0..K-1, NaN or infinite.
+__device__ inline float direct_lse(const Taps4& t, int K, float gt, bool* ok, int* tgt, float* zt) {
+  *ok = gt > -1.f && gt < (float)K;
+  *tgt = *ok ? (int)gt : -1;
+  float mx = t.at(0);
+  for (int k = 1; k < K; ++k) mx = fmaxf(mx, t.at(k));
+  float se = 0.f, z_t = 0.f;
+  for (int k = 0; k < K; ++k) {
+    const float z = t.at(k);
+    se += expf(z - mx);
+    z_t = k == *tgt ? z : z_t;
+  }
+  *zt = z_t;
+  return mx + logf(se);
+}
+__global__ void seg_ce_direct_fwd_kernel(const float* __restrict__ lg, const float* __restrict__ gt, int B, int h, int w, int S,
+                                         int K, float* __restrict__ part) {
+  __shared__ float red[NT / 64];
+  const int H = h * S, W = w * S;
+  const long long npix = (long long)B * H * W;
+  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+  float acc = 0.f;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(p % W);
+    const int y = (int)((p / W) % H);
+    const long long b = p / ((long long)W * H);
+    const Taps4 t = taps_of(lg, b, h, w, K, tap_of(y, h, sy), tap_of(x, w, sx));
+    bool ok;
+    int tgt;
+    float zt;
+    const float lse = direct_lse(t, K, gt[p], &ok, &tgt, &zt);
+    acc += ok ? lse - zt : NAN;
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int i = 0; i < NT / 64; ++i) s += red[i];
+    part[blockIdx.x] = s;
+  }
+}
+__global__ void seg_ce_direct_grad_kernel(const float* __restrict__ lg, const float* __restrict__ gt, int B, int h, int w, int S,
+                                          int K, const float* __restrict__ gout, float inv_n, float* __restrict__ g) {
+  const int H = h * S, W = w * S;
+  const long long npix = (long long)B * H * W;
+  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+  const float sc = *gout * inv_n;
+  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
+    const int x = (int)(p % W);
+    const int y = (int)((p / W) % H);
+    const long long b = p / ((long long)W * H);
+    const Taps4 t = taps_of(lg, b, h, w, K, tap_of(y, h, sy), tap_of(x, w, sx));
+    bool ok;
+    int tgt;
+    float zt;
+    const float lse = direct_lse(t, K, gt[p], &ok, &tgt, &zt);
+    for (int k = 0; k < K; ++k) g[p * K + k] = ok ? sc * (expf(t.at(k) - lse) - (k == tgt ? 1.f : 0.f)) : 0.f;
+  }
+}
+
+// ---- nn.AvgPool2d(7, stride 1, padding 3), padding counted: y = (sum of x over the 7x7 window clipped to the map) / 49 ----
+// One thread owns 4 channels of one column over a strip of POOL_ROWS rows: per input row it forms the 7-tap row sum
+// (7 16-byte reads, consecutive lanes on consecutive channels) and keeps the last 7 row sums in registers; every output is
+// the sum of those 7 in fixed order (no subtraction, so no drift along the strip).  The operator is symmetric: its own adjoint.
+constexpr int POOL_ROWS = 8;
+constexpr int POOL_GRID_CAP = 2048;
+__global__ void avgpool7_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C) {
+  const int CG = C / 4;
+  const int strips = (H + POOL_ROWS - 1) / POOL_ROWS;
+  const long long total = (long long)B * strips * W * CG;
+  for (long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (long long)gridDim.x * blockDim.x) {
+    long long r = o;
+    const int cg = (int)(r % CG); r /= CG;
+    const int j = (int)(r % W); r /= W;
+    const int s = (int)(r % strips); r /= strips;
+    const long long b = r;
+    const int r0 = s * POOL_ROWS, r1 = min(H, r0 + POOL_ROWS);
+    const int j0 = max(0, j - 3), j1 = min(W - 1, j + 3);
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 q0 = zero, q1 = zero, q2 = zero, q3 = zero, q4 = zero, q5 = zero, q6 = zero;
+    for (int ii = r0 - 3; ii < r1 + 3; ++ii) {
+      f32x4 hs = zero;
+      if (ii >= 0 && ii < H) {
+        const float* row = x + ((b * H + ii) * W) * (long long)C + 4 * cg;
+        for (int jj = j0; jj <= j1; ++jj) hs += ld4(row + (long long)jj * C);
+      }
+      q0 = q1, q1 = q2, q2 = q3, q3 = q4, q4 = q5, q5 = q6, q6 = hs;
+      const int i = ii - 3;
+      if (i >= r0) st4(y + ((b * H + i) * W + j) * (long long)C + 4 * cg, (((((q0 + q1) + q2) + q3) + q4) + q5 + q6) / 49.f);
+    }
   }
 }
 
@@ -501,8 +615,8 @@ extern "C" int munit_seg_ce_bwd(const float* logits, const int* labels, const fl
   hipLaunchKernelGGL(seg_ce_grad_kernel, dim3(grid_for(np)), dim3(NT), 0, st, logits, labels, mask, B, h, w, S, gout,
                      1.f / norm, g);
   MUNIT_CHECK_LAUNCH("seg_ce_grad");
-  hipLaunchKernelGGL(seg_up_adjoint_kernel, dim3(grid_for((long long)B * h * w * NCLS)), dim3(NT), 0, st, g, B, h, w, S,
-                     dlogits);
+  hipLaunchKernelGGL(seg_up_adjoint_kernel<NCLS>, dim3(grid_for((long long)B * h * w * NCLS)), dim3(NT), 0, st, g, B, h, w,
+                     S, NCLS, dlogits);
   MUNIT_CHECK_LAUNCH("seg_up_adjoint");
   return MUNIT_OK;
 }
@@ -554,7 +668,94 @@ extern "C" int munit_seg_ce_gt_bwd(const float* logits, const float* gt, const f
   hipLaunchKernelGGL(seg_ce_gt_grad_kernel, dim3(grid_for(np)), dim3(NT), 0, st, logits, gt, mask, B, h, w, S, gout,
                      1.f / norm, g);
   MUNIT_CHECK_LAUNCH("seg_ce_gt_grad");
-  hipLaunchKernelGGL(seg_up_adjoint_kernel, dim3(grid_for((long long)B * h * w * NCLS)), dim3(NT), 0, st, g, B, h, w, S,
+  hipLaunchKernelGGL(seg_up_adjoint_kernel<NCLS>, dim3(grid_for((long long)B * h * w * NCLS)), dim3(NT), 0, st, g, B, h, w,
+                     S, NCLS, dlogits);
+  MUNIT_CHECK_LAUNCH("seg_up_adjoint");
+  return MUNIT_OK;
+}
+
+// ---- trainable segmentation head (adaptation.sem_seg_lambda) ----
+namespace {
+int check_pool(const float* x, const float* y, int B, int H, int W, int C, const char* what) {
+  MUNIT_CHECK_ARG(x && y && x != y && B > 0 && H > 0 && W > 0 && C > 0, "%s: bad args", what);
+  MUNIT_CHECK_ARG(C % 4 == 0, "%s: C %% 4 == 0 required, got %d", what, C);
+  MUNIT_CHECK_ARG((long long)B * H * W * C < (1ll << 40), "%s: too large", what);
+  return MUNIT_OK;
+}
+void launch_pool(const float* x, float* y, int B, int H, int W, int C, hipStream_t st) {
+  const long long n = (long long)B * ((H + POOL_ROWS - 1) / POOL_ROWS) * W * (C / 4);
+  const unsigned nb = (unsigned)std::max<long long>(1, std::min<long long>((n + NT - 1) / NT, POOL_GRID_CAP));
+  hipLaunchKernelGGL(avgpool7_kernel, dim3(nb), dim3(NT), 0, st, x, y, B, H, W, C);
+}
+int check_direct(const float* lg, const float* gt, int B, int h, int w, int S, int K, const char* what) {
+  MUNIT_CHECK_ARG(lg && gt && B > 0 && h > 0 && w > 0, "%s: bad args", what);
+  MUNIT_CHECK_ARG(S == 1 || S == 2 || S == 4 || S == 8, "%s: scale must be 1, 2, 4 or 8, got %d", what, S);
+  MUNIT_CHECK_ARG(K >= 2 && K <= 32, "%s: 2..32 classes, got %d", what, K);
+  MUNIT_CHECK_ARG((long long)B * h * S * w * S * K < (1ll << 40), "%s: too large", what);
+  return MUNIT_OK;
+}
+}  // namespace
+
+extern "C" int munit_avgpool7_fwd(const float* x, float* y, int B, int H, int W, int C, munit_stream_t stream) {
+  int rc = check_pool(x, y, B, H, W, C, "avgpool7_fwd");
+  if (rc) return rc;
+  launch_pool(x, y, B, H, W, C, (hipStream_t)stream);
+  MUNIT_CHECK_LAUNCH("avgpool7_fwd");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_avgpool7_bwd(const float* dy, float* dx, int B, int H, int W, int C, munit_stream_t stream) {
+  int rc = check_pool(dy, dx, B, H, W, C, "avgpool7_bwd");
+  if (rc) return rc;
+  launch_pool(dy, dx, B, H, W, C, (hipStream_t)stream);      // symmetric windows: the operator is its own adjoint
+  MUNIT_CHECK_LAUNCH("avgpool7_bwd");
+  return MUNIT_OK;
+}
+
+extern "C" size_t munit_seg_ce_direct_workspace_bytes(int B, int h, int w, int S, int K) {
+  const long long np = head_pix(B, h, w, S);
+  const size_t part = align_up((size_t)grid_for(np) * sizeof(float), 256);
+  const size_t grad = align_up((size_t)np * K * sizeof(float), 256);
+  return std::max(part, grad);
+}
+
+extern "C" int munit_seg_ce_direct_fwd(const float* logits, const float* gt, int B, int h, int w, int S, int K, float norm,
+                                       float* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  int rc = check_direct(logits, gt, B, h, w, S, K, "seg_ce_direct_fwd");
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(out && ws && norm > 0.f, "seg_ce_direct_fwd: bad args");
+  const long long np = head_pix(B, h, w, S);
+  const unsigned nb = grid_for(np);
+  if (ws_bytes < (size_t)nb * sizeof(float)) {
+    munit_set_error("seg_ce_direct_fwd: workspace %zu < %zu", ws_bytes, (size_t)nb * sizeof(float));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* part = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(seg_ce_direct_fwd_kernel, dim3(nb), dim3(NT), 0, st, logits, gt, B, h, w, S, K, part);
+  MUNIT_CHECK_LAUNCH("seg_ce_direct_fwd");
+  hipLaunchKernelGGL(seg_ce_final_kernel, dim3(1), dim3(64), 0, st, part, (int)nb, 1.0 / (double)norm, out);
+  MUNIT_CHECK_LAUNCH("seg_ce_final");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_seg_ce_direct_bwd(const float* logits, const float* gt, int B, int h, int w, int S, int K, float norm,
+                                       const float* gout, float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  int rc = check_direct(logits, gt, B, h, w, S, K, "seg_ce_direct_bwd");
+  if (rc) return rc;
+  MUNIT_CHECK_ARG(gout && dlogits && ws && norm > 0.f, "seg_ce_direct_bwd: bad args");
+  const long long np = head_pix(B, h, w, S);
+  const size_t need = (size_t)np * K * sizeof(float);
+  if (ws_bytes < need) {
+    munit_set_error("seg_ce_direct_bwd: workspace %zu < %zu", ws_bytes, need);
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* g = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(seg_ce_direct_grad_kernel, dim3(grid_for(np)), dim3(NT), 0, st, logits, gt, B, h, w, S, K, gout,
+                     1.f / norm, g);
+  MUNIT_CHECK_LAUNCH("seg_ce_direct_grad");
+  hipLaunchKernelGGL(seg_up_adjoint_kernel<0>, dim3(grid_for((long long)B * h * w * K)), dim3(NT), 0, st, g, B, h, w, S, K,
                      dlogits);
   MUNIT_CHECK_LAUNCH("seg_up_adjoint");
   return MUNIT_OK;

@@ -1320,6 +1320,79 @@ def seg_cross_entropy_gt(logits, gt, mask=None, scale=8, norm=None):
     return _SegCEGT.apply(logits, gt, mask, int(scale), float(norm))
 
 
+class _SegCEDirect(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, logits, gt, scale, norm):
+        lib = _lib.load()
+        logits = nhwc(logits)
+        _require(logits, "segmentation-head logits")
+        b, k, h, w = logits.shape
+        _require(gt, "segmentation-head target")
+        if tuple(gt.shape) != (b, h * scale, w * scale) or not gt.is_contiguous():
+            raise RuntimeError("munit_amd.seg_cross_entropy_direct: the target must be contiguous float32 (%d, %d, %d), got %s"
+                               % (b, h * scale, w * scale, tuple(gt.shape)))
+        _same_device(logits, gt)
+        ws = workspace(lib.munit_seg_ce_direct_workspace_bytes(b, h, w, scale, k), logits.device)
+        out = torch.empty((), device=logits.device, dtype=torch.float32)
+        _lib.check(lib.munit_seg_ce_direct_fwd(_p(logits), _p(gt), b, h, w, scale, k, c_float(norm), _p(out), _p(ws),
+                                               ws.numel(), _stream()), "seg_ce_direct_fwd")
+        ctx.cfg = (scale, norm)
+        ctx.save_for_backward(logits, gt)
+        return out
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, gout):
+        lib = _lib.load()
+        logits, gt = ctx.saved_tensors
+        scale, norm = ctx.cfg
+        b, k, h, w = logits.shape
+        gout = gout.contiguous()
+        ws = workspace(lib.munit_seg_ce_direct_workspace_bytes(b, h, w, scale, k), logits.device)
+        dl = torch.empty_like(logits)
+        _lib.check(lib.munit_seg_ce_direct_bwd(_p(logits), _p(gt), b, h, w, scale, k, c_float(norm), _p(gout), _p(dl),
+                                               _p(ws), ws.numel(), _stream()), "seg_ce_direct_bwd")
+        return dl, None, None, None
+
+
+def seg_cross_entropy_direct(logits, gt, scale=4, norm=None):
+    """nn.CrossEntropyLoss of the bilinearly up-sampled K-class logits (B, K, h, w), K in 2..32, against gt (B, h*scale,
+    w*scale) float32 truncated like .type(torch.long) (trainer.py:1305-1317): no mask, no class merge.  Sum of the pixel
+    losses / norm (default: all pixels, i.e. the mean).  A label outside 0..K-1 makes the loss NaN (include/munit_hip.h)."""
+    if norm is None:
+        norm = gt.numel()
+    return _SegCEDirect.apply(logits, gt, int(scale), float(norm))
+
+
+class _AvgPool7(Function):
+    @staticmethod
+    @_guarded
+    def forward(ctx, x):
+        lib = _lib.load()
+        _require(x, "avgpool7 input")
+        x = nhwc(x)
+        b, c, h, w = x.shape
+        y = torch.empty_like(x)
+        _lib.check(lib.munit_avgpool7_fwd(_p(x), _p(y), b, h, w, c, _stream()), "avgpool7_fwd")
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        dy = nhwc(dy)
+        b, c, h, w = dy.shape
+        dx = torch.empty_like(dy)
+        _lib.check(lib.munit_avgpool7_bwd(_p(dy), _p(dx), b, h, w, c, _stream()), "avgpool7_bwd")
+        return dx
+
+
+def avgpool7(x):
+    """nn.AvgPool2d(7, stride=1, padding=3), padding counted (scripts/resnet.py): every window's divisor is 49."""
+    return _AvgPool7.apply(x)
+
+
 def seg_labels(logits, scale=8):
     """argmax over the 19 up-sampled logits, int32 (B, H, W) (first maximal class on ties)."""
     lib = _lib.load()

@@ -15,12 +15,16 @@ The arithmetic runs on the device through the C ABI (munit_amd/ops.py):
     phase form the backward-data kernels need.
 
 Images must be square with a side that is a multiple of 32 (the logits then split into 4 x 4 phases of even size).
+
+`SegmentationHead` is the trainable head of adaptation.sem_seg_lambda (scripts/trainer.py:203-223, 1286-1324): the
+checkpoint's layer4 with its BatchNorms unfolded and in training mode, the 7x7 average the reference keeps, and a fresh
+1x1 scoring layer of 10 classes, on a content code.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import networks, ops
 
 NUM_CLASSES = 19
 BN_EPS = 1e-5
@@ -168,6 +172,70 @@ def load_segmentation_model(ckpt_path, classes):
     for p in model.parameters():
         p.requires_grad_(False)
     return model
+
+
+HEAD_CLASSES = 10      # the simulator's classes (nn.Conv2d(512, 10, kernel_size=1), trainer.py:207)
+
+
+class AvgPool7(nn.Module):
+    """nn.AvgPool2d(7, padding=3, stride=1) of scripts/resnet.py: no parameters, the divisor is always 49."""
+
+    def forward(self, x):
+        return ops.avgpool7(x)
+
+
+class SegmentationHead(nn.Sequential):
+    """Sequential(layer4, avgpool, Conv2d(512, 10, 1)) (trainer.py:207-210) with the reference's state_dict keys:
+    0.{0,1,2}.conv1.weight, 0.*.bn{1,2}.*, 0.0.downsample.{0.weight,1.*}, 2.weight, 2.bias.  Every parameter trains; the
+    seven BatchNorms normalise with batch statistics and move their running statistics while the module is in training
+    mode (networks.BatchNorm2d).
+
+    forward(code): the (B, 256, h, w) content code is split into its 4 x 4 phases once (munit_space_to_batch, f = 4), on
+    which layer4's dilation-4 3x3 convolutions are undilated pad-1 ones; batch statistics do not depend on the layout.
+    The inverse re-layout, the 7x7 average and the scoring layer follow in the reference's order.  h and w must be
+    multiples of 4.  Returns the (B, 10, h, w) logits; the bilinear up-sample lives in ops.seg_cross_entropy_direct.
+    The ReLU sign patterns go to ops.DANN_SINK in call order (the blocks are the feature classifier's BasicBlock)."""
+
+    def __init__(self, num_classes=HEAD_CLASSES):
+        blocks = [networks.BasicBlock(256, 512), networks.BasicBlock(512, 512), networks.BasicBlock(512, 512)]
+        super().__init__(nn.Sequential(*blocks), AvgPool7(), networks.Conv2d(512, num_classes, 1))
+
+    @staticmethod
+    def check_code_hw(h, w):
+        if h % 4 or w % 4 or h < 4 or w < 4:
+            raise ValueError("munit_amd.SegmentationHead: a %dx%d content code does not split into 4 x 4 phases (layer4's "
+                             "dilation); both extents must be multiples of 4" % (h, w))
+
+    def forward(self, code):
+        x = ops.nhwc(code)
+        if x.dim() != 4 or x.shape[1] != 256:
+            raise ValueError("munit_amd.SegmentationHead: a (B, 256, h, w) content code expected, got %s" % (tuple(x.shape),))
+        self.check_code_hw(x.shape[2], x.shape[3])
+        x = ops.space_to_batch(x, 4)
+        for blk in self[0]:
+            x = blk(x)
+        x = ops.space_to_batch(x, 4, inverse=True)
+        return self[2](self[1](x))
+
+
+def load_segmentation_head(ckpt_path, num_classes=HEAD_CLASSES):
+    """trainer.py:203-214: the layer4 of the user's Resnet34_8s checkpoint (loaded strictly, with weights_only, as
+    load_segmentation_model does) under a scoring layer drawn from nn.Conv2d(512, 10, 1)'s distribution.  Trainable and
+    in training mode; stays on the host until moved."""
+    pretrained = load_segmentation_model(ckpt_path, NUM_CLASSES)
+    head = SegmentationHead(num_classes)
+    head[0].load_state_dict(pretrained.resnet34_8s.layer4.state_dict(), strict=True)
+    for p in head.parameters():
+        p.requires_grad_(True)
+    return head
+
+
+def seg_head_loss(head, c_a, c_b, target_a, target_b, scale):
+    """trainer.py:1303-1317: CE(up(head(c_a)), target_a) + CE(up(head(c_b)), target_b) -- two forwards of the head, a then
+    b, each with its own batch statistics.  targets: float32 (B, H, W) at the crop size."""
+    l_a = ops.seg_cross_entropy_direct(head(c_a), target_a, scale)
+    l_b = ops.seg_cross_entropy_direct(head(c_b), target_b, scale)
+    return ops.scalar_sum([l_a, l_b])
 
 
 def seg_loss(model, x_orig, x_trans, mask=None, gt=None):

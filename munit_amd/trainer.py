@@ -46,8 +46,17 @@ computes on the joined batch, and all ranks end every update with bitwise identi
 output classifiers have no batch statistics; their fooling term lands in the generator's flat gradient and needs no
 exchange of its own.
 
-The other aux losses (VGG, the a/b domain classifier of domain_adv_w, sem_seg_lambda) raise NotImplementedError when their
-weight is non-zero.
+The segmentation head (adaptation.sem_seg_lambda > 0 with a semantic_ckpt_path, trainer.py:203-223 and 1286-1324): the
+checkpoint's layer4, the 7x7 average and a fresh Conv2d(512, 10, 1) on the content codes (segmentation.SegmentationHead),
+trained by segmentation_head_update against the simulator's label maps under its own optimizer segmentation_opt -- two
+forwards of the head, a then b, each with its own batch statistics, the bilinear up-sample inside the cross-entropy kernel,
+the plain step().  The encoders run without a tape there: the reference back-propagates into them, but gen_update zeroes
+that gradient before any use.  fp32, Adam and one process only; update_learning_rate does not step scheduler_seg and
+save / resume do not carry the head, as in the reference.
+
+With that every live branch of scripts/train.py's loop runs here.  The two weights still refused, vgg_w and domain_adv_w,
+cannot run in the reference either (load_vgg16 raises unconditionally; the a/b domain classifier's loss builds a
+4-element target for any batch and save / resume read an attribute that does not exist).
 """
 import os
 import warnings
@@ -59,7 +68,7 @@ from torch.optim import Optimizer
 from . import ops
 from .networks import (AdaINGen, AdaINGen_double, ContentEncoder, InstanceNorm2d, MsImageDis, _ApplyRefreshesImages,
                        domainClassifier)
-from .segmentation import colorize, seg_loss
+from .segmentation import SegmentationHead, colorize, load_segmentation_head, seg_head_loss, seg_loss
 from .utils import get_model_list, get_scheduler, load_segmentation_model, normalize_config, weights_init
 
 
@@ -497,6 +506,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self._check_aux(hyperparameters)
         self._check_featda(hyperparameters, self.use_classifier_sr)
         self._check_outda(hyperparameters, self.use_output_classifier_sr)
+        self._check_seghead(hyperparameters, self.train_seg)
 
         if self.gen_state == 0:
             self.gen_a = AdaINGen(hyperparameters["input_dim_a"], hyperparameters["gen"])
@@ -570,6 +580,15 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self.output_classifier_sr_b.apply(weights_init("gaussian"))
             self.output_scheduler_sr = get_scheduler(self.output_classif_opt_sr, hyperparameters)
 
+        # segmentation head on the content codes (trainer.py:203-223): created after the initialisation above, so it keeps the
+        # checkpoint's weights; its own optimizer, a scheduler that update_learning_rate never steps, nothing in save / resume
+        if self.train_seg:
+            self.segmentation_head = load_segmentation_head(hyperparameters["semantic_ckpt_path"])
+            dann_params = list(self.segmentation_head.parameters())
+            self.segmentation_opt = optimizer([p for p in dann_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
+                                              weight_decay=hyperparameters["weight_decay"])
+            self.scheduler_seg = get_scheduler(self.segmentation_opt, hyperparameters)
+
         self._consts = {}
         # deferred discriminator exchange + step (data parallel, _defer_dis_step)
         self._dis_pending, self._dis_event, self._dis_waited = None, None, set()
@@ -590,8 +609,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             bad.append("semantic_w (without a semantic_ckpt_path)")
         if hp.get("domain_adv_w", 0) > 0:
             bad.append("domain_adv_w")
-        if hp["adaptation"].get("sem_seg_lambda", 0) > 0:
-            bad.append("adaptation.sem_seg_lambda")
+        if hp["adaptation"].get("sem_seg_lambda", 0) > 0 and not hp.get("semantic_ckpt_path"):
+            bad.append("adaptation.sem_seg_lambda (without a semantic_ckpt_path: the head starts from that checkpoint's layer4)")
         ocl = hp["adaptation"].get("output_classifier_lambda", 0) > 0
         oadv = hp["adaptation"].get("output_adv_lambda", 0) > 0
         if construct and oadv and not ocl:
@@ -602,8 +621,10 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                        "nothing reads: set both)")
         if bad:
             raise NotImplementedError(
-                "munit_amd covers the AdaINGen + MsImageDis training step only; set these weights to 0 "
-                "(they need external checkpoints / models outside the hot path): " + ", ".join(bad))
+                "munit_amd: set these weights to 0: " + ", ".join(bad) + ".  vgg_w and domain_adv_w cannot run in the "
+                "reference either (load_vgg16 raises unconditionally; the a/b domain classifier's loss builds a 4-element "
+                "target for any batch size); semantic_w and adaptation.sem_seg_lambda need the user's Resnet34_8s "
+                "checkpoint (semantic_ckpt_path)")
 
     @staticmethod
     def _check_featda(hp, built):
@@ -656,6 +677,38 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                                       % (keys, hp["optimizer"]))
 
     @staticmethod
+    def _check_seghead(hp, built, update=False):
+        """Refusals of adaptation.sem_seg_lambda, before any device work.  built: whether this trainer was constructed with
+        the weight (it then owns the head); update: the check of segmentation_head_update."""
+        if update and not built:
+            raise ValueError("munit_amd: segmentation_head_update needs a trainer constructed with "
+                             "adaptation.sem_seg_lambda > 0 (and a semantic_ckpt_path): the head is built under that weight")
+        if not built:
+            return
+        key = "adaptation.sem_seg_lambda"
+        if hp.get("precision", "f32") != "f32":
+            raise NotImplementedError("munit_amd: %s runs in fp32 only (precision %r)" % (key, hp["precision"]))
+        if "extra" in hp.get("optimizer", "adam"):
+            raise NotImplementedError("munit_amd: %s is not implemented for optimizer %r: the reference's update calls "
+                                      "step() without extrapolation(), on which its ExtraAdam raises" % (key, hp["optimizer"]))
+        if dp_size() > 1:
+            raise NotImplementedError("munit_amd: %s is not implemented for data-parallel training (world size %d), also "
+                                      "under adaptation.data_parallel: 1: the head's gradients are not exchanged and its batch "
+                                      "norms take their statistics from one rank's batch; spanning them over the ranks is a "
+                                      "later change" % (key, dp_size()))
+        h, w, n = hp["crop_image_height"], hp["crop_image_width"], hp["gen"]["n_downsample"]
+        if h != w:
+            raise ValueError("munit_amd: %s needs a square crop (the reference up-samples the head's output to "
+                             "(crop_image_height, crop_image_height)); got %dx%d" % (key, h, w))
+        if 2 ** n not in (1, 2, 4, 8):
+            raise ValueError("munit_amd: %s needs gen.n_downsample in 0..3 (the head kernel up-samples by 1, 2, 4 or 8); "
+                             "got %d" % (key, n))
+        if h % 2 ** n or (h >> n) % 4 or (w >> n) % 4:
+            raise ValueError("munit_amd: %s needs a content code whose extents are multiples of 4 (layer4's dilation-4 "
+                             "convolutions run on its 4 x 4 phases): crop %dx%d with gen.n_downsample %d gives %gx%g"
+                             % (key, h, w, n, h / 2 ** n, w / 2 ** n))
+
+    @staticmethod
     def _check_semantic(hp):
         if hp.get("precision", "f32") != "f32":
             raise NotImplementedError("munit_amd: semantic_w > 0 runs in fp32 only (precision %r)" % hp["precision"])
@@ -668,17 +721,17 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                              "1/8-resolution features split into 4 x 4 phases); got %d" % h)
 
     @staticmethod
-    def _check_semantic_gt(x_a, gt_a, gt_b):
+    def _check_semantic_gt(x_a, gt_a, gt_b, names=("semantic_gt_a", "semantic_gt_b")):
         """Argument checks of semantic_gt_a / semantic_gt_b (no device work): None when neither is given, else the two maps
-        viewed as (B, H, W)."""
+        viewed as (B, H, W).  names: what the caller calls the two maps (segmentation_head_update: target_a / target_b)."""
         if gt_a is None and gt_b is None:
             return None
         if gt_a is None or gt_b is None:
-            raise ValueError("munit_amd: semantic_gt_a and semantic_gt_b must be given together (got only semantic_gt_%s)"
-                             % ("b" if gt_a is None else "a"))
+            raise ValueError("munit_amd: %s and %s must be given together (got only %s)"
+                             % (names[0], names[1], names[1] if gt_a is None else names[0]))
         b, _, h, w = x_a.shape
         out = []
-        for name, g in (("semantic_gt_a", gt_a), ("semantic_gt_b", gt_b)):
+        for name, g in zip(names, (gt_a, gt_b)):
             if not torch.is_tensor(g) or g.is_complex() or g.dtype == torch.bool:
                 raise ValueError("munit_amd: %s must be a tensor of a real dtype, got %s"
                                  % (name, g.dtype if torch.is_tensor(g) else type(g)))
@@ -728,6 +781,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self.classif_opt_sr.bind(device)
         if self.use_output_classifier_sr:
             self.output_classif_opt_sr.bind(device)
+        if self.train_seg:
+            self.segmentation_opt.bind(device)
         self._consts = {}
         # flat-gradient ranges of the decoders and MLPs (final before the first encodes' backward: GradExchange)
         gens = [self.gen] if self.gen_state == 1 else [self.gen_a, self.gen_b]
@@ -781,6 +836,13 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self.output_classif_opt_sr.extrapolation()
         else:
             self.output_classif_opt_sr.step()
+
+    def segmentation_opt_step(self):
+        """trainer.py:270-277.  Exists as in the reference, whose update does not call it either."""
+        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
+            self.segmentation_opt.extrapolation()
+        else:
+            self.segmentation_opt.step()
 
     # ---- criteria (trainer.py:279-305) ------------------------------------------------
     def recon_criterion(self, input, target):
@@ -874,6 +936,39 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.output_classif_opt_sr.step()
         if comet_exp is not None and self.iterations % 100 == 0:
             comet_exp.log_metric("loss_output_classifier_sr", (lam * self.loss_output_classifier_sr_update).cpu(), step=step)
+
+    # ---- segmentation head on the content codes (trainer.py:1286-1324) --------------------
+    def segmentation_head_update(self, x_a, x_b, target_a, target_b, lamb, comet_exp=None):
+        """trainer.py:1286-1324: (CE(up(head(c_a)), target_a) + CE(up(head(c_b)), target_b)) * lamb, then the optimizer's plain
+        step() (never extrapolation()).  Only the content encoders run, without a tape: the gradient the reference sends into
+        the encoders is zeroed by the next gen_update before anything reads it.  targets: (B, 1, H, W) or (B, H, W) label maps
+        of the simulator's 10 classes at the crop size, on the images' device."""
+        ops.set_compute(self.precision)
+        self._check_seghead(self.hyperparameters, self.train_seg, update=True)
+        dev = x_a.device
+        b, _, h, w = x_a.shape
+        if (h, w) != (self.newsize, self.newsize) or x_b.shape != x_a.shape:
+            raise ValueError("munit_amd: segmentation_head_update needs both images at the crop size %dx%d (the head's output "
+                             "is up-sampled to it), got %s and %s" % (self.newsize, self.newsize, tuple(x_a.shape), tuple(x_b.shape)))
+        if target_a is None or target_b is None:
+            raise ValueError("munit_amd: segmentation_head_update needs both label maps (target_a and target_b)")
+        gts = self._check_semantic_gt(x_a, target_a, target_b, ("target_a", "target_b"))
+        for name, g in zip(("target_a", "target_b"), gts):
+            if g.device != dev:
+                raise ValueError("munit_amd: %s must live on the images' device %s, got %s" % (name, dev, g.device))
+        gt = self._gt_to_device(gts, dev)
+        scale = 2 ** self.hyperparameters["gen"]["n_downsample"]
+        self.segmentation_opt.zero_grad()
+        x_a, x_b = ops.nhwc(x_a), ops.nhwc(x_b)
+        with torch.no_grad():
+            c_a = self._content_enc(1)(x_a)
+            c_b = self._content_enc(2)(x_b)
+        loss = seg_head_loss(self.segmentation_head, c_a.detach(), c_b.detach(), gt[:b], gt[b:], scale)
+        self.loss_semantic_head = ops.weighted_sum([loss.detach()], [lamb])      # the weighted loss, as the reference logs it
+        torch.autograd.backward([loss], [self._const(lamb, dev)])
+        ops.join_side_streams()
+        self.segmentation_opt.step()
+        self._log(comet_exp, ["loss_semantic_head"])
 
     # ---- generator dispatch -----------------------------------------------------------
     def _enc(self, x, k):
