@@ -1,6 +1,6 @@
 """Minimal end-to-end training loop on munit_amd: the loaders of munit_amd.data feeding MUNIT_Trainer, in the
 shape of the reference's scripts/train.py:157-330 (dis_update / gen_update cadence of `ratio_disc_gen`,
-update_learning_rate first, periodic save).  Control plane only -- no comet, FID or image dumps.
+update_learning_rate first, periodic sample grids, periodic save).  Control plane only -- no comet and no FID.
 
   python examples/train_loop.py --config configs.yaml --data-root /path/with/trainA,trainB,testA,testB [--iters N]
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_loop.py ...      (data parallel, RCCL)
@@ -17,6 +17,15 @@ Output-level adaptation (adaptation.output_classifier_lambda and output_adv_lamb
 output_domain_classifier_sr_update runs on (x_a, x_as, x_b, x_bs), scripts/train.py:209-223, with the synthetic batch of
 that iteration (the one its synthetic-pair step uses too, when both fall on the same iteration).  A trainer that owns these
 classifiers cannot train without synthetic images: without the lists (or `synth_pairs`) the loop stops at start-up.
+
+With --output-path the folder gets the reference's layout (munit_amd.utils.prepare_sub_folder): checkpoints/ and images/.  The
+sample grids of scripts/train.py:285-320 are written into images/: `display_size` samples of each train loader (and of each
+test loader -- testA / testB under the data root, or the config's data_folder_test_* / data_list_test_* -- when those exist)
+are taken once before the first iteration; every `image_save_iter` iterations gen_a2b_ / gen_b2a_test_%08d.jpg and
+..._train_%08d.jpg are written, every `image_display_iter` iterations ..._train_current.jpg (write_samples; a key that is
+absent or 0 writes nothing).  All ranks sample -- sample() draws styles from the host RNG -- and rank 0 writes.  Checkpoints
+(--save-every) go to checkpoints/ unless --output names another folder; --output alone keeps its meaning, a bare checkpoint
+folder and no grids.
 """
 import argparse
 import os
@@ -100,6 +109,59 @@ def run_iteration(trainer, config, it, real_batch, synth_pairs, on_call=None):
         call("segmentation_head_update", x_as, x_bs, sem_a, sem_b, ad["sem_seg_lambda"], None)
 
 
+def display_batch(loader, display_size):
+    """scripts/train.py:132-143: the first `display_size` samples of the loader's dataset as one batch (the image of a
+    loader that yields (image, mask) pairs)."""
+    items = [loader.dataset[i] for i in range(display_size)]
+    return torch.stack([t[0] if isinstance(t, tuple) else t for t in items])
+
+
+def held_out_loaders(config, root, batch, new_size, num_workers):
+    """The two test loaders as munit_amd.data.get_all_data_loaders builds them (new_size is the crop as well, no shuffle,
+    no flip) when their files exist, else None."""
+    from munit_amd import data as D
+    out = []
+    for dom in ("a", "b"):
+        folder = os.path.join(root, "test" + dom.upper()) if root else None
+        flist, froot = config.get("data_list_test_" + dom), config.get("data_folder_test_" + dom)
+        if folder and os.path.isdir(folder) and D.make_dataset(folder):
+            out.append(D.get_data_loader_folder(folder, batch, False, new_size, new_size, new_size, num_workers, seed=4))
+        elif isinstance(flist, str) and isinstance(froot, str) and os.path.isfile(flist):
+            out.append(D.get_data_loader_list(froot, flist, batch, False, new_size, new_size, new_size, num_workers, seed=4))
+        else:
+            return None
+    return out
+
+
+def write_samples(trainer, config, it, displays, image_directory, rank=0, write=None, comet_exp=None):
+    """The sample grids of iteration `it` (counted from 0), scripts/train.py:285-320: when (it + 1) % image_save_iter == 0
+    the test pair and the train pair are sampled, in that order, and written as test_%08d and train_%08d; when
+    (it + 1) % image_display_iter == 0 the train pair is sampled again and written as train_current.  A cadence key that
+    is absent or 0 writes nothing.  displays: (train_a, train_b, test_a, test_b) display batches, the test pair None when
+    there are no test images (then only the train grids are written).  Every rank samples -- sample() draws its random
+    styles from the host RNG, which has to advance alike on all ranks -- and rank 0 alone calls
+    write(outputs, display_size, image_directory, postfix, comet_exp) (default: munit_amd.utils.write_2images)."""
+    if write is None:
+        from munit_amd.utils import write_2images as write
+    train_a, train_b, test_a, test_b = displays
+    n = config["display_size"]
+    save_every = int(config.get("image_save_iter") or 0)
+    show_every = int(config.get("image_display_iter") or 0)
+    if save_every > 0 and (it + 1) % save_every == 0:
+        with torch.no_grad():
+            test_outputs = trainer.sample(test_a, test_b) if test_a is not None else None
+            train_outputs = trainer.sample(train_a, train_b)
+        if rank == 0:
+            if test_outputs is not None:
+                write(test_outputs, n, image_directory, "test_%08d" % (it + 1), comet_exp)
+            write(train_outputs, n, image_directory, "train_%08d" % (it + 1), comet_exp)
+    if show_every > 0 and (it + 1) % show_every == 0:
+        with torch.no_grad():
+            outputs = trainer.sample(train_a, train_b)
+        if rank == 0:
+            write(outputs, n, image_directory, "train_current", comet_exp)
+
+
 def main(argv=None, synth_pairs=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
@@ -109,7 +171,9 @@ def main(argv=None, synth_pairs=None):
     ap.add_argument("--synth-list-a"), ap.add_argument("--synth-list-b"), ap.add_argument("--synth-mask-list")
     ap.add_argument("--seg-list-a"), ap.add_argument("--seg-list-b")
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--output", default=None, help="checkpoint directory")
+    ap.add_argument("--output", default=None, help="checkpoint directory (default with --output-path: its checkpoints/)")
+    ap.add_argument("--output-path", default=None, help="run folder in the reference's layout: checkpoints/ and images/ "
+                    "are made inside it, and the sample grids are written")
     ap.add_argument("--save-every", type=int, default=0)
     args = ap.parse_args(argv)
 
@@ -122,7 +186,7 @@ def main(argv=None, synth_pairs=None):
         dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
     dev = torch.device("cuda", local_rank)
 
-    from munit_amd.utils import get_config
+    from munit_amd.utils import get_config, prepare_sub_folder
     from munit_amd.trainer import MUNIT_Trainer
     from munit_amd import data as D
 
@@ -151,8 +215,18 @@ def main(argv=None, synth_pairs=None):
                          "images: give the synthetic lists (%s, or the config keys %s)"
                          % (", ".join("--" + a.replace("_", "-") for a, _ in SYNTH_LISTS), ", ".join(k for _, k in SYNTH_LISTS)))
 
+    checkpoint_directory, image_directory, displays = args.output, None, None
     if args.output and local_rank == 0:
-        os.makedirs(args.output, exist_ok=True)   # the reference's prepare_sub_folder (utils.py:817-834)
+        os.makedirs(args.output, exist_ok=True)
+    if args.output_path:
+        if local_rank == 0:
+            sub, image_directory = prepare_sub_folder(args.output_path)
+            checkpoint_directory = checkpoint_directory or sub
+        # scripts/train.py:132-143, on every rank: dataset[i] draws from the loader's RNG, and the ranks' draws stay alike
+        n = config["display_size"]
+        tests = held_out_loaders(config, None if args.mask_list_a else (args.data_root or config.get("data_root")), b, ns, nw)
+        displays = (display_batch(loader_a, n), display_batch(loader_b, n)) + \
+            ((display_batch(tests[0], n), display_batch(tests[1], n)) if tests else (None, None))
     it, t0 = 0, time.perf_counter()
     while it < args.iters:
         for batch_a, batch_b in zip(loader_a, loader_b):
@@ -160,9 +234,11 @@ def main(argv=None, synth_pairs=None):
             if m_a is None and config.get("recon_mask", 0) == 1:      # no mask files: everything counts
                 m_a, m_b = torch.ones_like(x_a[:, :1]), torch.ones_like(x_b[:, :1])
             run_iteration(trainer, config, it, (x_a, x_b, m_a, m_b), synth_pairs)
+            if displays is not None:
+                write_samples(trainer, config, it, displays, image_directory, local_rank)
             it += 1
-            if args.output and args.save_every and it % args.save_every == 0 and local_rank == 0:
-                trainer.save(args.output, it - 1)      # file names carry iterations + 1 (trainer.py:1337-1344)
+            if checkpoint_directory and args.save_every and it % args.save_every == 0 and local_rank == 0:
+                trainer.save(checkpoint_directory, it - 1)      # file names carry iterations + 1 (trainer.py:1337-1344)
             if it >= args.iters:
                 break
     torch.cuda.synchronize()

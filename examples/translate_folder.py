@@ -1,7 +1,7 @@
 """Folder translation with a trained generator -- the reference's scripts/test.py:86-129 on munit_amd:
 style image -> gen.encode(., 2) style code; every content image -> gen.encode(., 1) content; gen.decode(c, s, 2);
 outputs saved as JPEG after the same (x + 1) / 2 de-normalisation and per-image min-max scaling that
-torchvision.utils.save_image(normalize=True) applies.  The Resize + ToTensor + Normalize transform runs on the GPU
+torchvision.utils.save_image(normalize=True) applies, computed by the grid kernel (munit_amd.utils.write_image).  The Resize + ToTensor + Normalize transform runs on the GPU
 (munit_amd.data, bit-identical to PIL + torchvision).
 
   python examples/translate_folder.py --config cfg.yaml --checkpoint outputs/checkpoints/gen_00100000.pt \
@@ -26,13 +26,10 @@ def load_image(path, new_size, dev):
 
 
 def save_image(x, path):
-    """vutils.save_image(x, padding=0, normalize=True) for a single image: min-max to [0, 1], x255 + 0.5, clamp."""
-    from PIL import Image
-    x = x[0].float()
-    lo, hi = float(x.min()), float(x.max())
-    x = (x - lo) / max(hi - lo, 1e-5)
-    arr = x.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to("cpu", torch.uint8).numpy()
-    Image.fromarray(arr).save(path)
+    """vutils.save_image((x + 1) / 2.0, path, padding=0, normalize=True) of scripts/test.py:123-129 for a single image:
+    the de-normalisation, the min-max scaling to [0, 1] and x255 + 0.5 in one device pass (munit_amd.utils.write_image)."""
+    from munit_amd.utils import write_image
+    write_image(x, path, 1.0, 0.5)
 
 
 def main(argv=None, keep=None):
@@ -75,13 +72,13 @@ def main(argv=None, keep=None):
         for j, path in enumerate(sorted(D.make_dataset(args.input_folder))):
             x_a = load_image(path, new_size, dev)
             if args.save_input:
-                save_image((x_a + 1) / 2.0, os.path.join(args.output_folder, "input{:03d}.jpg".format(j)))
+                save_image(x_a, os.path.join(args.output_folder, "input{:03d}.jpg".format(j)))
             c_a, _ = enc(x_a, 1)
             x_ab = dec(c_a, s_b, 2)
             if keep is not None:
                 keep.append(x_ab.detach().float().cpu())
             out = os.path.join(args.output_folder, "output{:03d}.jpg".format(j))
-            save_image((x_ab + 1) / 2.0, out)
+            save_image(x_ab, out)
             outs.append(out)
     return outs
 

@@ -368,6 +368,32 @@ int munit_label_preprocess(const unsigned char* pool, const munit_image_desc* de
                            int out_w, float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Sample grids (scripts/utils.py:768-814, __write_images): torchvision's make_grid(nrow, padding=0, normalize=True)
+ * followed by save_image's conversion to bytes, for a list of image batches, in two launches and without a host
+ * synchronisation.  `src` is a HOST array of nsrc (1..16) descriptors, handed to the kernels by value; source s is n >= 1
+ * fp32 images of H x W with 1 or 3 channels, planar or interleaved, starting at any 4-byte boundary.
+ *   v   = (x + pre_add) * pre_mul                       (two fp32 roundings; 0, 1 is the identity)
+ *   lo, hi = minimum, maximum of v over the sum-of-n images named (a one-channel image counts three times)
+ *   d   = max(hi - lo, 1e-5), t = (v - lo) * (1 / d)    (hi - lo in double, rounded to fp32 once: python floats; the
+ *                                                        reciprocal is what torch's device kernel for tensor / scalar takes)
+ *   out = (uint8) clamp(t * 255 + 0.5, 0, 255), truncating; `* 255` and `+ 0.5` rounded separately
+ * Tiling: nmaps = sum n images in list order, row-major, xmaps = min(nrow, nmaps) per row, ymaps = ceil(nmaps / xmaps)
+ * rows; cells past nmaps are 0.  out: [ymaps * H][xmaps * W][3] bytes, every one written; at most 2^31 - 1 of them.
+ * The workspace holds the per-block (min, max) partials of the range pass; the pack pass reduces them (no atomics: two
+ * calls are bitwise equal).  A NaN input gives no defined picture; nothing outside the stated tensors is touched.
+ * ------------------------------------------------------------------------------------ */
+typedef struct {
+  const float* data;  /* device pointer */
+  int n;              /* images */
+  int channels;       /* 1 or 3 */
+  int layout;         /* 0 planar [n][C][H][W], 1 interleaved [n][H][W][C] */
+} munit_grid_src;
+
+size_t munit_image_grid_workspace_bytes(int nsrc, int H, int W, int nrow);
+int munit_image_grid_u8(const munit_grid_src* src, int nsrc, int H, int W, int nrow, float pre_add, float pre_mul,
+                        unsigned char* out, void* ws, size_t ws_bytes, munit_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Semantic-consistency loss (scripts/trainer.py:706-771): the frozen Resnet34_8s segmentation network
  * (scripts/utils.py:933-983, scripts/resnet.py) and its head.  The convolutions run through munit_conv2d_* with
  * BatchNorm folded into their weights; the dilated 3x3 layers of layer3 / layer4 run undilated on the phase images

@@ -39,6 +39,11 @@ class ImageDesc(Structure):
                 ("crop_i", c_int), ("crop_j", c_int), ("flip", c_int), ("kind", c_int)]
 
 
+class GridSrc(Structure):
+    """munit_grid_src."""
+    _fields_ = [("data", c_void_p), ("n", c_int), ("channels", c_int), ("layout", c_int)]
+
+
 _P = c_void_p  # device pointers travel as integers
 _DESC = POINTER(ConvDesc)
 
@@ -116,6 +121,8 @@ SIGNATURES = {
     "munit_mask_preprocess": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "munit_label_preprocess_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "munit_label_preprocess": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "munit_image_grid_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "munit_image_grid_u8": (c_int, [POINTER(GridSrc), c_int, c_int, c_int, c_int, c_float, c_float, _P, _P, c_size_t, _P]),
     "munit_seg_input_fwd": (c_int, [_P, _P, c_size_t, _P]),
     "munit_seg_input_bwd": (c_int, [_P, _P, c_size_t, _P]),
     "munit_space_to_batch": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

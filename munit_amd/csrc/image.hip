@@ -11,6 +11,10 @@
 // result is bit-identical to Image.resize.  Masks use the NEAREST path (ImagingScaleAffine: source
 // index tables from a running double accumulator); so do the mask and the label maps of the synthetic
 // pairs (MyDatasetSynthetic.transform, utils.py:483-553), whose chain differs: munit_label_preprocess.
+//
+// The way out is here too: munit_image_grid_u8 turns a list of float image batches into the uint8 sample grid that the
+// reference's write_2images saves (utils.py:768-814: torchvision's make_grid(normalize=True, padding=0) and save_image's
+// x255 + 0.5), byte for byte what torch's op sequence gives on the device.
 #include "common.h"
 
 namespace {
@@ -265,6 +269,112 @@ __global__ void label_finish_kernel(const munit_image_desc* __restrict__ descs, 
 
 int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 8192); }
 
+// ---- sample grids: make_grid(normalize=True, padding=0) + save_image's byte conversion (munit_image_grid_u8) -------------
+constexpr int GRID_MAX_SRC = 16;
+constexpr int GRID_NT = 256;
+constexpr int GRID_RANGE_BLOCKS = 512;    // most (min, max) partials the range pass writes: the size of the workspace
+constexpr int GRID_PACK_BLOCKS = 2048;
+constexpr long long GRID_MAX_OUT_BYTES = 2147483647LL;   // pixel and element indices of this file fit an int
+
+// The sources, handed to both kernels by value.  Source s owns the elements [elems[s], elems[s + 1]) of the range pass and
+// the grid cells [first[s], first[s + 1]).
+struct GridArgs {
+  const float* data[GRID_MAX_SRC];
+  long long elems[GRID_MAX_SRC + 1];
+  int first[GRID_MAX_SRC + 1];
+  int channels[GRID_MAX_SRC];
+  int layout[GRID_MAX_SRC];
+  int nsrc;
+};
+
+// minimum and maximum over the 256 threads of a block, in every thread (fminf / fmaxf skip a NaN operand)
+__device__ inline void block_min_max256(float& lo, float& hi, float* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, off, 64));
+    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    red[wave] = lo;
+    red[4 + wave] = hi;
+  }
+  __syncthreads();
+  lo = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+  hi = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+}
+
+// Range pass: partial[2 b], partial[2 b + 1] = minimum and maximum of (x + pre_add) * pre_mul over the elements block b
+// visits.  A source may start at any 4-byte boundary, so every load is a scalar one.  The channel of a one-channel source
+// is read once: repeating it three times changes neither extreme.
+__global__ void __launch_bounds__(GRID_NT)
+grid_range_kernel(GridArgs a, float pre_add, float pre_mul, float* __restrict__ partial) {
+  __shared__ float red[8];
+  const long long total = a.elems[a.nsrc];
+  float lo = INFINITY, hi = -INFINITY;
+  int s = 0;
+  for (long long i = (long long)blockIdx.x * GRID_NT + threadIdx.x; i < total; i += (long long)gridDim.x * GRID_NT) {
+    while (i >= a.elems[s + 1]) ++s;            // i only grows, and i < total = elems[nsrc] ends the walk
+    const float v = (a.data[s][i - a.elems[s]] + pre_add) * pre_mul;
+    lo = fminf(lo, v);
+    hi = fmaxf(hi, v);
+  }
+  block_min_max256(lo, hi, red);
+  if (threadIdx.x == 0) {
+    partial[2 * blockIdx.x] = lo;
+    partial[2 * blockIdx.x + 1] = hi;
+  }
+}
+
+// Pack pass: every block reduces the partials to (lo, hi) itself -- minimum and maximum do not depend on the order -- and
+// writes whole pixels of the [ymaps * H][xmaps * W][3] byte grid, three byte stores each (W * 3 is in general no multiple
+// of 4 and `out` has no alignment to speak of, so nothing wider is attempted).  Cells past nmaps are written as 0.
+//   t = (v - lo) * (1 / d),  d = max(hi - lo, 1e-5): torch's device kernel for `tensor / python_float` multiplies by the
+//   fp32 reciprocal of the scalar; hi - lo is formed in double and rounded once, as the reference's python floats are.
+__global__ void __launch_bounds__(GRID_NT)
+grid_pack_kernel(GridArgs a, int H, int W, int xmaps, int ymaps, int nmaps, float pre_add, float pre_mul,
+                 const float* __restrict__ partial, int nparts, unsigned char* __restrict__ out) {
+  __shared__ float red[8];
+  float lo = INFINITY, hi = -INFINITY;
+  for (int i = threadIdx.x; i < nparts; i += GRID_NT) {
+    lo = fminf(lo, partial[2 * i]);
+    hi = fmaxf(hi, partial[2 * i + 1]);
+  }
+  block_min_max256(lo, hi, red);
+  const float d = (float)fmax((double)hi - (double)lo, 1e-5);
+  const float r = __fdiv_rn(1.0f, d);
+  const long long row = (long long)xmaps * W;
+  const long long total = (long long)ymaps * H * row;
+  for (long long p = (long long)blockIdx.x * GRID_NT + threadIdx.x; p < total; p += (long long)gridDim.x * GRID_NT) {
+    const int y = (int)(p / row), x = (int)(p - (long long)y * row);
+    const int cy = y / H, iy = y - cy * H, cx = x / W, ix = x - cx * W;
+    const int m = cy * xmaps + cx;
+    unsigned char px[3] = {0, 0, 0};
+    if (m < nmaps) {
+      int s = 0;
+      while (m >= a.first[s + 1]) ++s;          // m < nmaps = first[nsrc] ends the walk
+      const int C = a.channels[s];
+      const long long img = m - a.first[s];
+      const float* __restrict__ src = a.data[s];
+      const long long hw = (long long)H * W;
+      const long long pos = (long long)iy * W + ix;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int cs = C == 3 ? c : 0;
+        const long long idx = a.layout[s] == 0 ? (img * C + cs) * hw + pos : (img * hw + pos) * C + cs;
+        const float v = (src[idx] + pre_add) * pre_mul;
+        const float t = (v - lo) * r;
+        const float q = fminf(fmaxf(t * 255.0f + 0.5f, 0.0f), 255.0f);
+        px[c] = (unsigned char)(int)q;
+      }
+    }
+    unsigned char* o = out + p * 3;
+    o[0] = px[0];
+    o[1] = px[1];
+    o[2] = px[2];
+  }
+}
+
 }  // namespace
 
 extern "C" int munit_image_ksize(int src_size, int rs_size) {
@@ -358,5 +468,58 @@ extern "C" int munit_label_preprocess(const unsigned char* pool, const munit_ima
   hipLaunchKernelGGL(label_finish_kernel, dim3(grid_for(total)), dim3(256), 0, st, descs, out, vmax, N,
                      (long long)out_h * out_w);
   MUNIT_CHECK_LAUNCH("label_finish");
+  return MUNIT_OK;
+}
+
+extern "C" size_t munit_image_grid_workspace_bytes(int nsrc, int H, int W, int nrow) {
+  if (nsrc < 1 || nsrc > GRID_MAX_SRC || H < 1 || W < 1 || nrow < 1) return 0;
+  return align_up((size_t)GRID_RANGE_BLOCKS * 2 * sizeof(float), 256);
+}
+
+extern "C" int munit_image_grid_u8(const munit_grid_src* src, int nsrc, int H, int W, int nrow, float pre_add, float pre_mul,
+                                   unsigned char* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(src && out && ws, "image_grid: null pointer");
+  MUNIT_CHECK_ARG(nsrc >= 1 && nsrc <= GRID_MAX_SRC, "image_grid: nsrc must be 1..%d, got %d", GRID_MAX_SRC, nsrc);
+  MUNIT_CHECK_ARG(H > 0 && W > 0 && nrow > 0, "image_grid: bad shape");
+  GridArgs a;
+  a.nsrc = nsrc;
+  a.elems[0] = 0;
+  a.first[0] = 0;
+  const long long hw = (long long)H * W;
+  long long nmaps = 0;
+  for (int s = 0; s < nsrc; ++s) {
+    MUNIT_CHECK_ARG(src[s].data, "image_grid: source %d is null", s);
+    MUNIT_CHECK_ARG(src[s].n >= 1, "image_grid: source %d holds %d images", s, src[s].n);
+    MUNIT_CHECK_ARG(src[s].channels == 1 || src[s].channels == 3, "image_grid: source %d has %d channels (1 or 3)", s,
+                    src[s].channels);
+    MUNIT_CHECK_ARG(src[s].layout == 0 || src[s].layout == 1, "image_grid: source %d has layout %d (0 planar, 1 interleaved)",
+                    s, src[s].layout);
+    nmaps += src[s].n;
+    // every cell is part of the output, so this bounds nmaps, the element counts and the products below as well
+    MUNIT_CHECK_ARG(nmaps <= GRID_MAX_OUT_BYTES / 3 / hw, "image_grid: output above %lld bytes", GRID_MAX_OUT_BYTES);
+    a.data[s] = src[s].data;
+    a.channels[s] = src[s].channels;
+    a.layout[s] = src[s].layout;
+    a.elems[s + 1] = a.elems[s] + (long long)src[s].n * src[s].channels * hw;
+    a.first[s + 1] = (int)nmaps;
+  }
+  const int xmaps = (int)std::min<long long>(nrow, nmaps);
+  const int ymaps = (int)((nmaps + xmaps - 1) / xmaps);
+  MUNIT_CHECK_ARG((long long)ymaps * xmaps <= GRID_MAX_OUT_BYTES / 3 / hw, "image_grid: output above %lld bytes",
+                  GRID_MAX_OUT_BYTES);
+  if (ws_bytes < munit_image_grid_workspace_bytes(nsrc, H, W, nrow)) {
+    munit_set_error("image_grid: workspace %zu < %zu", ws_bytes, munit_image_grid_workspace_bytes(nsrc, H, W, nrow));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* partial = reinterpret_cast<float*>(ws);
+  const int nparts = (int)std::min<long long>((a.elems[nsrc] + GRID_NT - 1) / GRID_NT, GRID_RANGE_BLOCKS);
+  hipLaunchKernelGGL(grid_range_kernel, dim3(nparts), dim3(GRID_NT), 0, st, a, pre_add, pre_mul, partial);
+  MUNIT_CHECK_LAUNCH("grid_range");
+  const long long pixels = (long long)ymaps * xmaps * hw;
+  const int blocks = (int)std::min<long long>((pixels + GRID_NT - 1) / GRID_NT, GRID_PACK_BLOCKS);
+  hipLaunchKernelGGL(grid_pack_kernel, dim3(blocks), dim3(GRID_NT), 0, st, a, H, W, xmaps, ymaps, (int)nmaps, pre_add,
+                     pre_mul, partial, nparts, out);
+  MUNIT_CHECK_LAUNCH("grid_pack");
   return MUNIT_OK;
 }

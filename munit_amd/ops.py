@@ -1410,6 +1410,58 @@ def seg_labels(logits, scale=8):
 
 
 # ------------------------------------------------------------------------------------------
+# sample grids (include/munit_hip.h: munit_image_grid_u8; image.hip)
+# ------------------------------------------------------------------------------------------
+def _grid_layout(t):
+    """0 for planar-dense (B, C, H, W) memory, 1 for interleaved-dense (channels_last), None for anything else.  Axes of
+    size 1 have no stride to speak of; a one-channel tensor is both and counts as planar."""
+    b, c, h, w = t.shape
+    for layout, want in ((0, (c * h * w, h * w, w, 1)), (1, (h * w * c, 1, w * c, c))):
+        if all(size == 1 or st == ws for size, st, ws in zip(t.shape, t.stride(), want)):
+            return layout
+    return None
+
+
+def image_grid(tensors, nrow, pre_add=0.0, pre_mul=1.0):
+    """torchvision's make_grid(cat of t[:nrow].expand(-1, 3, -1, -1), nrow=nrow, padding=0, normalize=True) of
+    (t + pre_add) * pre_mul, followed by save_image's conversion to bytes (scripts/utils.py:768-784): a uint8 tensor
+    (ymaps * H, xmaps * W, 3) on the tensors' device, what PIL.Image.fromarray takes.  tensors: 1..16 fp32 HIP tensors
+    (B, 1 | 3, H, W) of one H x W, planar- or interleaved-dense in memory (read from the strides; anything else is refused,
+    not copied); each contributes its first min(B, nrow) images.  One munit_image_grid_u8 call, no host synchronisation."""
+    lib = _lib.load()
+    tensors = list(tensors)
+    nrow = int(nrow)
+    if not 1 <= len(tensors) <= 16:
+        raise RuntimeError("munit_amd.image_grid: 1..16 tensors per call, got %d" % len(tensors))
+    if nrow < 1:
+        raise RuntimeError("munit_amd.image_grid: nrow must be positive, got %d" % nrow)
+    src = (_lib.GridSrc * len(tensors))()
+    for i, t in enumerate(tensors):
+        _require(t, "image_grid tensor %d" % i)
+        if t.dim() != 4 or t.shape[1] not in (1, 3) or t.shape[0] < 1:
+            raise RuntimeError("munit_amd.image_grid: tensor %d must be (B >= 1, 1 | 3, H, W), got %s" % (i, tuple(t.shape)))
+        if tuple(t.shape[2:]) != tuple(tensors[0].shape[2:]):
+            raise RuntimeError("munit_amd.image_grid: tensor %d is %d x %d, tensor 0 is %d x %d"
+                               % ((i,) + tuple(t.shape[2:]) + tuple(tensors[0].shape[2:])))
+        layout = _grid_layout(t)
+        if layout is None:
+            raise RuntimeError("munit_amd.image_grid: tensor %d (shape %s, strides %s) is neither planar- nor "
+                               "interleaved-dense in memory" % (i, tuple(t.shape), t.stride()))
+        src[i] = _lib.GridSrc(t.data_ptr(), min(t.shape[0], nrow), t.shape[1], layout)
+    _same_device(*tensors)
+    h, w = tensors[0].shape[2:]
+    nmaps = sum(s.n for s in src)
+    xmaps = min(nrow, nmaps)
+    ymaps = (nmaps + xmaps - 1) // xmaps
+    with _on(tensors[0]):
+        out = torch.empty((ymaps * h, xmaps * w, 3), dtype=torch.uint8, device=tensors[0].device)
+        ws = workspace(lib.munit_image_grid_workspace_bytes(len(tensors), h, w, nrow), out.device)
+        _lib.check(lib.munit_image_grid_u8(src, len(tensors), h, w, nrow, float(pre_add), float(pre_mul), _p(out), _p(ws),
+                                           ws.numel(), _stream()), "image_grid_u8")
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # feature classifier of adaptation.adv_lambda / dfeat_lambda (networks.domainClassifier; include/munit_hip.h, dann.hip)
 # ------------------------------------------------------------------------------------------
 class bn_world(object):

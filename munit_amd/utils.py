@@ -1,4 +1,5 @@
-"""Host-side helpers of the hot path: config, init, LR schedule (reference: scripts/utils.py)."""
+"""Host-side helpers of the hot path: config, init, LR schedule, sample grids and output folders (reference:
+scripts/utils.py)."""
 import math
 import os
 
@@ -114,3 +115,47 @@ def mapping(im):
     for grey, cls in LABEL_CLASSES.items():
         im[im == grey] = cls
     return im
+
+
+def _save_grid(tensors, nrow, path, pre_add=0.0, pre_mul=1.0):
+    """One ops.image_grid, one device-to-host copy, one PIL save with Pillow's defaults (what torchvision's save_image
+    does with the array)."""
+    from PIL import Image
+    from . import ops
+    grid = ops.image_grid(tensors, nrow, pre_add, pre_mul)
+    Image.fromarray(grid.cpu().numpy()).save(path)
+
+
+def write_2images(image_outputs, display_image_num, image_directory, postfix, comet_exp=None):
+    """utils.py:768-814: the first half of `image_outputs` (the tuple of MUNIT_Trainer.sample) as one grid into
+    gen_a2b_<postfix>.jpg, the second half into gen_b2a_<postfix>.jpg -- one row per tensor, its first
+    `display_image_num` images, one-channel tensors repeated over three channels, the whole grid min-max scaled
+    (make_grid(normalize=True)) on the device (ops.image_grid)."""
+    n = len(image_outputs)
+    names = ("%s/gen_a2b_%s.jpg" % (image_directory, postfix), "%s/gen_b2a_%s.jpg" % (image_directory, postfix))
+    _save_grid(image_outputs[0:n // 2], display_image_num, names[0])
+    _save_grid(image_outputs[n // 2:n], display_image_num, names[1])
+    if comet_exp is not None:
+        comet_exp.log_image(names[0])
+        comet_exp.log_image(names[1])
+
+
+def write_image(x, path, pre_add=0.0, pre_mul=1.0):
+    """vutils.save_image((x + pre_add) * pre_mul, path, padding=0, normalize=True) for one image (1, C, H, W)
+    (scripts/test.py:123-129 with pre_add, pre_mul = 1, 0.5)."""
+    if x.dim() != 4 or x.shape[0] != 1:
+        raise ValueError("write_image takes one image (1, C, H, W), got %s" % (tuple(x.shape),))
+    _save_grid([x], 1, path, pre_add, pre_mul)
+
+
+def prepare_sub_folder(output_directory):
+    """utils.py:817-834: make sure <output_directory>/checkpoints and <output_directory>/images exist (a folder that has
+    to be made is announced on stdout, as the reference does) and return them in that order."""
+    made = []
+    for name in ("images", "checkpoints"):
+        d = os.path.join(output_directory, name)
+        if not os.path.exists(d):
+            print("Creating directory: %s" % d)
+            os.makedirs(d)
+        made.append(d)
+    return made[1], made[0]
