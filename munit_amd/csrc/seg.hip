@@ -177,57 +177,29 @@ __device__ inline float pixel_ce(const float* z, int label, const float* mask, l
   return lse - zt;
 }
 
-// per-block partial sums of the pixel losses over pixels [0, npix)
-__global__ void seg_ce_fwd_kernel(const float* __restrict__ lg, const int* __restrict__ labels, const float* __restrict__ mask,
-                                  int B, int h, int w, int S, float* __restrict__ part) {
-  __shared__ float red[NT / 64];
-  const int H = h * S, W = w * S;
-  const long long npix = (long long)B * H * W;
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  float acc = 0.f;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(p % W);
-    const int y = (int)((p / W) % H);
-    const long long b = p / ((long long)W * H);
+// What differs between the cross-entropy heads, per output pixel p = (b, y, x) with row / column taps ty / tx: loss() is the
+// pixel's loss, grad() writes classes() values sc * d loss / d z at g[p * classes()].  Heads travel to the kernels by value;
+// KC is seg_up_adjoint_kernel's.
+struct PseudoHead {   // pseudo-labels (semantic_w)
+  static constexpr int KC = NCLS;
+  const int* labels;
+  const float* mask;
+  int classes() const { return NCLS; }
+  __device__ inline float loss(const float* __restrict__ lg, long long b, int h, int w, const Tap& ty, const Tap& tx,
+                               long long p) const {
     float z[NCLS];
-    up_logits(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), z);
-    acc += pixel_ce(z, labels[p], mask, p, nullptr);
+    up_logits(lg, b, h, w, ty, tx, z);
+    return pixel_ce(z, labels[p], mask, p, nullptr);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < NT / 64; ++i) s += red[i];
-    part[blockIdx.x] = s;
-  }
-}
-__global__ void seg_ce_final_kernel(const float* __restrict__ part, int nb, double inv_n, float* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    double s = 0.0;
-    for (int i = 0; i < nb; ++i) s += (double)part[i];
-    *out = (float)(s * inv_n);
-  }
-}
-// g[p][k] = gout/n * d ce(p) / d z_k at the up-sampled resolution
-__global__ void seg_ce_grad_kernel(const float* __restrict__ lg, const int* __restrict__ labels, const float* __restrict__ mask,
-                                   int B, int h, int w, int S, const float* __restrict__ gout, float inv_n,
-                                   float* __restrict__ g) {
-  const int H = h * S, W = w * S;
-  const long long npix = (long long)B * H * W;
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  const float sc = *gout * inv_n;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(p % W);
-    const int y = (int)((p / W) % H);
-    const long long b = p / ((long long)W * H);
+  __device__ inline void grad(const float* __restrict__ lg, long long b, int h, int w, const Tap& ty, const Tap& tx,
+                              long long p, float sc, float* __restrict__ g) const {
     float z[NCLS], d[NCLS];
-    up_logits(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), z);
+    up_logits(lg, b, h, w, ty, tx, z);
     pixel_ce(z, labels[p], mask, p, d);
 #pragma unroll
     for (int k = 0; k < NCLS; ++k) g[p * NCLS + k] = sc * d[k];
   }
-}
+};
 // ---- cross-entropy against a ground-truth map of the simulator's 10 classes (trainer.py:732-737, utils.py:1330-1353) ----
 constexpr int NMRG = 10;
 // cross-entropy of one pixel on the 19 logits merged into 10: merged class 0 is the constant 0, the others the sums of
@@ -287,48 +259,26 @@ __device__ inline float pixel_ce_gt(const float* z, float gt, const float* mask,
   return ok ? lse - zt : NAN;
 }
 
-__global__ void seg_ce_gt_fwd_kernel(const float* __restrict__ lg, const float* __restrict__ gt, const float* __restrict__ mask,
-                                     int B, int h, int w, int S, float* __restrict__ part) {
-  __shared__ float red[NT / 64];
-  const int H = h * S, W = w * S;
-  const long long npix = (long long)B * H * W;
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  float acc = 0.f;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(p % W);
-    const int y = (int)((p / W) % H);
-    const long long b = p / ((long long)W * H);
+struct GtHead {   // 10-class ground truth (semantic_gt)
+  static constexpr int KC = NCLS;
+  const float* gt;
+  const float* mask;
+  int classes() const { return NCLS; }
+  __device__ inline float loss(const float* __restrict__ lg, long long b, int h, int w, const Tap& ty, const Tap& tx,
+                               long long p) const {
     float z[NCLS];
-    up_logits(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), z);
-    acc += pixel_ce_gt(z, gt[p], mask, p, nullptr);
+    up_logits(lg, b, h, w, ty, tx, z);
+    return pixel_ce_gt(z, gt[p], mask, p, nullptr);
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < NT / 64; ++i) s += red[i];
-    part[blockIdx.x] = s;
-  }
-}
-__global__ void seg_ce_gt_grad_kernel(const float* __restrict__ lg, const float* __restrict__ gt, const float* __restrict__ mask,
-                                      int B, int h, int w, int S, const float* __restrict__ gout, float inv_n,
-                                      float* __restrict__ g) {
-  const int H = h * S, W = w * S;
-  const long long npix = (long long)B * H * W;
-  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-  const float sc = *gout * inv_n;
-  for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (long long)gridDim.x * blockDim.x) {
-    const int x = (int)(p % W);
-    const int y = (int)((p / W) % H);
-    const long long b = p / ((long long)W * H);
+  __device__ inline void grad(const float* __restrict__ lg, long long b, int h, int w, const Tap& ty, const Tap& tx,
+                              long long p, float sc, float* __restrict__ g) const {
     float z[NCLS], d[NCLS];
-    up_logits(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), z);
+    up_logits(lg, b, h, w, ty, tx, z);
     pixel_ce_gt(z, gt[p], mask, p, d);
 #pragma unroll
     for (int k = 0; k < NCLS; ++k) g[p * NCLS + k] = sc * d[k];
   }
-}
+};
 
 // adjoint of the bilinear up-sample as a gather: dl[b][i][j][k] = sum over the output pixels whose taps touch (i, j), in
 // fixed row / column order (the taps of row y reach i0(y) <= i <= i0(y) + 1, so y lies within S rows of [i*S, (i+1)*S))
@@ -397,8 +347,34 @@ __device__ inline float direct_lse(const Taps4& t, int K, float gt, bool* ok, in
   *zt = z_t;
   return mx + logf(se);
 }
-__global__ void seg_ce_direct_fwd_kernel(const float* __restrict__ lg, const float* __restrict__ gt, int B, int h, int w, int S,
-                                         int K, float* __restrict__ part) {
+struct DirectHead {   // K-class head (sem_seg_lambda)
+  static constexpr int KC = 0;
+  const float* gt;
+  int K;
+  int classes() const { return K; }
+  __device__ inline float loss(const float* __restrict__ lg, long long b, int h, int w, const Tap& ty, const Tap& tx,
+                               long long p) const {
+    const Taps4 t = taps_of(lg, b, h, w, K, ty, tx);
+    bool ok;
+    int tgt;
+    float zt;
+    const float lse = direct_lse(t, K, gt[p], &ok, &tgt, &zt);
+    return ok ? lse - zt : NAN;
+  }
+  __device__ inline void grad(const float* __restrict__ lg, long long b, int h, int w, const Tap& ty, const Tap& tx,
+                              long long p, float sc, float* __restrict__ g) const {
+    const Taps4 t = taps_of(lg, b, h, w, K, ty, tx);
+    bool ok;
+    int tgt;
+    float zt;
+    const float lse = direct_lse(t, K, gt[p], &ok, &tgt, &zt);
+    for (int k = 0; k < K; ++k) g[p * K + k] = ok ? sc * (expf(t.at(k) - lse) - (k == tgt ? 1.f : 0.f)) : 0.f;
+  }
+};
+
+// per-block partial sums of the head's pixel losses over pixels [0, npix)
+template <class Head>
+__global__ void seg_ce_loss_kernel(Head hd, const float* __restrict__ lg, int B, int h, int w, int S, float* __restrict__ part) {
   __shared__ float red[NT / 64];
   const int H = h * S, W = w * S;
   const long long npix = (long long)B * H * W;
@@ -408,12 +384,7 @@ __global__ void seg_ce_direct_fwd_kernel(const float* __restrict__ lg, const flo
     const int x = (int)(p % W);
     const int y = (int)((p / W) % H);
     const long long b = p / ((long long)W * H);
-    const Taps4 t = taps_of(lg, b, h, w, K, tap_of(y, h, sy), tap_of(x, w, sx));
-    bool ok;
-    int tgt;
-    float zt;
-    const float lse = direct_lse(t, K, gt[p], &ok, &tgt, &zt);
-    acc += ok ? lse - zt : NAN;
+    acc += hd.loss(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), p);
   }
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
@@ -424,8 +395,17 @@ __global__ void seg_ce_direct_fwd_kernel(const float* __restrict__ lg, const flo
     part[blockIdx.x] = s;
   }
 }
-__global__ void seg_ce_direct_grad_kernel(const float* __restrict__ lg, const float* __restrict__ gt, int B, int h, int w, int S,
-                                          int K, const float* __restrict__ gout, float inv_n, float* __restrict__ g) {
+__global__ void seg_ce_final_kernel(const float* __restrict__ part, int nb, double inv_n, float* __restrict__ out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < nb; ++i) s += (double)part[i];
+    *out = (float)(s * inv_n);
+  }
+}
+// g[p][k] = gout/n * d ce(p) / d z_k at the up-sampled resolution
+template <class Head>
+__global__ void seg_ce_grad_kernel(Head hd, const float* __restrict__ lg, int B, int h, int w, int S,
+                                   const float* __restrict__ gout, float inv_n, float* __restrict__ g) {
   const int H = h * S, W = w * S;
   const long long npix = (long long)B * H * W;
   const float sy = (float)h / (float)H, sx = (float)w / (float)W;
@@ -434,12 +414,7 @@ __global__ void seg_ce_direct_grad_kernel(const float* __restrict__ lg, const fl
     const int x = (int)(p % W);
     const int y = (int)((p / W) % H);
     const long long b = p / ((long long)W * H);
-    const Taps4 t = taps_of(lg, b, h, w, K, tap_of(y, h, sy), tap_of(x, w, sx));
-    bool ok;
-    int tgt;
-    float zt;
-    const float lse = direct_lse(t, K, gt[p], &ok, &tgt, &zt);
-    for (int k = 0; k < K; ++k) g[p * K + k] = ok ? sc * (expf(t.at(k) - lse) - (k == tgt ? 1.f : 0.f)) : 0.f;
+    hd.grad(lg, b, h, w, tap_of(y, h, sy), tap_of(x, w, sx), p, sc, g);
   }
 }
 
@@ -486,15 +461,11 @@ __global__ void seg_labels_kernel(const float* __restrict__ lg, int B, int h, in
     const int y = (int)((p / W) % H);
     const long long b = p / ((long long)W * H);
     // one class at a time (no 19-entry array: keeps the kernel free of spills)
-    const Tap ty = tap_of(y, h, sy), tx = tap_of(x, w, sx);
-    const float* p00 = lg + ((b * h + ty.i0) * w + tx.i0) * NCLS;
-    const float* p01 = lg + ((b * h + ty.i0) * w + tx.i1) * NCLS;
-    const float* p10 = lg + ((b * h + ty.i1) * w + tx.i0) * NCLS;
-    const float* p11 = lg + ((b * h + ty.i1) * w + tx.i1) * NCLS;
+    const Taps4 t = taps_of(lg, b, h, w, NCLS, tap_of(y, h, sy), tap_of(x, w, sx));
     int best = 0;
     float bz = 0.f;
     for (int k = 0; k < NCLS; ++k) {
-      const float zk = ty.l0 * (tx.l0 * p00[k] + tx.l1 * p01[k]) + ty.l1 * (tx.l0 * p10[k] + tx.l1 * p11[k]);
+      const float zk = t.at(k);
       if (k == 0 || zk > bz) {
         best = k;
         bz = zk;
@@ -510,6 +481,47 @@ int check_head(const float* lg, const void* labels, int B, int h, int w, int S) 
   return MUNIT_OK;
 }
 long long head_pix(int B, int h, int w, int S) { return (long long)B * h * S * w * S; }
+
+// Forward of a cross-entropy head: per-block partials of the pixel losses in ws, then their sum / norm in out.
+template <class Head>
+int launch_ce_fwd(const char* what, Head hd, const float* logits, int B, int h, int w, int S, float norm, float* out, void* ws,
+                  size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(out && ws && norm > 0.f, "%s: bad args", what);
+  const long long np = head_pix(B, h, w, S);
+  const unsigned nb = grid_for(np);
+  if (ws_bytes < (size_t)nb * sizeof(float)) {
+    munit_set_error("%s: workspace %zu < %zu", what, ws_bytes, (size_t)nb * sizeof(float));
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* part = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(seg_ce_loss_kernel<Head>, dim3(nb), dim3(NT), 0, st, hd, logits, B, h, w, S, part);
+  MUNIT_CHECK_LAUNCH(what);
+  hipLaunchKernelGGL(seg_ce_final_kernel, dim3(1), dim3(64), 0, st, part, (int)nb, 1.0 / (double)norm, out);
+  MUNIT_CHECK_LAUNCH("seg_ce_final");
+  return MUNIT_OK;
+}
+// Backward: the full-resolution pixel gradients in ws, then the up-sample's adjoint into dlogits.
+template <class Head>
+int launch_ce_bwd(const char* what, Head hd, const float* logits, int B, int h, int w, int S, float norm, const float* gout,
+                  float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(gout && dlogits && ws && norm > 0.f, "%s: bad args", what);
+  const long long np = head_pix(B, h, w, S);
+  const int K = hd.classes();
+  const size_t need = (size_t)np * K * sizeof(float);
+  if (ws_bytes < need) {
+    munit_set_error("%s: workspace %zu < %zu", what, ws_bytes, need);
+    return MUNIT_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  float* g = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(seg_ce_grad_kernel<Head>, dim3(grid_for(np)), dim3(NT), 0, st, hd, logits, B, h, w, S, gout, 1.f / norm, g);
+  MUNIT_CHECK_LAUNCH(what);
+  hipLaunchKernelGGL(seg_up_adjoint_kernel<Head::KC>, dim3(grid_for((long long)B * h * w * K)), dim3(NT), 0, st, g, B, h, w, S,
+                     K, dlogits);
+  MUNIT_CHECK_LAUNCH("seg_up_adjoint");
+  return MUNIT_OK;
+}
 
 }  // namespace
 
@@ -572,30 +584,14 @@ extern "C" int munit_add_relu_fwd(const float* a, const float* r, float* y, size
 }
 
 extern "C" size_t munit_seg_ce_workspace_bytes(int B, int h, int w, int S) {
-  const long long np = head_pix(B, h, w, S);
-  const size_t part = align_up((size_t)grid_for(np) * sizeof(float), 256);
-  const size_t grad = align_up((size_t)np * NCLS * sizeof(float), 256);
-  return std::max(part, grad);
+  return munit_seg_ce_direct_workspace_bytes(B, h, w, S, NCLS);
 }
 
 extern "C" int munit_seg_ce_fwd(const float* logits, const int* labels, const float* mask, int B, int h, int w, int S,
                                 float norm, float* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
   int rc = check_head(logits, labels, B, h, w, S);
   if (rc) return rc;
-  MUNIT_CHECK_ARG(out && ws && norm > 0.f, "seg_ce_fwd: bad args");
-  const long long np = head_pix(B, h, w, S);
-  const unsigned nb = grid_for(np);
-  if (ws_bytes < (size_t)nb * sizeof(float)) {
-    munit_set_error("seg_ce_fwd: workspace %zu < %zu", ws_bytes, (size_t)nb * sizeof(float));
-    return MUNIT_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* part = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(seg_ce_fwd_kernel, dim3(nb), dim3(NT), 0, st, logits, labels, mask, B, h, w, S, part);
-  MUNIT_CHECK_LAUNCH("seg_ce_fwd");
-  hipLaunchKernelGGL(seg_ce_final_kernel, dim3(1), dim3(64), 0, st, part, (int)nb, 1.0 / (double)norm, out);
-  MUNIT_CHECK_LAUNCH("seg_ce_final");
-  return MUNIT_OK;
+  return launch_ce_fwd("seg_ce_fwd", PseudoHead{labels, mask}, logits, B, h, w, S, norm, out, ws, ws_bytes, stream);
 }
 
 extern "C" int munit_seg_ce_bwd(const float* logits, const int* labels, const float* mask, int B, int h, int w, int S,
@@ -603,22 +599,7 @@ extern "C" int munit_seg_ce_bwd(const float* logits, const int* labels, const fl
                                 munit_stream_t stream) {
   int rc = check_head(logits, labels, B, h, w, S);
   if (rc) return rc;
-  MUNIT_CHECK_ARG(gout && dlogits && ws && norm > 0.f, "seg_ce_bwd: bad args");
-  const long long np = head_pix(B, h, w, S);
-  const size_t need = (size_t)np * NCLS * sizeof(float);
-  if (ws_bytes < need) {
-    munit_set_error("seg_ce_bwd: workspace %zu < %zu", ws_bytes, need);
-    return MUNIT_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* g = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(seg_ce_grad_kernel, dim3(grid_for(np)), dim3(NT), 0, st, logits, labels, mask, B, h, w, S, gout,
-                     1.f / norm, g);
-  MUNIT_CHECK_LAUNCH("seg_ce_grad");
-  hipLaunchKernelGGL(seg_up_adjoint_kernel<NCLS>, dim3(grid_for((long long)B * h * w * NCLS)), dim3(NT), 0, st, g, B, h, w,
-                     S, NCLS, dlogits);
-  MUNIT_CHECK_LAUNCH("seg_up_adjoint");
-  return MUNIT_OK;
+  return launch_ce_bwd("seg_ce_bwd", PseudoHead{labels, mask}, logits, B, h, w, S, norm, gout, dlogits, ws, ws_bytes, stream);
 }
 
 extern "C" int munit_seg_labels(const float* logits, int B, int h, int w, int S, int* labels, munit_stream_t stream) {
@@ -630,25 +611,12 @@ extern "C" int munit_seg_labels(const float* logits, int B, int h, int w, int S,
   return MUNIT_OK;
 }
 
-// The same head against a ground-truth map (see pixel_ce_gt); reduction, up-sample adjoint and workspace are munit_seg_ce_*'s.
+// The same head against a ground-truth map (see pixel_ce_gt)
 extern "C" int munit_seg_ce_gt_fwd(const float* logits, const float* gt, const float* mask, int B, int h, int w, int S,
                                    float norm, float* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
   int rc = check_head(logits, gt, B, h, w, S);
   if (rc) return rc;
-  MUNIT_CHECK_ARG(out && ws && norm > 0.f, "seg_ce_gt_fwd: bad args");
-  const long long np = head_pix(B, h, w, S);
-  const unsigned nb = grid_for(np);
-  if (ws_bytes < (size_t)nb * sizeof(float)) {
-    munit_set_error("seg_ce_gt_fwd: workspace %zu < %zu", ws_bytes, (size_t)nb * sizeof(float));
-    return MUNIT_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* part = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(seg_ce_gt_fwd_kernel, dim3(nb), dim3(NT), 0, st, logits, gt, mask, B, h, w, S, part);
-  MUNIT_CHECK_LAUNCH("seg_ce_gt_fwd");
-  hipLaunchKernelGGL(seg_ce_final_kernel, dim3(1), dim3(64), 0, st, part, (int)nb, 1.0 / (double)norm, out);
-  MUNIT_CHECK_LAUNCH("seg_ce_final");
-  return MUNIT_OK;
+  return launch_ce_fwd("seg_ce_gt_fwd", GtHead{gt, mask}, logits, B, h, w, S, norm, out, ws, ws_bytes, stream);
 }
 
 extern "C" int munit_seg_ce_gt_bwd(const float* logits, const float* gt, const float* mask, int B, int h, int w, int S,
@@ -656,22 +624,7 @@ extern "C" int munit_seg_ce_gt_bwd(const float* logits, const float* gt, const f
                                    munit_stream_t stream) {
   int rc = check_head(logits, gt, B, h, w, S);
   if (rc) return rc;
-  MUNIT_CHECK_ARG(gout && dlogits && ws && norm > 0.f, "seg_ce_gt_bwd: bad args");
-  const long long np = head_pix(B, h, w, S);
-  const size_t need = (size_t)np * NCLS * sizeof(float);
-  if (ws_bytes < need) {
-    munit_set_error("seg_ce_gt_bwd: workspace %zu < %zu", ws_bytes, need);
-    return MUNIT_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* g = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(seg_ce_gt_grad_kernel, dim3(grid_for(np)), dim3(NT), 0, st, logits, gt, mask, B, h, w, S, gout,
-                     1.f / norm, g);
-  MUNIT_CHECK_LAUNCH("seg_ce_gt_grad");
-  hipLaunchKernelGGL(seg_up_adjoint_kernel<NCLS>, dim3(grid_for((long long)B * h * w * NCLS)), dim3(NT), 0, st, g, B, h, w,
-                     S, NCLS, dlogits);
-  MUNIT_CHECK_LAUNCH("seg_up_adjoint");
-  return MUNIT_OK;
+  return launch_ce_bwd("seg_ce_gt_bwd", GtHead{gt, mask}, logits, B, h, w, S, norm, gout, dlogits, ws, ws_bytes, stream);
 }
 
 // ---- trainable segmentation head (adaptation.sem_seg_lambda) ----
@@ -723,40 +676,12 @@ extern "C" int munit_seg_ce_direct_fwd(const float* logits, const float* gt, int
                                        float* out, void* ws, size_t ws_bytes, munit_stream_t stream) {
   int rc = check_direct(logits, gt, B, h, w, S, K, "seg_ce_direct_fwd");
   if (rc) return rc;
-  MUNIT_CHECK_ARG(out && ws && norm > 0.f, "seg_ce_direct_fwd: bad args");
-  const long long np = head_pix(B, h, w, S);
-  const unsigned nb = grid_for(np);
-  if (ws_bytes < (size_t)nb * sizeof(float)) {
-    munit_set_error("seg_ce_direct_fwd: workspace %zu < %zu", ws_bytes, (size_t)nb * sizeof(float));
-    return MUNIT_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* part = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(seg_ce_direct_fwd_kernel, dim3(nb), dim3(NT), 0, st, logits, gt, B, h, w, S, K, part);
-  MUNIT_CHECK_LAUNCH("seg_ce_direct_fwd");
-  hipLaunchKernelGGL(seg_ce_final_kernel, dim3(1), dim3(64), 0, st, part, (int)nb, 1.0 / (double)norm, out);
-  MUNIT_CHECK_LAUNCH("seg_ce_final");
-  return MUNIT_OK;
+  return launch_ce_fwd("seg_ce_direct_fwd", DirectHead{gt, K}, logits, B, h, w, S, norm, out, ws, ws_bytes, stream);
 }
 
 extern "C" int munit_seg_ce_direct_bwd(const float* logits, const float* gt, int B, int h, int w, int S, int K, float norm,
                                        const float* gout, float* dlogits, void* ws, size_t ws_bytes, munit_stream_t stream) {
   int rc = check_direct(logits, gt, B, h, w, S, K, "seg_ce_direct_bwd");
   if (rc) return rc;
-  MUNIT_CHECK_ARG(gout && dlogits && ws && norm > 0.f, "seg_ce_direct_bwd: bad args");
-  const long long np = head_pix(B, h, w, S);
-  const size_t need = (size_t)np * K * sizeof(float);
-  if (ws_bytes < need) {
-    munit_set_error("seg_ce_direct_bwd: workspace %zu < %zu", ws_bytes, need);
-    return MUNIT_ERR_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  float* g = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(seg_ce_direct_grad_kernel, dim3(grid_for(np)), dim3(NT), 0, st, logits, gt, B, h, w, S, K, gout,
-                     1.f / norm, g);
-  MUNIT_CHECK_LAUNCH("seg_ce_direct_grad");
-  hipLaunchKernelGGL(seg_up_adjoint_kernel<0>, dim3(grid_for((long long)B * h * w * K)), dim3(NT), 0, st, g, B, h, w, S, K,
-                     dlogits);
-  MUNIT_CHECK_LAUNCH("seg_up_adjoint");
-  return MUNIT_OK;
+  return launch_ce_bwd("seg_ce_direct_bwd", DirectHead{gt, K}, logits, B, h, w, S, norm, gout, dlogits, ws, ws_bytes, stream);
 }

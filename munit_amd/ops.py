@@ -9,6 +9,7 @@ Parameter gradients: when a parameter carries a `_munit_grad` buffer (the traine
 gradient storage) backward-weight accumulates straight into it (beta = 1) and autograd gets
 None; otherwise the gradient is returned the ordinary way (used by the op-level tests).
 """
+import collections
 import ctypes
 import os
 from ctypes import byref, c_float, c_int, c_void_p
@@ -1209,105 +1210,80 @@ def space_to_batch(x, f, inverse=False):
     return _SpaceToBatch.apply(x, f, inverse)
 
 
-def _seg_head_args(logits, labels, mask, scale):
+# The three cross-entropy heads of csrc/seg.hip differ in their library symbols and in what they take: a mask or not, the
+# target's dtype (and the noun error messages use for it), 19 logits or a class count K passed through to the library.
+_SegHead = collections.namedtuple("_SegHead", "fwd bwd ws_bytes masked dtype noun fixed")
+_SEG_PSEUDO = _SegHead("munit_seg_ce_fwd", "munit_seg_ce_bwd", "munit_seg_ce_workspace_bytes", True, torch.int32, "labels", True)
+_SEG_GT = _SegHead("munit_seg_ce_gt_fwd", "munit_seg_ce_gt_bwd", "munit_seg_ce_workspace_bytes", True, torch.float32,
+                   "ground truth", True)
+_SEG_DIRECT = _SegHead("munit_seg_ce_direct_fwd", "munit_seg_ce_direct_bwd", "munit_seg_ce_direct_workspace_bytes", False,
+                       torch.float32, "target", False)
+
+
+def _seg_ce_args(head, logits, target, mask, scale):
     logits = nhwc(logits)
     _require(logits, "segmentation logits")
     b, k, h, w = logits.shape
-    if k != 19:
+    if head.fixed and k != 19:
         raise RuntimeError("munit_amd.seg head: 19 classes expected, got %d" % k)
-    if labels.dtype != torch.int32 or tuple(labels.shape) != (b, h * scale, w * scale) or not labels.is_contiguous():
-        raise RuntimeError("munit_amd.seg head: labels must be contiguous int32 (%d, %d, %d)" % (b, h * scale, w * scale))
+    if head.dtype == torch.float32:
+        _require(target, "segmentation " + head.noun)
+    if target.dtype != head.dtype or tuple(target.shape) != (b, h * scale, w * scale) or not target.is_contiguous():
+        raise RuntimeError("munit_amd.seg head: the %s must be contiguous %s (%d, %d, %d), got %s %s"
+                           % (head.noun, head.dtype, b, h * scale, w * scale, target.dtype, tuple(target.shape)))
     if mask is not None:
         _require(mask, "segmentation mask")
         if mask.numel() != b * h * scale * w * scale or not mask.is_contiguous():
             raise RuntimeError("munit_amd.seg head: mask must hold one contiguous value per pixel")
-    _same_device(logits, labels, mask)
-    return logits, b, h, w
+    _same_device(logits, target, mask)
+    return logits
 
 
-class _SegCE(Function):
+def _seg_ce_operands(head, logits, target, mask, scale):
+    """What every library call of a head begins with: its pointers, and its dimensions (the workspace query's arguments)."""
+    b, k, h, w = logits.shape
+    ptrs = (_p(logits), _p(target)) + ((_p(mask),) if head.masked else ())
+    return ptrs, (b, h, w, scale) + (() if head.fixed else (k,))
+
+
+class _SegCrossEntropy(Function):
     @staticmethod
     @_guarded
-    def forward(ctx, logits, labels, mask, scale, norm):
+    def forward(ctx, logits, target, mask, head, scale, norm):
         lib = _lib.load()
-        logits, b, h, w = _seg_head_args(logits, labels, mask, scale)
-        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
+        logits = _seg_ce_args(head, logits, target, mask, scale)
+        ptrs, dims = _seg_ce_operands(head, logits, target, mask, scale)
+        ws = workspace(getattr(lib, head.ws_bytes)(*dims), logits.device)
         out = torch.empty((), device=logits.device, dtype=torch.float32)
-        _lib.check(lib.munit_seg_ce_fwd(_p(logits), _p(labels), _p(mask), b, h, w, scale, c_float(norm), _p(out), _p(ws),
-                                        ws.numel(), _stream()), "seg_ce_fwd")
-        ctx.cfg = (scale, norm)
-        ctx.save_for_backward(logits, labels, mask)
+        _lib.check(getattr(lib, head.fwd)(*ptrs, *dims, c_float(norm), _p(out), _p(ws), ws.numel(), _stream()), head.fwd[6:])
+        ctx.cfg = (head, scale, norm)
+        ctx.save_for_backward(logits, target, mask)
         return out
 
     @staticmethod
     @_guarded
     def backward(ctx, gout):
         lib = _lib.load()
-        logits, labels, mask = ctx.saved_tensors
-        scale, norm = ctx.cfg
-        b, _, h, w = logits.shape
+        logits, target, mask = ctx.saved_tensors
+        head, scale, norm = ctx.cfg
+        ptrs, dims = _seg_ce_operands(head, logits, target, mask, scale)
         gout = gout.contiguous()
-        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
+        ws = workspace(getattr(lib, head.ws_bytes)(*dims), logits.device)
         dl = torch.empty_like(logits)
-        _lib.check(lib.munit_seg_ce_bwd(_p(logits), _p(labels), _p(mask), b, h, w, scale, c_float(norm), _p(gout), _p(dl),
-                                        _p(ws), ws.numel(), _stream()), "seg_ce_bwd")
-        return dl, None, None, None, None
+        _lib.check(getattr(lib, head.bwd)(*ptrs, *dims, c_float(norm), _p(gout), _p(dl), _p(ws), ws.numel(), _stream()),
+                   head.bwd[6:])
+        return dl, None, None, None, None, None
+
+
+def _seg_ce(head, logits, target, mask, scale, norm):
+    return _SegCrossEntropy.apply(logits, target, mask, head, int(scale), float(target.numel() if norm is None else norm))
 
 
 def seg_cross_entropy(logits, labels, mask=None, scale=8, norm=None):
     """nn.CrossEntropyLoss of the bilinearly up-sampled logits (trainer.py:746-771): the masked 20-class form when `mask`
     (one 0/1 value per output pixel) is given, else the plain 19-class one.  Sum of the pixel losses / norm (default:
     all pixels, i.e. the mean)."""
-    if norm is None:
-        norm = labels.numel()
-    return _SegCE.apply(logits, labels, mask, int(scale), float(norm))
-
-
-def _seg_gt_args(logits, gt, mask, scale):
-    logits = nhwc(logits)
-    _require(logits, "segmentation logits")
-    b, k, h, w = logits.shape
-    if k != 19:
-        raise RuntimeError("munit_amd.seg head: 19 classes expected, got %d" % k)
-    _require(gt, "segmentation ground truth")
-    if tuple(gt.shape) != (b, h * scale, w * scale) or not gt.is_contiguous():
-        raise RuntimeError("munit_amd.seg head: the ground truth must be contiguous float32 (%d, %d, %d), got %s"
-                           % (b, h * scale, w * scale, tuple(gt.shape)))
-    if mask is not None:
-        _require(mask, "segmentation mask")
-        if mask.numel() != b * h * scale * w * scale or not mask.is_contiguous():
-            raise RuntimeError("munit_amd.seg head: mask must hold one contiguous value per pixel")
-    _same_device(logits, gt, mask)
-    return logits, b, h, w
-
-
-class _SegCEGT(Function):
-    @staticmethod
-    @_guarded
-    def forward(ctx, logits, gt, mask, scale, norm):
-        lib = _lib.load()
-        logits, b, h, w = _seg_gt_args(logits, gt, mask, scale)
-        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
-        out = torch.empty((), device=logits.device, dtype=torch.float32)
-        _lib.check(lib.munit_seg_ce_gt_fwd(_p(logits), _p(gt), _p(mask), b, h, w, scale, c_float(norm), _p(out), _p(ws),
-                                           ws.numel(), _stream()), "seg_ce_gt_fwd")
-        ctx.cfg = (scale, norm)
-        ctx.save_for_backward(logits, gt, mask)
-        return out
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, gout):
-        lib = _lib.load()
-        logits, gt, mask = ctx.saved_tensors
-        scale, norm = ctx.cfg
-        b, _, h, w = logits.shape
-        gout = gout.contiguous()
-        ws = workspace(lib.munit_seg_ce_workspace_bytes(b, h, w, scale), logits.device)
-        dl = torch.empty_like(logits)
-        _lib.check(lib.munit_seg_ce_gt_bwd(_p(logits), _p(gt), _p(mask), b, h, w, scale, c_float(norm), _p(gout), _p(dl),
-                                           _p(ws), ws.numel(), _stream()), "seg_ce_gt_bwd")
-        return dl, None, None, None, None
+    return _seg_ce(_SEG_PSEUDO, logits, labels, mask, scale, norm)
 
 
 def seg_cross_entropy_gt(logits, gt, mask=None, scale=8, norm=None):
@@ -1315,54 +1291,14 @@ def seg_cross_entropy_gt(logits, gt, mask=None, scale=8, norm=None):
     logits are merged into 10 (merge_classes, utils.py:1330-1353) inside the kernel; gt is float32 (B, H, W) with values
     0..9, truncated like .type(torch.long).  The masked form appends the mask as an 11th class.  A label outside 0..9
     makes the loss NaN (include/munit_hip.h)."""
-    if norm is None:
-        norm = gt.numel()
-    return _SegCEGT.apply(logits, gt, mask, int(scale), float(norm))
-
-
-class _SegCEDirect(Function):
-    @staticmethod
-    @_guarded
-    def forward(ctx, logits, gt, scale, norm):
-        lib = _lib.load()
-        logits = nhwc(logits)
-        _require(logits, "segmentation-head logits")
-        b, k, h, w = logits.shape
-        _require(gt, "segmentation-head target")
-        if tuple(gt.shape) != (b, h * scale, w * scale) or not gt.is_contiguous():
-            raise RuntimeError("munit_amd.seg_cross_entropy_direct: the target must be contiguous float32 (%d, %d, %d), got %s"
-                               % (b, h * scale, w * scale, tuple(gt.shape)))
-        _same_device(logits, gt)
-        ws = workspace(lib.munit_seg_ce_direct_workspace_bytes(b, h, w, scale, k), logits.device)
-        out = torch.empty((), device=logits.device, dtype=torch.float32)
-        _lib.check(lib.munit_seg_ce_direct_fwd(_p(logits), _p(gt), b, h, w, scale, k, c_float(norm), _p(out), _p(ws),
-                                               ws.numel(), _stream()), "seg_ce_direct_fwd")
-        ctx.cfg = (scale, norm)
-        ctx.save_for_backward(logits, gt)
-        return out
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, gout):
-        lib = _lib.load()
-        logits, gt = ctx.saved_tensors
-        scale, norm = ctx.cfg
-        b, k, h, w = logits.shape
-        gout = gout.contiguous()
-        ws = workspace(lib.munit_seg_ce_direct_workspace_bytes(b, h, w, scale, k), logits.device)
-        dl = torch.empty_like(logits)
-        _lib.check(lib.munit_seg_ce_direct_bwd(_p(logits), _p(gt), b, h, w, scale, k, c_float(norm), _p(gout), _p(dl),
-                                               _p(ws), ws.numel(), _stream()), "seg_ce_direct_bwd")
-        return dl, None, None, None
+    return _seg_ce(_SEG_GT, logits, gt, mask, scale, norm)
 
 
 def seg_cross_entropy_direct(logits, gt, scale=4, norm=None):
     """nn.CrossEntropyLoss of the bilinearly up-sampled K-class logits (B, K, h, w), K in 2..32, against gt (B, h*scale,
     w*scale) float32 truncated like .type(torch.long) (trainer.py:1305-1317): no mask, no class merge.  Sum of the pixel
     losses / norm (default: all pixels, i.e. the mean).  A label outside 0..K-1 makes the loss NaN (include/munit_hip.h)."""
-    if norm is None:
-        norm = gt.numel()
-    return _SegCEDirect.apply(logits, gt, int(scale), float(norm))
+    return _seg_ce(_SEG_DIRECT, logits, gt, None, scale, norm)
 
 
 class _AvgPool7(Function):
