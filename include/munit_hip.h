@@ -294,6 +294,21 @@ int munit_lsgan_fwd(const float* const* x, const size_t* n, const float* target,
                     void* ws, size_t ws_bytes, munit_stream_t stream);
 int munit_lsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
                     float* const* dx, munit_stream_t stream);
+/* Multi-scale non-saturating GAN loss (dis.gan_type nsgan, networks.py:79-139), the sibling of the LSGAN pair above with the
+ * same arguments and the same contract (segments, host arrays by value, any 4-byte start, double-scaled means added in index
+ * order, nullable seg_out, no atomics, bitwise repeatable, bwd writes every dx[s] in full).  target[s] must be exactly 0 or 1
+ * (anything else: MUNIT_ERR_ARG before any launch).  With z = x for target 0 and z = -x for target 1,
+ *   out[0] = sum_s mean(softplus(z_s)),  softplus(z) = max(z, 0) + log1p(exp(-|z|)),
+ *   dx_s[i] = gout[0] / n_s * (1 - 2 target_s) * sigmoid(z),  sigmoid(z) = 1 / (1 + exp(-z)) for z >= 0, exp(z) / (1 + exp(z)) else
+ * -- the quantity the reference's mean(binary_cross_entropy(sigmoid(x), target)) evaluates.  Where the reference's fp32
+ * `sigmoid` saturates (logits beyond about 16.6), the reference returns 100 per element and a zero gradient; the build
+ * returns the true value |z| and the true gradient.  Infinite logits give +inf / 0 loss elements and gout / n_s / 0 gradients,
+ * a NaN logit a NaN loss and a NaN in that one dx element.  ws: munit_nsgan_workspace_bytes(nseg). */
+size_t munit_nsgan_workspace_bytes(int nseg);
+int munit_nsgan_fwd(const float* const* x, const size_t* n, const float* target, int nseg, float* out, float* seg_out,
+                    void* ws, size_t ws_bytes, munit_stream_t stream);
+int munit_nsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
+                    float* const* dx, munit_stream_t stream);
 /* out = sum_i w[i] * *(terms[i]); n <= 32; terms are device scalars, w host floats. */
 int munit_weighted_sum(const float* const* terms, const float* w, int n, float* out,
                        munit_stream_t stream);

@@ -108,6 +108,9 @@ SIGNATURES = {
     "munit_lsgan_workspace_bytes": (c_size_t, [c_int]),
     "munit_lsgan_fwd": (c_int, [POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float), c_int, _P, _P, _P, c_size_t, _P]),
     "munit_lsgan_bwd": (c_int, [POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float), c_int, _P, POINTER(c_void_p), _P]),
+    "munit_nsgan_workspace_bytes": (c_size_t, [c_int]),
+    "munit_nsgan_fwd": (c_int, [POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float), c_int, _P, _P, _P, c_size_t, _P]),
+    "munit_nsgan_bwd": (c_int, [POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float), c_int, _P, POINTER(c_void_p), _P]),
     "munit_weighted_sum": (c_int, [POINTER(c_void_p), POINTER(c_float), c_int, _P, _P]),
     "munit_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int,
                                 _P]),

@@ -1,5 +1,5 @@
 // Small HBM-bound kernels of the MUNIT step: activation backward, the discriminator's
-// 3x3/s2 average-pool pyramid, the style encoder's global average pool, the L1 / LSGAN loss
+// 3x3/s2 average-pool pyramid, the style encoder's global average pool, the L1 / LSGAN / nsgan loss
 // reductions with their gradient seeds, the fused flat-buffer Adam update and scaling.
 #include "common.h"
 
@@ -284,6 +284,44 @@ __global__ __launch_bounds__(NT) void lsgan_bwd_kernel(LsganArgs a, const float*
     dx[i] = g * (x[i] - target);
 }
 
+// Multi-scale non-saturating GAN loss (networks.py:79-139, gan_type nsgan): sum over segments s of mean(softplus(z)), z = x
+// for target 0 and -x for target 1 -- what binary_cross_entropy(sigmoid(x), target) evaluates, in the form that neither
+// saturates nor meets inf - inf: max(z, 0) + log1p(exp(-|z|)).  Segments, block ranges and the finishing block are the LSGAN
+// pair's (LsganArgs, lsgan_segment, lsgan_finish_kernel); target[s] is exactly 0 or 1 here (checked on the host).
+__device__ inline float nsgan_softplus(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
+
+__device__ inline float nsgan_sigmoid(float z) {
+  if (z >= 0.f) return 1.f / (1.f + expf(-z));
+  const float e = expf(z);      // z < 0, or NaN (which stays NaN)
+  return e / (1.f + e);
+}
+
+__global__ __launch_bounds__(NT) void nsgan_partial_kernel(LsganArgs a, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const int s = lsgan_segment(a, blockIdx.x);
+  const float* __restrict__ x = a.x[s];
+  const float sign = 1.f - 2.f * a.target[s];
+  const unsigned long long n = a.n[s];
+  const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
+  float acc = 0.f;
+  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride)
+    acc += nsgan_softplus(sign * x[i]);
+  acc = block_sum256(acc, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(NT) void nsgan_bwd_kernel(LsganArgs a, const float* __restrict__ gout) {
+  const int s = lsgan_segment(a, blockIdx.x);
+  const float* __restrict__ x = a.x[s];
+  float* __restrict__ dx = a.dx[s];
+  const float sign = 1.f - 2.f * a.target[s];
+  const unsigned long long n = a.n[s];
+  const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
+  const float g = sign * (gout[0] / (float)n);
+  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride)
+    dx[i] = g * nsgan_sigmoid(sign * x[i]);
+}
+
 struct WsumArgs {
   const float* t[32];
   float w[32];
@@ -566,6 +604,42 @@ extern "C" int munit_lsgan_bwd(const float* const* x, const size_t* n, const flo
   const int blocks = lsgan_fill(a, x, n, target, nseg, dx);
   hipLaunchKernelGGL(lsgan_bwd_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, gout);
   MUNIT_CHECK_LAUNCH("lsgan_bwd");
+  return MUNIT_OK;
+}
+
+extern "C" size_t munit_nsgan_workspace_bytes(int nseg) { return munit_lsgan_workspace_bytes(nseg); }
+
+extern "C" int munit_nsgan_fwd(const float* const* x, const size_t* n, const float* target, int nseg, float* out,
+                               float* seg_out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x && n && target && out && ws, "nsgan_fwd: null pointer");
+  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "nsgan_fwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
+  for (int s = 0; s < nseg; ++s) {
+    MUNIT_CHECK_ARG(x[s] && n[s] > 0, "nsgan_fwd: segment %d is null or empty", s);
+    MUNIT_CHECK_ARG(target[s] == 0.f || target[s] == 1.f, "nsgan_fwd: target %d must be 0 or 1, got %g", s, (double)target[s]);
+  }
+  MUNIT_CHECK_ARG(ws_bytes >= munit_nsgan_workspace_bytes(nseg), "nsgan_fwd: workspace too small");
+  LsganArgs a{};
+  const int blocks = lsgan_fill(a, x, n, target, nseg, nullptr);
+  float* partial = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(nsgan_partial_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, partial);
+  MUNIT_CHECK_LAUNCH("nsgan_partial");
+  hipLaunchKernelGGL(lsgan_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, partial, out, seg_out);
+  MUNIT_CHECK_LAUNCH("nsgan_finish");
+  return MUNIT_OK;
+}
+
+extern "C" int munit_nsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
+                               float* const* dx, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x && n && target && gout && dx, "nsgan_bwd: null pointer");
+  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "nsgan_bwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
+  for (int s = 0; s < nseg; ++s) {
+    MUNIT_CHECK_ARG(x[s] && dx[s] && n[s] > 0, "nsgan_bwd: segment %d is null or empty", s);
+    MUNIT_CHECK_ARG(target[s] == 0.f || target[s] == 1.f, "nsgan_bwd: target %d must be 0 or 1, got %g", s, (double)target[s]);
+  }
+  LsganArgs a{};
+  const int blocks = lsgan_fill(a, x, n, target, nseg, dx);
+  hipLaunchKernelGGL(nsgan_bwd_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, gout);
+  MUNIT_CHECK_LAUNCH("nsgan_bwd");
   return MUNIT_OK;
 }
 

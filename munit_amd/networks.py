@@ -525,8 +525,8 @@ BATCH_DIS_PAIR = os.environ.get("MUNIT_NO_BATCH_DIS_PAIR", "0") != "1"
 
 
 class MsImageDis(_ApplyRefreshesImages, nn.Module):
-    """networks.py:20-115 (LSGAN branch; nsgan hard-codes .cuda() BCE in the reference and is
-    not on the configs' path)."""
+    """networks.py:20-162: gan_type lsgan, and nsgan -- the reference's mean(binary_cross_entropy(sigmoid(x), t)) evaluated as
+    mean(softplus(+-x)) by one ops.nsgan_loss over all scales (exact where the reference's fp32 sigmoid saturates)."""
 
     def __init__(self, input_dim, params):
         super().__init__()
@@ -574,6 +574,8 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         return outputs
 
     def calc_dis_loss(self, input_fake, input_real):
+        if self.gan_type == "nsgan":        # networks.py:92-98: fake -> 0, real -> 1
+            return self._nsgan_pair(input_fake, input_real)
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
         terms = []
         if BATCH_DIS_PAIR and input_fake.shape == input_real.shape and input_fake.dtype == input_real.dtype:
@@ -597,6 +599,8 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
 
     def calc_gen_loss(self, input_fake):
         outs0 = self.forward(input_fake)
+        if self.gan_type == "nsgan":        # networks.py:110-112: fake -> 1
+            return self._multi_scale(ops.nsgan_loss, outs0, [1.0] * len(outs0))
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
         return ops.scalar_sum([ops.mse_const(out0, 1.0) for out0 in outs0])
 
@@ -609,9 +613,36 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
             return ops.lsgan_loss(outs, targets)
         return ops.scalar_sum([ops.lsgan_loss(outs[i:i + step], targets[i:i + step]) for i in range(0, len(outs), step)])
 
+    @staticmethod
+    def _multi_scale(loss, outs, targets):
+        """_lsgan's grouping for another loss of the same signature (ops.nsgan_loss)"""
+        per = 2 if isinstance(targets[0], tuple) else 1
+        step = max(1, 8 // per)
+        if len(outs) <= step:
+            return loss(outs, targets)
+        return ops.scalar_sum([loss(outs[i:i + step], targets[i:i + step]) for i in range(0, len(outs), step)])
+
+    def _nsgan_pair(self, input0, input1):
+        """nsgan of calc_dis_loss / calc_dis_loss_sr (networks.py:92-98, 130-136): first argument -> 0, second -> 1, summed
+        over the scales.  One pass over [first; second] under calc_dis_loss's condition, the recorded LeakyReLU branches handed
+        over in the reference's order; the loss of all scales and both halves is one kernel pair (ops.nsgan_loss)."""
+        if BATCH_DIS_PAIR and input0.shape == input1.shape and input0.dtype == input1.dtype:
+            nb = input0.shape[0]
+            n0 = len(ops.MASK_SINK) if ops.MASK_SINK is not None else 0
+            outs = self.forward(torch.cat([ops.nhwc(input0), ops.nhwc(input1)], 0))
+            if ops.MASK_SINK is not None:
+                rec = ops.MASK_SINK[n0:]
+                ops.MASK_SINK[n0:] = [m[:nb] for m in rec] + [m[nb:] for m in rec]
+            return self._multi_scale(ops.nsgan_loss, outs, [(0.0, 1.0)] * len(outs))
+        outs0 = self.forward(input0)
+        outs1 = self.forward(input1)
+        return self._multi_scale(ops.nsgan_loss, outs0 + outs1, [0.0] * len(outs0) + [1.0] * len(outs1))
+
     def calc_dis_loss_sr(self, input_sim, input_real):
         """networks.py:117-139 (LSGAN): simulated -> 0, real -> 1, summed over the scales.  One pass over [sim; real] under
         calc_dis_loss's condition; the loss of all scales and both halves is one kernel pair (ops.lsgan_loss)."""
+        if self.gan_type == "nsgan":
+            return self._nsgan_pair(input_sim, input_real)
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
         if BATCH_DIS_PAIR and input_sim.shape == input_real.shape and input_sim.dtype == input_real.dtype:
             nb = input_sim.shape[0]
@@ -627,6 +658,9 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
 
     def calc_gen_loss_sr(self, input_fake):
         """networks.py:141-162 (LSGAN; the reference's nsgan branch there names an undefined variable): target 0.5."""
+        if self.gan_type == "nsgan":
+            raise NotImplementedError("munit_amd: MsImageDis.calc_gen_loss_sr has no gan_type 'nsgan': the reference's own "
+                                      "branch names an undefined variable (out1, networks.py:155) and raises NameError")
         outs0 = self.forward(input_fake)
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
         return self._lsgan(outs0, [0.5] * len(outs0))

@@ -949,6 +949,66 @@ def lsgan_loss(outs, targets):
     return _LsganLoss.apply(tuple(tuple(t) if isinstance(t, (tuple, list)) else float(t) for t in targets), *outs)
 
 
+class _NsganLoss(Function):
+    """sum over the tensors (and, for a pair target, over the two batch halves of a tensor) of mean(softplus(z)), z = x for
+    target 0 and -x for target 1: one munit_nsgan_fwd, one munit_nsgan_bwd that writes every tensor's gradient whole.  No view
+    of a tensor enters the tape."""
+
+    @staticmethod
+    def forward(ctx, targets, *xs):
+        lib = _lib.load()
+        if len(xs) == 0 or len(xs) != len(targets):
+            raise RuntimeError("munit_amd.nsgan_loss: one target per tensor expected (%d tensors, %d targets)"
+                               % (len(xs), len(targets)))
+        for i, (x, t) in enumerate(zip(xs, targets)):
+            _require(x, "nsgan_loss input %d" % i)
+            if x.numel() == 0:
+                raise RuntimeError("munit_amd.nsgan_loss: input %d is empty" % i)
+            if isinstance(t, (tuple, list)):
+                if len(t) != 2:
+                    raise RuntimeError("munit_amd.nsgan_loss: a pair target holds two numbers, got %r" % (t,))
+                if x.dim() == 0 or x.shape[0] % 2:
+                    raise RuntimeError("munit_amd.nsgan_loss: a pair target splits the batch in two halves; input %d has "
+                                       "batch %s" % (i, x.shape[0] if x.dim() else "()"))
+            if any(v not in (0.0, 1.0) for v in (t if isinstance(t, (tuple, list)) else (t,))):
+                raise RuntimeError("munit_amd.nsgan_loss: a target is 0 or 1 (the label of binary cross-entropy), got %r "
+                                   "for input %d" % (t, i))
+        nseg = sum(2 if isinstance(t, (tuple, list)) else 1 for t in targets)
+        if nseg > 8:
+            raise RuntimeError("munit_amd.nsgan_loss: at most 8 segments per call, got %d" % nseg)
+        _same_device(*xs)
+        xs = tuple(nhwc(x) if x.dim() == 4 else x.contiguous() for x in xs)
+        segs = _lsgan_segments(xs, targets)
+        out = torch.empty((), device=xs[0].device, dtype=torch.float32)
+        px, pn, pt = _lsgan_arrays(segs)
+        with _on(out):
+            ws = workspace(lib.munit_nsgan_workspace_bytes(len(segs)), out.device)
+            _lib.check(lib.munit_nsgan_fwd(px, pn, pt, len(segs), _p(out), None, _p(ws), ws.numel(), _stream()), "nsgan_fwd")
+        ctx.targets = targets
+        ctx.save_for_backward(*xs)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        xs = ctx.saved_tensors
+        gout = gout.contiguous()
+        dxs = tuple(torch.empty_like(x) for x in xs)
+        segs = _lsgan_segments(xs, ctx.targets)
+        px, pn, pt = _lsgan_arrays(segs)
+        pd = (c_void_p * len(segs))(*[p for p, _, _ in _lsgan_segments(dxs, ctx.targets)])
+        with _on(gout):
+            _lib.check(lib.munit_nsgan_bwd(px, pn, pt, len(segs), _p(gout), pd, _stream()), "nsgan_bwd")
+        return (None,) + dxs
+
+
+def nsgan_loss(outs, targets):
+    """Multi-scale non-saturating GAN loss (networks.py:79-139, gan_type nsgan): sum_i mean(BCE(sigmoid(outs[i]), targets[i]))
+    over whole discriminator outputs, evaluated as mean(softplus(+-x)) (exact where the reference's fp32 sigmoid saturates).
+    targets[i]: 0 or 1, or a pair of them that splits outs[i] at half its batch, as in lsgan_loss.  At most 8 segments."""
+    return _NsganLoss.apply(tuple(tuple(t) if isinstance(t, (tuple, list)) else float(t) for t in targets), *outs)
+
+
 class _ScalarSum(Function):
     """sum of device scalars with unit weights; backward hands the upstream gradient to every
     term unchanged (no kernel)."""

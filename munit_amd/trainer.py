@@ -33,8 +33,10 @@ trainer.py:181-201): two more MsImageDis, output_classifier_sr_a / _b, on the im
 output_domain_classifier_sr_update (simulated -> 0, real -> 1) under their own optimizer output_classif_opt_sr, which takes
 the plain step() as the reference's update does; gen_update adds calc_gen_loss_sr (target 0.5) of the two translations
 with weight output_adv_lambda, forming no classifier weight gradient (the next update's zero_grad would discard it).  The
-multi-scale loss of a discriminator pass is one kernel pair (ops.lsgan_loss).  Either weight without the other is refused;
-fp32, Adam only.  As in the reference, update_learning_rate does not step output_scheduler_sr and save / resume do not carry
+multi-scale loss of a discriminator pass is one kernel pair (ops.lsgan_loss).  dis.gan_type: nsgan (the discriminators'
+non-saturating loss, ops.nsgan_loss inside MsImageDis) needs no code here; together with output_adv_lambda > 0 it is refused,
+since the fooling term is calc_gen_loss_sr, whose nsgan branch raises NameError in the reference.  Either weight without the
+other is refused; fp32, Adam only.  As in the reference, update_learning_rate does not step output_scheduler_sr and save / resume do not carry
 these classifiers either.
 
 Both adaptation levels train data-parallel under the build extension adaptation.data_parallel: 1 (default 0: a process
@@ -658,6 +660,10 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         whether this trainer was constructed with both weights (it then owns the classifiers); update: the check of
         output_domain_classifier_sr_update, which runs whatever the weights of `hp` are."""
         adv = hp["adaptation"].get("output_adv_lambda", 0) > 0
+        if adv and hp.get("dis", {}).get("gan_type") == "nsgan":
+            raise NotImplementedError("munit_amd: dis.gan_type: nsgan cannot run together with adaptation.output_adv_lambda > 0: "
+                                      "the fooling term is MsImageDis.calc_gen_loss_sr, whose nsgan branch names an undefined "
+                                      "variable in the reference (NameError): there is no behaviour to reproduce")
         if (adv or update) and not built:
             raise ValueError("munit_amd: adaptation.output_adv_lambda > 0 needs a trainer constructed with "
                              "adaptation.output_classifier_lambda > 0 and adaptation.output_adv_lambda > 0 (the classifiers "
