@@ -220,44 +220,84 @@ __global__ void mse_bwd_kernel(const float* __restrict__ x, float target, long l
     dx[i] = g * (x[i] - target);
 }
 
-// Multi-scale LSGAN loss (networks.py:117-162 and its callers): sum over segments s of mean((x_s - target_s)^2) in one launch
+// Multi-scale GAN losses (networks.py:79-162 and its callers): sum over segments s of mean(term(x_s, target_s)) in one launch
 // pair.  A segment is any run of floats -- a whole discriminator output or one half of a batched [sim; real] output, which may
 // start at any 4-byte boundary: every access below is a scalar one.  Segment s owns the blocks [start[s], start[s + 1]).
-constexpr int LSGAN_MAX_SEG = 8;
-struct LsganArgs {
-  const float* x[LSGAN_MAX_SEG];
-  float* dx[LSGAN_MAX_SEG];
-  unsigned long long n[LSGAN_MAX_SEG];
-  float target[LSGAN_MAX_SEG];
-  int start[LSGAN_MAX_SEG + 1];
+// What differs between the losses is a `Loss` functor, built once per block from target[s]: the per-element forward term,
+// the per-segment gradient scale, the per-element gradient, the host-side target check and the launch labels.
+constexpr int SEG_MAX = 8;
+struct SegmentArgs {
+  const float* x[SEG_MAX];
+  float* dx[SEG_MAX];
+  unsigned long long n[SEG_MAX];
+  float target[SEG_MAX];
+  int start[SEG_MAX + 1];
   int nseg;
 };
 
-__device__ inline int lsgan_segment(const LsganArgs& a, int block) {
+// LSGAN: term (x - target)^2, any target.
+struct LsganTerm {
+  static constexpr const char* partial_label = "lsgan_partial";
+  static constexpr const char* finish_label = "lsgan_finish";
+  static constexpr const char* bwd_label = "lsgan_bwd";
+  static bool target_ok(float) { return true; }
+  float target;
+  __device__ explicit LsganTerm(float t) : target(t) {}
+  __device__ float term(float x) const {
+    const float d = x - target;
+    return d * d;
+  }
+  __device__ float scale(float gout, unsigned long long n) const { return 2.f * gout / (float)n; }
+  __device__ float grad(float g, float x) const { return g * (x - target); }
+};
+
+// Non-saturating GAN loss (gan_type nsgan): term softplus(z), z = x for target 0 and -x for target 1 -- what
+// binary_cross_entropy(sigmoid(x), target) evaluates, in the form that neither saturates nor meets inf - inf:
+// max(z, 0) + log1p(exp(-|z|)).  target[s] is exactly 0 or 1 here (target_ok, checked on the host).
+__device__ inline float nsgan_softplus(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
+
+__device__ inline float nsgan_sigmoid(float z) {
+  if (z >= 0.f) return 1.f / (1.f + expf(-z));
+  const float e = expf(z);      // z < 0, or NaN (which stays NaN)
+  return e / (1.f + e);
+}
+
+struct NsganTerm {
+  static constexpr const char* partial_label = "nsgan_partial";
+  static constexpr const char* finish_label = "nsgan_finish";
+  static constexpr const char* bwd_label = "nsgan_bwd";
+  static bool target_ok(float t) { return t == 0.f || t == 1.f; }
+  float sign;
+  __device__ explicit NsganTerm(float t) : sign(1.f - 2.f * t) {}
+  __device__ float term(float x) const { return nsgan_softplus(sign * x); }
+  __device__ float scale(float gout, unsigned long long n) const { return sign * (gout / (float)n); }
+  __device__ float grad(float g, float x) const { return g * nsgan_sigmoid(sign * x); }
+};
+
+__device__ inline int segment_of(const SegmentArgs& a, int block) {
   int s = 0;
   while (s + 1 < a.nseg && block >= a.start[s + 1]) ++s;
   return s;
 }
 
-__global__ __launch_bounds__(NT) void lsgan_partial_kernel(LsganArgs a, float* __restrict__ partial) {
+template <class Loss>
+__global__ __launch_bounds__(NT) void segment_partial_kernel(SegmentArgs a, float* __restrict__ partial) {
   __shared__ float red[4];
-  const int s = lsgan_segment(a, blockIdx.x);
+  const int s = segment_of(a, blockIdx.x);
   const float* __restrict__ x = a.x[s];
-  const float target = a.target[s];
+  const Loss loss(a.target[s]);
   const unsigned long long n = a.n[s];
   const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
   float acc = 0.f;
-  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride) {
-    const float d = x[i] - target;
-    acc += d * d;
-  }
+  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride)
+    acc += loss.term(x[i]);
   acc = block_sum256(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // one block: every segment's partials in a fixed order, the mean in double, the segments added in index order
-__global__ __launch_bounds__(NT) void lsgan_finish_kernel(LsganArgs a, const float* __restrict__ partial,
-                                                          float* __restrict__ out, float* __restrict__ seg_out) {
+__global__ __launch_bounds__(NT) void segment_finish_kernel(SegmentArgs a, const float* __restrict__ partial,
+                                                            float* __restrict__ out, float* __restrict__ seg_out) {
   __shared__ float red[4];
   double total = 0.0;
   for (int s = 0; s < a.nseg; ++s) {
@@ -272,54 +312,17 @@ __global__ __launch_bounds__(NT) void lsgan_finish_kernel(LsganArgs a, const flo
   if (threadIdx.x == 0) out[0] = (float)total;
 }
 
-__global__ __launch_bounds__(NT) void lsgan_bwd_kernel(LsganArgs a, const float* __restrict__ gout) {
-  const int s = lsgan_segment(a, blockIdx.x);
+template <class Loss>
+__global__ __launch_bounds__(NT) void segment_bwd_kernel(SegmentArgs a, const float* __restrict__ gout) {
+  const int s = segment_of(a, blockIdx.x);
   const float* __restrict__ x = a.x[s];
   float* __restrict__ dx = a.dx[s];
-  const float target = a.target[s];
+  const Loss loss(a.target[s]);
   const unsigned long long n = a.n[s];
   const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
-  const float g = 2.f * gout[0] / (float)n;
+  const float g = loss.scale(gout[0], n);
   for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride)
-    dx[i] = g * (x[i] - target);
-}
-
-// Multi-scale non-saturating GAN loss (networks.py:79-139, gan_type nsgan): sum over segments s of mean(softplus(z)), z = x
-// for target 0 and -x for target 1 -- what binary_cross_entropy(sigmoid(x), target) evaluates, in the form that neither
-// saturates nor meets inf - inf: max(z, 0) + log1p(exp(-|z|)).  Segments, block ranges and the finishing block are the LSGAN
-// pair's (LsganArgs, lsgan_segment, lsgan_finish_kernel); target[s] is exactly 0 or 1 here (checked on the host).
-__device__ inline float nsgan_softplus(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
-
-__device__ inline float nsgan_sigmoid(float z) {
-  if (z >= 0.f) return 1.f / (1.f + expf(-z));
-  const float e = expf(z);      // z < 0, or NaN (which stays NaN)
-  return e / (1.f + e);
-}
-
-__global__ __launch_bounds__(NT) void nsgan_partial_kernel(LsganArgs a, float* __restrict__ partial) {
-  __shared__ float red[4];
-  const int s = lsgan_segment(a, blockIdx.x);
-  const float* __restrict__ x = a.x[s];
-  const float sign = 1.f - 2.f * a.target[s];
-  const unsigned long long n = a.n[s];
-  const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
-  float acc = 0.f;
-  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride)
-    acc += nsgan_softplus(sign * x[i]);
-  acc = block_sum256(acc, red);
-  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
-__global__ __launch_bounds__(NT) void nsgan_bwd_kernel(LsganArgs a, const float* __restrict__ gout) {
-  const int s = lsgan_segment(a, blockIdx.x);
-  const float* __restrict__ x = a.x[s];
-  float* __restrict__ dx = a.dx[s];
-  const float sign = 1.f - 2.f * a.target[s];
-  const unsigned long long n = a.n[s];
-  const unsigned long long stride = (unsigned long long)(a.start[s + 1] - a.start[s]) * NT;
-  const float g = sign * (gout[0] / (float)n);
-  for (unsigned long long i = (unsigned long long)(blockIdx.x - a.start[s]) * NT + threadIdx.x; i < n; i += stride)
-    dx[i] = g * nsgan_sigmoid(sign * x[i]);
+    dx[i] = loss.grad(g, x[i]);
 }
 
 struct WsumArgs {
@@ -559,7 +562,7 @@ extern "C" int munit_mse_const_bwd(const float* x, float target, size_t n, const
 
 namespace {
 // Blocks of segment s: one per 256 elements, at most an equal share of LOSS_PARTS (so the grid never exceeds LOSS_PARTS).
-int lsgan_fill(LsganArgs& a, const float* const* x, const size_t* n, const float* target, int nseg, float* const* dx) {
+int segment_fill(SegmentArgs& a, const float* const* x, const size_t* n, const float* target, int nseg, float* const* dx) {
   a.nseg = nseg;
   a.start[0] = 0;
   const long long cap = LOSS_PARTS / nseg;
@@ -573,74 +576,72 @@ int lsgan_fill(LsganArgs& a, const float* const* x, const size_t* n, const float
   }
   return a.start[nseg];
 }
+
+size_t segment_workspace_bytes(int nseg) { return (nseg >= 1 && nseg <= SEG_MAX) ? LOSS_PARTS * sizeof(float) : 0; }
+
+// `name` prefixes the error text ("lsgan_fwd", ...); dx is null on the forward side
+template <class Loss>
+int segment_check(const char* name, const float* const* x, const size_t* n, const float* target, int nseg,
+                  float* const* dx) {
+  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= SEG_MAX, "%s: nseg must be 1..%d, got %d", name, SEG_MAX, nseg);
+  for (int s = 0; s < nseg; ++s) {
+    MUNIT_CHECK_ARG(x[s] && (!dx || dx[s]) && n[s] > 0, "%s: segment %d is null or empty", name, s);
+    MUNIT_CHECK_ARG(Loss::target_ok(target[s]), "%s: target %d must be 0 or 1, got %g", name, s, (double)target[s]);
+  }
+  return MUNIT_OK;
+}
+
+template <class Loss>
+int segment_loss_fwd(const char* name, const float* const* x, const size_t* n, const float* target, int nseg, float* out,
+                     float* seg_out, void* ws, size_t ws_bytes, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x && n && target && out && ws, "%s: null pointer", name);
+  if (const int rc = segment_check<Loss>(name, x, n, target, nseg, nullptr)) return rc;
+  MUNIT_CHECK_ARG(ws_bytes >= segment_workspace_bytes(nseg), "%s: workspace too small", name);
+  SegmentArgs a{};
+  const int blocks = segment_fill(a, x, n, target, nseg, nullptr);
+  float* partial = reinterpret_cast<float*>(ws);
+  hipLaunchKernelGGL(segment_partial_kernel<Loss>, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, partial);
+  MUNIT_CHECK_LAUNCH(Loss::partial_label);
+  hipLaunchKernelGGL(segment_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, partial, out, seg_out);
+  MUNIT_CHECK_LAUNCH(Loss::finish_label);
+  return MUNIT_OK;
+}
+
+template <class Loss>
+int segment_loss_bwd(const char* name, const float* const* x, const size_t* n, const float* target, int nseg,
+                     const float* gout, float* const* dx, munit_stream_t stream) {
+  MUNIT_CHECK_ARG(x && n && target && gout && dx, "%s: null pointer", name);
+  if (const int rc = segment_check<Loss>(name, x, n, target, nseg, dx)) return rc;
+  SegmentArgs a{};
+  const int blocks = segment_fill(a, x, n, target, nseg, dx);
+  hipLaunchKernelGGL(segment_bwd_kernel<Loss>, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, gout);
+  MUNIT_CHECK_LAUNCH(Loss::bwd_label);
+  return MUNIT_OK;
+}
 }  // namespace
 
-extern "C" size_t munit_lsgan_workspace_bytes(int nseg) {
-  return (nseg >= 1 && nseg <= LSGAN_MAX_SEG) ? LOSS_PARTS * sizeof(float) : 0;
-}
+extern "C" size_t munit_lsgan_workspace_bytes(int nseg) { return segment_workspace_bytes(nseg); }
 
 extern "C" int munit_lsgan_fwd(const float* const* x, const size_t* n, const float* target, int nseg, float* out,
                                float* seg_out, void* ws, size_t ws_bytes, munit_stream_t stream) {
-  MUNIT_CHECK_ARG(x && n && target && out && ws, "lsgan_fwd: null pointer");
-  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "lsgan_fwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
-  for (int s = 0; s < nseg; ++s) MUNIT_CHECK_ARG(x[s] && n[s] > 0, "lsgan_fwd: segment %d is null or empty", s);
-  MUNIT_CHECK_ARG(ws_bytes >= munit_lsgan_workspace_bytes(nseg), "lsgan_fwd: workspace too small");
-  LsganArgs a{};
-  const int blocks = lsgan_fill(a, x, n, target, nseg, nullptr);
-  float* partial = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(lsgan_partial_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, partial);
-  MUNIT_CHECK_LAUNCH("lsgan_partial");
-  hipLaunchKernelGGL(lsgan_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, partial, out, seg_out);
-  MUNIT_CHECK_LAUNCH("lsgan_finish");
-  return MUNIT_OK;
+  return segment_loss_fwd<LsganTerm>("lsgan_fwd", x, n, target, nseg, out, seg_out, ws, ws_bytes, stream);
 }
 
 extern "C" int munit_lsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
                                float* const* dx, munit_stream_t stream) {
-  MUNIT_CHECK_ARG(x && n && target && gout && dx, "lsgan_bwd: null pointer");
-  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "lsgan_bwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
-  for (int s = 0; s < nseg; ++s) MUNIT_CHECK_ARG(x[s] && dx[s] && n[s] > 0, "lsgan_bwd: segment %d is null or empty", s);
-  LsganArgs a{};
-  const int blocks = lsgan_fill(a, x, n, target, nseg, dx);
-  hipLaunchKernelGGL(lsgan_bwd_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, gout);
-  MUNIT_CHECK_LAUNCH("lsgan_bwd");
-  return MUNIT_OK;
+  return segment_loss_bwd<LsganTerm>("lsgan_bwd", x, n, target, nseg, gout, dx, stream);
 }
 
-extern "C" size_t munit_nsgan_workspace_bytes(int nseg) { return munit_lsgan_workspace_bytes(nseg); }
+extern "C" size_t munit_nsgan_workspace_bytes(int nseg) { return segment_workspace_bytes(nseg); }
 
 extern "C" int munit_nsgan_fwd(const float* const* x, const size_t* n, const float* target, int nseg, float* out,
                                float* seg_out, void* ws, size_t ws_bytes, munit_stream_t stream) {
-  MUNIT_CHECK_ARG(x && n && target && out && ws, "nsgan_fwd: null pointer");
-  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "nsgan_fwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
-  for (int s = 0; s < nseg; ++s) {
-    MUNIT_CHECK_ARG(x[s] && n[s] > 0, "nsgan_fwd: segment %d is null or empty", s);
-    MUNIT_CHECK_ARG(target[s] == 0.f || target[s] == 1.f, "nsgan_fwd: target %d must be 0 or 1, got %g", s, (double)target[s]);
-  }
-  MUNIT_CHECK_ARG(ws_bytes >= munit_nsgan_workspace_bytes(nseg), "nsgan_fwd: workspace too small");
-  LsganArgs a{};
-  const int blocks = lsgan_fill(a, x, n, target, nseg, nullptr);
-  float* partial = reinterpret_cast<float*>(ws);
-  hipLaunchKernelGGL(nsgan_partial_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, partial);
-  MUNIT_CHECK_LAUNCH("nsgan_partial");
-  hipLaunchKernelGGL(lsgan_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, a, partial, out, seg_out);
-  MUNIT_CHECK_LAUNCH("nsgan_finish");
-  return MUNIT_OK;
+  return segment_loss_fwd<NsganTerm>("nsgan_fwd", x, n, target, nseg, out, seg_out, ws, ws_bytes, stream);
 }
 
 extern "C" int munit_nsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
                                float* const* dx, munit_stream_t stream) {
-  MUNIT_CHECK_ARG(x && n && target && gout && dx, "nsgan_bwd: null pointer");
-  MUNIT_CHECK_ARG(nseg >= 1 && nseg <= LSGAN_MAX_SEG, "nsgan_bwd: nseg must be 1..%d, got %d", LSGAN_MAX_SEG, nseg);
-  for (int s = 0; s < nseg; ++s) {
-    MUNIT_CHECK_ARG(x[s] && dx[s] && n[s] > 0, "nsgan_bwd: segment %d is null or empty", s);
-    MUNIT_CHECK_ARG(target[s] == 0.f || target[s] == 1.f, "nsgan_bwd: target %d must be 0 or 1, got %g", s, (double)target[s]);
-  }
-  LsganArgs a{};
-  const int blocks = lsgan_fill(a, x, n, target, nseg, dx);
-  hipLaunchKernelGGL(nsgan_bwd_kernel, dim3(blocks), dim3(NT), 0, (hipStream_t)stream, a, gout);
-  MUNIT_CHECK_LAUNCH("nsgan_bwd");
-  return MUNIT_OK;
+  return segment_loss_bwd<NsganTerm>("nsgan_bwd", x, n, target, nseg, gout, dx, stream);
 }
 
 extern "C" int munit_weighted_sum(const float* const* terms, const float* w, int n, float* out,

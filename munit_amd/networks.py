@@ -573,28 +573,40 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
                 x = self.downsample(x)
         return outputs
 
+    def _pair(self, first, second):
+        """The discriminator's outputs for a (first -> 0, second -> 1) pair, as (outs, targets) of ops.lsgan_loss /
+        ops.nsgan_loss.  BATCH_DIS_PAIR and equal shapes: one pass over [first; second] -- every layer of the discriminator
+        is per-sample (no batch statistics), so the two halves of each output are exactly the reference's outs0 / outs1
+        (networks.py:84-91) -- half the launches, and the small scales (16x16 ... 4x4 maps), which cannot fill the chip at
+        B = 8, cost about the same at 2 B; every target is the pair (0.0, 1.0).  Else two passes, outs0 + outs1."""
+        if BATCH_DIS_PAIR and first.shape == second.shape and first.dtype == second.dtype:
+            nb = first.shape[0]
+            n0 = len(ops.MASK_SINK) if ops.MASK_SINK is not None else 0
+            outs = self.forward(torch.cat([ops.nhwc(first), ops.nhwc(second)], 0))
+            if ops.MASK_SINK is not None:   # parity harness: hand the recorded LeakyReLU branches over in the reference's order
+                rec = ops.MASK_SINK[n0:]    # (all layers of the first pass, then all layers of the second pass)
+                ops.MASK_SINK[n0:] = [m[:nb] for m in rec] + [m[nb:] for m in rec]
+            return outs, [(0.0, 1.0)] * len(outs)
+        outs0 = self.forward(first)
+        outs1 = self.forward(second)
+        return outs0 + outs1, [0.0] * len(outs0) + [1.0] * len(outs1)
+
     def calc_dis_loss(self, input_fake, input_real):
         if self.gan_type == "nsgan":        # networks.py:92-98: fake -> 0, real -> 1
-            return self._nsgan_pair(input_fake, input_real)
+            return self._multi_scale(ops.nsgan_loss, *self._pair(input_fake, input_real))
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
+        # lsgan here and in calc_gen_loss stays on ops.mse_const per scale and half, summed by ops.scalar_sum in this order:
+        # ops.lsgan_loss would change the launches and the summation order of the benchmarked dis_update / gen_update
+        outs, targets = self._pair(input_fake, input_real)
         terms = []
-        if BATCH_DIS_PAIR and input_fake.shape == input_real.shape and input_fake.dtype == input_real.dtype:
-            # one pass over [fake; real]: every layer of the discriminator is per-sample (no batch statistics), so the two
-            # halves of each output are exactly the reference's outs0 / outs1 (networks.py:84-91) -- half the launches, and the
-            # small scales (16x16 ... 4x4 maps), which cannot fill the chip at B = 8, cost about the same at 2 B
+        if isinstance(targets[0], tuple):
             nb = input_fake.shape[0]
-            n0 = len(ops.MASK_SINK) if ops.MASK_SINK is not None else 0
-            outs = self.forward(torch.cat([ops.nhwc(input_fake), ops.nhwc(input_real)], 0))
-            if ops.MASK_SINK is not None:   # parity harness: hand the recorded LeakyReLU branches over in the reference's order
-                rec = ops.MASK_SINK[n0:]    # (all layers of the fake pass, then all layers of the real pass)
-                ops.MASK_SINK[n0:] = [m[:nb] for m in rec] + [m[nb:] for m in rec]
             for out in outs:
                 terms += [ops.mse_const(out[:nb], 0.0), ops.mse_const(out[nb:], 1.0)]
-            return ops.scalar_sum(terms)
-        outs0 = self.forward(input_fake)
-        outs1 = self.forward(input_real)
-        for out0, out1 in zip(outs0, outs1):
-            terms += [ops.mse_const(out0, 0.0), ops.mse_const(out1, 1.0)]
+        else:
+            k = len(outs) // 2
+            for out0, out1 in zip(outs[:k], outs[k:]):
+                terms += [ops.mse_const(out0, 0.0), ops.mse_const(out1, 1.0)]
         return ops.scalar_sum(terms)
 
     def calc_gen_loss(self, input_fake):
@@ -602,59 +614,24 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         if self.gan_type == "nsgan":        # networks.py:110-112: fake -> 1
             return self._multi_scale(ops.nsgan_loss, outs0, [1.0] * len(outs0))
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
-        return ops.scalar_sum([ops.mse_const(out0, 1.0) for out0 in outs0])
-
-    @staticmethod
-    def _lsgan(outs, targets):
-        """ops.lsgan_loss over all scales in one launch pair (in groups of 8 segments when there are more scales than that)"""
-        per = 2 if isinstance(targets[0], tuple) else 1
-        step = max(1, 8 // per)
-        if len(outs) <= step:
-            return ops.lsgan_loss(outs, targets)
-        return ops.scalar_sum([ops.lsgan_loss(outs[i:i + step], targets[i:i + step]) for i in range(0, len(outs), step)])
+        return ops.scalar_sum([ops.mse_const(out0, 1.0) for out0 in outs0])     # not ops.lsgan_loss: see calc_dis_loss
 
     @staticmethod
     def _multi_scale(loss, outs, targets):
-        """_lsgan's grouping for another loss of the same signature (ops.nsgan_loss)"""
+        """loss (ops.lsgan_loss / ops.nsgan_loss) over all scales in one launch pair (in groups of 8 segments when there are
+        more scales than that)"""
         per = 2 if isinstance(targets[0], tuple) else 1
         step = max(1, 8 // per)
         if len(outs) <= step:
             return loss(outs, targets)
         return ops.scalar_sum([loss(outs[i:i + step], targets[i:i + step]) for i in range(0, len(outs), step)])
 
-    def _nsgan_pair(self, input0, input1):
-        """nsgan of calc_dis_loss / calc_dis_loss_sr (networks.py:92-98, 130-136): first argument -> 0, second -> 1, summed
-        over the scales.  One pass over [first; second] under calc_dis_loss's condition, the recorded LeakyReLU branches handed
-        over in the reference's order; the loss of all scales and both halves is one kernel pair (ops.nsgan_loss)."""
-        if BATCH_DIS_PAIR and input0.shape == input1.shape and input0.dtype == input1.dtype:
-            nb = input0.shape[0]
-            n0 = len(ops.MASK_SINK) if ops.MASK_SINK is not None else 0
-            outs = self.forward(torch.cat([ops.nhwc(input0), ops.nhwc(input1)], 0))
-            if ops.MASK_SINK is not None:
-                rec = ops.MASK_SINK[n0:]
-                ops.MASK_SINK[n0:] = [m[:nb] for m in rec] + [m[nb:] for m in rec]
-            return self._multi_scale(ops.nsgan_loss, outs, [(0.0, 1.0)] * len(outs))
-        outs0 = self.forward(input0)
-        outs1 = self.forward(input1)
-        return self._multi_scale(ops.nsgan_loss, outs0 + outs1, [0.0] * len(outs0) + [1.0] * len(outs1))
-
     def calc_dis_loss_sr(self, input_sim, input_real):
-        """networks.py:117-139 (LSGAN): simulated -> 0, real -> 1, summed over the scales.  One pass over [sim; real] under
-        calc_dis_loss's condition; the loss of all scales and both halves is one kernel pair (ops.lsgan_loss)."""
-        if self.gan_type == "nsgan":
-            return self._nsgan_pair(input_sim, input_real)
-        assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
-        if BATCH_DIS_PAIR and input_sim.shape == input_real.shape and input_sim.dtype == input_real.dtype:
-            nb = input_sim.shape[0]
-            n0 = len(ops.MASK_SINK) if ops.MASK_SINK is not None else 0
-            outs = self.forward(torch.cat([ops.nhwc(input_sim), ops.nhwc(input_real)], 0))
-            if ops.MASK_SINK is not None:   # parity harness: the reference's order (the simulated pass, then the real pass)
-                rec = ops.MASK_SINK[n0:]
-                ops.MASK_SINK[n0:] = [m[:nb] for m in rec] + [m[nb:] for m in rec]
-            return self._lsgan(outs, [(0.0, 1.0)] * len(outs))
-        outs0 = self.forward(input_sim)
-        outs1 = self.forward(input_real)
-        return self._lsgan(outs0 + outs1, [0.0] * len(outs0) + [1.0] * len(outs1))
+        """networks.py:117-139: simulated -> 0, real -> 1, summed over the scales.  One pass over [sim; real] under _pair's
+        condition; the loss of all scales and both halves is one kernel pair (ops.lsgan_loss / ops.nsgan_loss)."""
+        assert self.gan_type in ("lsgan", "nsgan"), "Unsupported GAN type: {}".format(self.gan_type)
+        loss = ops.nsgan_loss if self.gan_type == "nsgan" else ops.lsgan_loss
+        return self._multi_scale(loss, *self._pair(input_sim, input_real))
 
     def calc_gen_loss_sr(self, input_fake):
         """networks.py:141-162 (LSGAN; the reference's nsgan branch there names an undefined variable): target 0.5."""
@@ -663,7 +640,7 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
                                       "branch names an undefined variable (out1, networks.py:155) and raises NameError")
         outs0 = self.forward(input_fake)
         assert self.gan_type == "lsgan", "Unsupported GAN type: {}".format(self.gan_type)
-        return self._lsgan(outs0, [0.5] * len(outs0))
+        return self._multi_scale(ops.lsgan_loss, outs0, [0.5] * len(outs0))
 
 
 # --------------------------------------------------------------------------------------

@@ -875,7 +875,7 @@ def mse_const(x, target):
     return _MseConst.apply(x, float(target))
 
 
-def _lsgan_segments(xs, targets):
+def _segments(xs, targets):
     """(pointer, elements, target) of every segment: a number targets the whole tensor, a pair its two batch halves"""
     segs = []
     for x, t in zip(xs, targets):
@@ -887,44 +887,56 @@ def _lsgan_segments(xs, targets):
     return segs
 
 
-def _lsgan_arrays(segs):
+def _segment_arrays(segs):
     n = len(segs)
     return ((c_void_p * n)(*[p for p, _, _ in segs]), (ctypes.c_size_t * n)(*[m for _, m, _ in segs]),
             (c_float * n)(*[t for _, _, t in segs]))
 
 
-class _LsganLoss(Function):
-    """sum over the tensors (and, for a pair target, over the two batch halves of a tensor) of mean((x - target)^2): one
-    munit_lsgan_fwd, one munit_lsgan_bwd that writes every tensor's gradient whole.  No view of a tensor enters the tape."""
+# One segment loss: the name its messages carry, its C entry points (looked up on the library at every call) and whether a
+# target is a binary cross-entropy label.
+_SegmentKind = collections.namedtuple("_SegmentKind", "name workspace_bytes fwd bwd binary_targets")
+_LSGAN = _SegmentKind("lsgan_loss", "munit_lsgan_workspace_bytes", "munit_lsgan_fwd", "munit_lsgan_bwd", False)
+_NSGAN = _SegmentKind("nsgan_loss", "munit_nsgan_workspace_bytes", "munit_nsgan_fwd", "munit_nsgan_bwd", True)
+
+
+class _SegmentLoss(Function):
+    """sum over the tensors (and, for a pair target, over the two batch halves of a tensor) of the mean of kind's term --
+    (x - target)^2 for lsgan; softplus(z), z = x for target 0 and -x for target 1, for nsgan: one forward call, one backward
+    call that writes every tensor's gradient whole.  No view of a tensor enters the tape."""
 
     @staticmethod
-    def forward(ctx, targets, *xs):
+    def forward(ctx, kind, targets, *xs):
         lib = _lib.load()
+        who = "munit_amd." + kind.name
         if len(xs) == 0 or len(xs) != len(targets):
-            raise RuntimeError("munit_amd.lsgan_loss: one target per tensor expected (%d tensors, %d targets)"
-                               % (len(xs), len(targets)))
+            raise RuntimeError("%s: one target per tensor expected (%d tensors, %d targets)" % (who, len(xs), len(targets)))
         for i, (x, t) in enumerate(zip(xs, targets)):
-            _require(x, "lsgan_loss input %d" % i)
+            _require(x, "%s input %d" % (kind.name, i))
             if x.numel() == 0:
-                raise RuntimeError("munit_amd.lsgan_loss: input %d is empty" % i)
+                raise RuntimeError("%s: input %d is empty" % (who, i))
             if isinstance(t, (tuple, list)):
                 if len(t) != 2:
-                    raise RuntimeError("munit_amd.lsgan_loss: a pair target holds two numbers, got %r" % (t,))
+                    raise RuntimeError("%s: a pair target holds two numbers, got %r" % (who, t))
                 if x.dim() == 0 or x.shape[0] % 2:
-                    raise RuntimeError("munit_amd.lsgan_loss: a pair target splits the batch in two halves; input %d has "
-                                       "batch %s" % (i, x.shape[0] if x.dim() else "()"))
+                    raise RuntimeError("%s: a pair target splits the batch in two halves; input %d has batch %s"
+                                       % (who, i, x.shape[0] if x.dim() else "()"))
+            if kind.binary_targets and any(v not in (0.0, 1.0) for v in (t if isinstance(t, (tuple, list)) else (t,))):
+                raise RuntimeError("%s: a target is 0 or 1 (the label of binary cross-entropy), got %r for input %d"
+                                   % (who, t, i))
         nseg = sum(2 if isinstance(t, (tuple, list)) else 1 for t in targets)
         if nseg > 8:
-            raise RuntimeError("munit_amd.lsgan_loss: at most 8 segments per call, got %d" % nseg)
+            raise RuntimeError("%s: at most 8 segments per call, got %d" % (who, nseg))
         _same_device(*xs)
         xs = tuple(nhwc(x) if x.dim() == 4 else x.contiguous() for x in xs)
-        segs = _lsgan_segments(xs, targets)
+        segs = _segments(xs, targets)
         out = torch.empty((), device=xs[0].device, dtype=torch.float32)
-        px, pn, pt = _lsgan_arrays(segs)
+        px, pn, pt = _segment_arrays(segs)
         with _on(out):
-            ws = workspace(lib.munit_lsgan_workspace_bytes(len(segs)), out.device)
-            _lib.check(lib.munit_lsgan_fwd(px, pn, pt, len(segs), _p(out), None, _p(ws), ws.numel(), _stream()), "lsgan_fwd")
-        ctx.targets = targets
+            ws = workspace(getattr(lib, kind.workspace_bytes)(len(segs)), out.device)
+            _lib.check(getattr(lib, kind.fwd)(px, pn, pt, len(segs), _p(out), None, _p(ws), ws.numel(), _stream()),
+                       kind.fwd[len("munit_"):])
+        ctx.kind, ctx.targets = kind, targets
         ctx.save_for_backward(*xs)
         return out
 
@@ -934,79 +946,31 @@ class _LsganLoss(Function):
         xs = ctx.saved_tensors
         gout = gout.contiguous()
         dxs = tuple(torch.empty_like(x) for x in xs)
-        segs = _lsgan_segments(xs, ctx.targets)
-        px, pn, pt = _lsgan_arrays(segs)
-        pd = (c_void_p * len(segs))(*[p for p, _, _ in _lsgan_segments(dxs, ctx.targets)])
+        segs = _segments(xs, ctx.targets)
+        px, pn, pt = _segment_arrays(segs)
+        pd = (c_void_p * len(segs))(*[p for p, _, _ in _segments(dxs, ctx.targets)])
         with _on(gout):
-            _lib.check(lib.munit_lsgan_bwd(px, pn, pt, len(segs), _p(gout), pd, _stream()), "lsgan_bwd")
-        return (None,) + dxs
+            _lib.check(getattr(lib, ctx.kind.bwd)(px, pn, pt, len(segs), _p(gout), pd, _stream()),
+                       ctx.kind.bwd[len("munit_"):])
+        return (None, None) + dxs
+
+
+def _segment_loss(kind, outs, targets):
+    return _SegmentLoss.apply(kind, tuple(tuple(t) if isinstance(t, (tuple, list)) else float(t) for t in targets), *outs)
 
 
 def lsgan_loss(outs, targets):
     """Multi-scale LSGAN loss (networks.py:117-162): sum_i mean((outs[i] - targets[i])^2) over whole discriminator outputs.
     targets[i]: one number, or a pair (t_first, t_second) that splits outs[i] at half its batch (the [sim; real] output of
     a batched pass; NHWC, so both halves are contiguous).  At most 8 segments (a pair counts twice) per call."""
-    return _LsganLoss.apply(tuple(tuple(t) if isinstance(t, (tuple, list)) else float(t) for t in targets), *outs)
-
-
-class _NsganLoss(Function):
-    """sum over the tensors (and, for a pair target, over the two batch halves of a tensor) of mean(softplus(z)), z = x for
-    target 0 and -x for target 1: one munit_nsgan_fwd, one munit_nsgan_bwd that writes every tensor's gradient whole.  No view
-    of a tensor enters the tape."""
-
-    @staticmethod
-    def forward(ctx, targets, *xs):
-        lib = _lib.load()
-        if len(xs) == 0 or len(xs) != len(targets):
-            raise RuntimeError("munit_amd.nsgan_loss: one target per tensor expected (%d tensors, %d targets)"
-                               % (len(xs), len(targets)))
-        for i, (x, t) in enumerate(zip(xs, targets)):
-            _require(x, "nsgan_loss input %d" % i)
-            if x.numel() == 0:
-                raise RuntimeError("munit_amd.nsgan_loss: input %d is empty" % i)
-            if isinstance(t, (tuple, list)):
-                if len(t) != 2:
-                    raise RuntimeError("munit_amd.nsgan_loss: a pair target holds two numbers, got %r" % (t,))
-                if x.dim() == 0 or x.shape[0] % 2:
-                    raise RuntimeError("munit_amd.nsgan_loss: a pair target splits the batch in two halves; input %d has "
-                                       "batch %s" % (i, x.shape[0] if x.dim() else "()"))
-            if any(v not in (0.0, 1.0) for v in (t if isinstance(t, (tuple, list)) else (t,))):
-                raise RuntimeError("munit_amd.nsgan_loss: a target is 0 or 1 (the label of binary cross-entropy), got %r "
-                                   "for input %d" % (t, i))
-        nseg = sum(2 if isinstance(t, (tuple, list)) else 1 for t in targets)
-        if nseg > 8:
-            raise RuntimeError("munit_amd.nsgan_loss: at most 8 segments per call, got %d" % nseg)
-        _same_device(*xs)
-        xs = tuple(nhwc(x) if x.dim() == 4 else x.contiguous() for x in xs)
-        segs = _lsgan_segments(xs, targets)
-        out = torch.empty((), device=xs[0].device, dtype=torch.float32)
-        px, pn, pt = _lsgan_arrays(segs)
-        with _on(out):
-            ws = workspace(lib.munit_nsgan_workspace_bytes(len(segs)), out.device)
-            _lib.check(lib.munit_nsgan_fwd(px, pn, pt, len(segs), _p(out), None, _p(ws), ws.numel(), _stream()), "nsgan_fwd")
-        ctx.targets = targets
-        ctx.save_for_backward(*xs)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = _lib.load()
-        xs = ctx.saved_tensors
-        gout = gout.contiguous()
-        dxs = tuple(torch.empty_like(x) for x in xs)
-        segs = _lsgan_segments(xs, ctx.targets)
-        px, pn, pt = _lsgan_arrays(segs)
-        pd = (c_void_p * len(segs))(*[p for p, _, _ in _lsgan_segments(dxs, ctx.targets)])
-        with _on(gout):
-            _lib.check(lib.munit_nsgan_bwd(px, pn, pt, len(segs), _p(gout), pd, _stream()), "nsgan_bwd")
-        return (None,) + dxs
+    return _segment_loss(_LSGAN, outs, targets)
 
 
 def nsgan_loss(outs, targets):
     """Multi-scale non-saturating GAN loss (networks.py:79-139, gan_type nsgan): sum_i mean(BCE(sigmoid(outs[i]), targets[i]))
     over whole discriminator outputs, evaluated as mean(softplus(+-x)) (exact where the reference's fp32 sigmoid saturates).
     targets[i]: 0 or 1, or a pair of them that splits outs[i] at half its batch, as in lsgan_loss.  At most 8 segments."""
-    return _NsganLoss.apply(tuple(tuple(t) if isinstance(t, (tuple, list)) else float(t) for t in targets), *outs)
+    return _segment_loss(_NSGAN, outs, targets)
 
 
 class _ScalarSum(Function):
@@ -1489,34 +1453,50 @@ def _xch_all_reduce(xch):
     dist.all_reduce(xch)
 
 
-class _BatchNormDP(Function):
-    """_BatchNorm with statistics over `world` ranks of equal batches (include/munit_hip.h, munit_batchnorm_dp_*): local
-    reduction into the rank's row of the exchange buffer, all-reduce, merge + apply; the backward likewise.  dgamma / dbeta
-    receive the LOCAL sums: the optimizer's gradient exchange averages them like every other weight gradient."""
+def _bn_operands(x, gamma, beta, running_mean, running_var):
+    """the operand check of every batch_norm form; returns (x as NHWC, b, c, h, w)"""
+    _require(x, "batch-norm input")
+    x = nhwc(x)
+    b, c, h, w = x.shape
+    for t, nm in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _require(t, "batch-norm " + nm)
+        if tuple(t.shape) != (c,) or not t.is_contiguous():
+            raise RuntimeError("munit_amd.batch_norm: %s must be a contiguous (%d,) tensor" % (nm, c))
+    _same_device(x, gamma, beta, running_mean, running_var)
+    return x, b, c, h, w
+
+
+class _BatchNorm(Function):
+    """Training-mode nn.BatchNorm2d (+ReLU).  running_mean / running_var are updated in place by the forward kernel.
+    need_weight_grads False: backward forms dx only (gen_update: the classifier's weight gradients would be zeroed unused).
+    world > 1: statistics over `world` ranks of equal batches (include/munit_hip.h, munit_batchnorm_dp_*): local reduction
+    into the rank's row of the exchange buffer, all-reduce, merge + apply; the backward likewise.  dgamma / dbeta receive the
+    LOCAL sums: the optimizer's gradient exchange averages them like every other weight gradient."""
     @staticmethod
     @_guarded
     def forward(ctx, x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads, world, rank):
-        _require(x, "batch-norm input")
+        x, b, c, h, w = _bn_operands(x, gamma, beta, running_mean, running_var)
         lib = _lib.load()
-        x = nhwc(x)
-        b, c, h, w = x.shape
-        for t, nm in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
-            _require(t, "batch-norm " + nm)
-            if tuple(t.shape) != (c,) or not t.is_contiguous():
-                raise RuntimeError("munit_amd.batch_norm: %s must be a contiguous (%d,) tensor" % (nm, c))
-        _same_device(x, gamma, beta, running_mean, running_var)
+        dp = world > 1
         y = torch.empty_like(x)
         mean = torch.empty(2 * c, device=x.device, dtype=torch.float32)      # high parts, then low parts
-        rstd = torch.empty(2 * c, device=x.device, dtype=torch.float32)      # likewise: the backward cancels with few rows
-        xch = torch.empty(world * 3 * c, device=x.device, dtype=torch.float32)
-        ws = workspace(lib.munit_batchnorm_dp_workspace_bytes(c), x.device)
+        # across ranks rstd has both parts too: the backward cancels with few rows
+        rstd = torch.empty(2 * c if dp else c, device=x.device, dtype=torch.float32)
         relu = int(bool(relu))
-        _lib.check(lib.munit_batchnorm_dp_stats_local(_p(x), b * h * w, c, world, rank, _p(xch), xch.numel(), _p(ws),
-                                                      ws.numel(), _stream()), "batchnorm_dp_stats_local")
-        _xch_all_reduce(xch)
-        _lib.check(lib.munit_batchnorm_dp_fwd_apply(_p(x), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
-                                                    b * h * w, c, world, _p(xch), xch.numel(), _p(gamma), _p(beta), relu,
-                                                    c_float(eps), c_float(momentum), _stream()), "batchnorm_dp_fwd_apply")
+        if dp:
+            xch = torch.empty(world * 3 * c, device=x.device, dtype=torch.float32)
+            ws = workspace(lib.munit_batchnorm_dp_workspace_bytes(c), x.device)
+            _lib.check(lib.munit_batchnorm_dp_stats_local(_p(x), b * h * w, c, world, rank, _p(xch), xch.numel(), _p(ws),
+                                                          ws.numel(), _stream()), "batchnorm_dp_stats_local")
+            _xch_all_reduce(xch)
+            _lib.check(lib.munit_batchnorm_dp_fwd_apply(_p(x), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var),
+                                                        b * h * w, c, world, _p(xch), xch.numel(), _p(gamma), _p(beta), relu,
+                                                        c_float(eps), c_float(momentum), _stream()), "batchnorm_dp_fwd_apply")
+        else:
+            ws = workspace(lib.munit_batchnorm_workspace_bytes(c), x.device)
+            _lib.check(lib.munit_batchnorm_fwd(_p(x), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var), b * h * w,
+                                               c, _p(gamma), _p(beta), relu, 0, c_float(eps), c_float(momentum), _p(ws),
+                                               ws.numel(), _stream()), "batchnorm_fwd")
         ctx.relu, ctx.world, ctx.rank = relu, world, rank
         ctx.want = bool(need_weight_grads)
         ctx.gbuf = getattr(gamma, "_munit_grad", None)
@@ -1540,76 +1520,27 @@ class _BatchNormDP(Function):
         if want:
             dgamma = ctx.gbuf if into else torch.empty_like(gamma)
             dbeta = ctx.bbuf if into else torch.empty_like(gamma)
-        xch = torch.empty(ctx.world * 4 * c, device=x.device, dtype=torch.float32)     # two sums, each as two floats
-        ws = workspace(lib.munit_batchnorm_dp_workspace_bytes(c), x.device)
-        _lib.check(lib.munit_batchnorm_dp_bwd_local(_p(x), _p(dy), _p(y), _p(mean), _p(rstd), b * h * w, c, ctx.relu,
-                                                    ctx.world, ctx.rank, _p(xch), xch.numel(), _p(ws), ws.numel(), _stream()),
-                   "batchnorm_dp_bwd_local")
-        _xch_all_reduce(xch)       # need_weight_grads False forms dx only, but still takes part in the exchange
-        _lib.check(lib.munit_batchnorm_dp_bwd_finish(_p(x), _p(dy), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma),
-                                                     _p(dbeta), c_float(1.0 if into else 0.0), b * h * w, c, ctx.relu,
-                                                     ctx.world, ctx.rank, _p(xch), xch.numel(), _p(ws), ws.numel(), _stream()),
-                   "batchnorm_dp_bwd_finish")
+        beta = c_float(1.0 if into else 0.0)
+        if ctx.world > 1:
+            xch = torch.empty(ctx.world * 4 * c, device=x.device, dtype=torch.float32)     # two sums, each as two floats
+            ws = workspace(lib.munit_batchnorm_dp_workspace_bytes(c), x.device)
+            _lib.check(lib.munit_batchnorm_dp_bwd_local(_p(x), _p(dy), _p(y), _p(mean), _p(rstd), b * h * w, c, ctx.relu,
+                                                        ctx.world, ctx.rank, _p(xch), xch.numel(), _p(ws), ws.numel(),
+                                                        _stream()), "batchnorm_dp_bwd_local")
+            _xch_all_reduce(xch)       # need_weight_grads False forms dx only, but still takes part in the exchange
+            _lib.check(lib.munit_batchnorm_dp_bwd_finish(_p(x), _p(dy), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dx),
+                                                         _p(dgamma), _p(dbeta), beta, b * h * w, c, ctx.relu, ctx.world,
+                                                         ctx.rank, _p(xch), xch.numel(), _p(ws), ws.numel(), _stream()),
+                       "batchnorm_dp_bwd_finish")
+        else:
+            ws = workspace(lib.munit_batchnorm_workspace_bytes(c), x.device)
+            _lib.check(lib.munit_batchnorm_bwd(_p(x), _p(dy), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma),
+                                               _p(dbeta), beta, b * h * w, c, ctx.relu, _p(ws), ws.numel(), _stream()),
+                       "batchnorm_bwd")
         tail = (None,) * 8
         if into or not want:
             return (dx, None, None) + tail
         return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None) + tail
-
-
-class _BatchNorm(Function):
-    """Training-mode nn.BatchNorm2d (+ReLU).  running_mean / running_var are updated in place by the forward kernel.
-    need_weight_grads False: backward forms dx only (gen_update: the classifier's weight gradients would be zeroed unused)."""
-    @staticmethod
-    @_guarded
-    def forward(ctx, x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads):
-        _require(x, "batch-norm input")
-        lib = _lib.load()
-        x = nhwc(x)
-        b, c, h, w = x.shape
-        for t, nm in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
-            _require(t, "batch-norm " + nm)
-            if tuple(t.shape) != (c,) or not t.is_contiguous():
-                raise RuntimeError("munit_amd.batch_norm: %s must be a contiguous (%d,) tensor" % (nm, c))
-        _same_device(x, gamma, beta, running_mean, running_var)
-        y = torch.empty_like(x)
-        mean = torch.empty(2 * c, device=x.device, dtype=torch.float32)      # high parts, then low parts
-        rstd = torch.empty(c, device=x.device, dtype=torch.float32)
-        ws = workspace(lib.munit_batchnorm_workspace_bytes(c), x.device)
-        relu = int(bool(relu))
-        _lib.check(lib.munit_batchnorm_fwd(_p(x), _p(y), _p(mean), _p(rstd), _p(running_mean), _p(running_var), b * h * w, c,
-                                           _p(gamma), _p(beta), relu, 0, c_float(eps), c_float(momentum), _p(ws), ws.numel(),
-                                           _stream()), "batchnorm_fwd")
-        ctx.relu = relu
-        ctx.want = bool(need_weight_grads)
-        ctx.gbuf = getattr(gamma, "_munit_grad", None)
-        ctx.bbuf = getattr(beta, "_munit_grad", None)
-        ctx.save_for_backward(x, y if relu else None, gamma, mean, rstd)
-        if DANN_SINK is not None and relu:
-            DANN_SINK.append(y > 0)
-        return y
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, y, gamma, mean, rstd = ctx.saved_tensors
-        dy = nhwc(dy)
-        b, c, h, w = x.shape
-        dx = torch.empty_like(x)
-        want = ctx.want and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        into = want and ctx.gbuf is not None and ctx.bbuf is not None
-        dgamma = dbeta = None
-        if want:
-            dgamma = ctx.gbuf if into else torch.empty_like(gamma)
-            dbeta = ctx.bbuf if into else torch.empty_like(gamma)
-        ws = workspace(lib.munit_batchnorm_workspace_bytes(c), x.device)
-        _lib.check(lib.munit_batchnorm_bwd(_p(x), _p(dy), _p(y), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta),
-                                           c_float(1.0 if into else 0.0), b * h * w, c, ctx.relu, _p(ws), ws.numel(),
-                                           _stream()), "batchnorm_bwd")
-        if into or not want:
-            return dx, None, None, None, None, None, None, None, None
-        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None, None, None, None,
-                None, None, None)
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, relu=False, eps=1e-5, momentum=0.1, training=True,
@@ -1623,19 +1554,12 @@ def batch_norm(x, gamma, beta, running_mean, running_var, relu=False, eps=1e-5, 
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() != world:
             raise RuntimeError("munit_amd.batch_norm: world %d needs a process group of that size" % world)
-        return _BatchNormDP.apply(x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads,
-                                  int(world), dist.get_rank())
+        return _BatchNorm.apply(x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads,
+                                int(world), dist.get_rank())
     if training:
-        return _BatchNorm.apply(x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads)
-    _require(x, "batch-norm input")
+        return _BatchNorm.apply(x, gamma, beta, running_mean, running_var, relu, eps, momentum, need_weight_grads, 0, 0)
+    x, b, c, h, w = _bn_operands(x.detach(), gamma, beta, running_mean, running_var)
     lib = _lib.load()
-    x = nhwc(x.detach())
-    b, c, h, w = x.shape
-    for t, nm in ((gamma, "weight"), (beta, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
-        _require(t, "batch-norm " + nm)
-        if tuple(t.shape) != (c,) or not t.is_contiguous():
-            raise RuntimeError("munit_amd.batch_norm: %s must be a contiguous (%d,) tensor" % (nm, c))
-    _same_device(x, gamma, beta, running_mean, running_var)
     y = torch.empty_like(x)
     with _on(x):
         _lib.check(lib.munit_batchnorm_fwd(_p(x), _p(y), None, None, _p(running_mean), _p(running_var), b * h * w, c,

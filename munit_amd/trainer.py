@@ -501,6 +501,12 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.last_exchange = None   # the GradExchange of the last data-parallel gen_update (introspection)
 
         optimizer = FusedExtraAdam if "extra" in hyperparameters["optimizer"] else FusedAdam  # trainer.py:41-45
+
+        def make_opt(*modules):
+            """the optimizer over the trainable parameters of `modules`, in their order"""
+            return optimizer([p for m in modules for p in m.parameters() if p.requires_grad], lr=lr,
+                             betas=(hyperparameters["beta1"], hyperparameters["beta2"]),
+                             weight_decay=hyperparameters["weight_decay"])
         self.domain_classif_ab = hyperparameters.get("domain_adv_w", 0) > 0
         self.use_classifier_sr = hyperparameters["adaptation"]["dfeat_lambda"] > 0
         self.train_seg = hyperparameters["adaptation"]["sem_seg_lambda"] > 0
@@ -534,16 +540,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self.s_a = torch.randn(display_size, self.style_dim, 1, 1)
         self.s_b = torch.randn(display_size, self.style_dim, 1, 1)
 
-        beta1, beta2 = hyperparameters["beta1"], hyperparameters["beta2"]
-        dis_params = list(self.dis_a.parameters()) + list(self.dis_b.parameters())
-        if self.gen_state == 0:
-            gen_params = list(self.gen_a.parameters()) + list(self.gen_b.parameters())
-        else:
-            gen_params = list(self.gen.parameters())
-        self.dis_opt = optimizer([p for p in dis_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
-                                 weight_decay=hyperparameters["weight_decay"])
-        self.gen_opt = optimizer([p for p in gen_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
-                                 weight_decay=hyperparameters["weight_decay"])
+        self.dis_opt = make_opt(self.dis_a, self.dis_b)
+        self.gen_opt = make_opt(self.gen_a, self.gen_b) if self.gen_state == 0 else make_opt(self.gen)
         self.dis_scheduler = get_scheduler(self.dis_opt, hyperparameters)
         self.gen_scheduler = get_scheduler(self.gen_opt, hyperparameters)
 
@@ -563,9 +561,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         if self.use_classifier_sr:
             self.domain_classifier_sr_b = domainClassifier(256)
             self.domain_classifier_sr_a = domainClassifier(256)
-            dann_params = list(self.domain_classifier_sr_a.parameters()) + list(self.domain_classifier_sr_b.parameters())
-            self.classif_opt_sr = optimizer([p for p in dann_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
-                                            weight_decay=hyperparameters["weight_decay"])
+            self.classif_opt_sr = make_opt(self.domain_classifier_sr_a, self.domain_classifier_sr_b)
             self.domain_classifier_sr_a.apply(weights_init("gaussian"))
             self.domain_classifier_sr_b.apply(weights_init("gaussian"))
             self.classif_sr_scheduler = get_scheduler(self.classif_opt_sr, hyperparameters)
@@ -575,9 +571,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         if self.use_output_classifier_sr:
             self.output_classifier_sr_a = MsImageDis(hyperparameters["input_dim_a"], hyperparameters["dis"])
             self.output_classifier_sr_b = MsImageDis(hyperparameters["input_dim_a"], hyperparameters["dis"])
-            dann_params = list(self.output_classifier_sr_a.parameters()) + list(self.output_classifier_sr_b.parameters())
-            self.output_classif_opt_sr = optimizer([p for p in dann_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
-                                                   weight_decay=hyperparameters["weight_decay"])
+            self.output_classif_opt_sr = make_opt(self.output_classifier_sr_a, self.output_classifier_sr_b)
             self.output_classifier_sr_a.apply(weights_init("gaussian"))
             self.output_classifier_sr_b.apply(weights_init("gaussian"))
             self.output_scheduler_sr = get_scheduler(self.output_classif_opt_sr, hyperparameters)
@@ -586,9 +580,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         # checkpoint's weights; its own optimizer, a scheduler that update_learning_rate never steps, nothing in save / resume
         if self.train_seg:
             self.segmentation_head = load_segmentation_head(hyperparameters["semantic_ckpt_path"])
-            dann_params = list(self.segmentation_head.parameters())
-            self.segmentation_opt = optimizer([p for p in dann_params if p.requires_grad], lr=lr, betas=(beta1, beta2),
-                                              weight_decay=hyperparameters["weight_decay"])
+            self.segmentation_opt = make_opt(self.segmentation_head)
             self.scheduler_seg = get_scheduler(self.segmentation_opt, hyperparameters)
 
         self._consts = {}
@@ -816,39 +808,30 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         return t
 
     # ---- optimizer steps (trainer.py:252-268) -----------------------------------------
+    def _opt_step(self, opt):
+        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
+            opt.extrapolation()
+        else:
+            opt.step()
+
     def dis_opt_step(self):
         """ExtraAdam extrapolates on even iterations and steps on odd ones (trainer.py:252-259)."""
-        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
-            self.dis_opt.extrapolation()
-        else:
-            self.dis_opt.step()
+        self._opt_step(self.dis_opt)
 
     def gen_opt_step(self):
-        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
-            self.gen_opt.extrapolation()
-        else:
-            self.gen_opt.step()
+        self._opt_step(self.gen_opt)
 
     def classif_opt_sr_step(self):
         """trainer.py:243-250."""
-        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
-            self.classif_opt_sr.extrapolation()
-        else:
-            self.classif_opt_sr.step()
+        self._opt_step(self.classif_opt_sr)
 
     def output_classif_opt_sr_step(self):
         """trainer.py:234-241.  Exists as in the reference, whose update does not call it either."""
-        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
-            self.output_classif_opt_sr.extrapolation()
-        else:
-            self.output_classif_opt_sr.step()
+        self._opt_step(self.output_classif_opt_sr)
 
     def segmentation_opt_step(self):
         """trainer.py:270-277.  Exists as in the reference, whose update does not call it either."""
-        if "extra" in self.hyperparameters["optimizer"] and (self.iterations % 2 == 0):
-            self.segmentation_opt.extrapolation()
-        else:
-            self.segmentation_opt.step()
+        self._opt_step(self.segmentation_opt)
 
     # ---- criteria (trainer.py:279-305) ------------------------------------------------
     def recon_criterion(self, input, target):

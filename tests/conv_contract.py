@@ -371,3 +371,23 @@ def check_linear(b, k, n, act):
                 L.verify(label + " one byte short (refused)")
                 assert all(bool((t.view(torch.int32) == POISON[4][0]).all()) for t in outs), \
                     what + ": %s wrote before refusing a short workspace" % label
+
+
+class Calls(object):
+    """Record the C entry points (by name prefix) called while active."""
+
+    def __init__(self, prefixes):
+        self.lib = _lib.load()
+        self.names = [n for n in _lib.SIGNATURES if n.startswith(tuple(prefixes))]
+        self.calls = []
+
+    def __enter__(self):
+        self.saved = {n: getattr(self.lib, n) for n in self.names}
+        for n, f in self.saved.items():
+            setattr(self.lib, n, (lambda f, n: lambda *a: self.calls.append(n) or f(*a))(f, n))
+        return self.calls
+
+    def __exit__(self, *exc):
+        for n, f in self.saved.items():
+            setattr(self.lib, n, f)
+        return False

@@ -14,7 +14,8 @@ import torch.nn.functional as F
 from munit_amd import _lib, ops
 from oracle import munit_oracle as O
 from tests import featda_oracle as D
-from tests.conv_contract import ERR_WORKSPACE, GUARD_BYTE, POISON, Arena, Launches, fill_random, no_nan, poison, stream
+from tests.conv_contract import (ERR_WORKSPACE, GUARD_BYTE, POISON, Arena, Calls, Launches, fill_random, no_nan, poison,
+                                 stream)
 from tests.parity import nerr
 
 pytestmark = pytest.mark.gpu
@@ -615,38 +616,18 @@ def test_multi_stream_gen_update_is_bitwise_the_single_stream_one(monkeypatch):
     assert float(res[0][0].abs().max()) > 0
 
 
-class _Calls(object):
-    """Record the C entry points (by name prefix) called while active."""
-
-    def __init__(self, prefixes):
-        self.lib = _lib.load()
-        self.names = [n for n in _lib.SIGNATURES if n.startswith(tuple(prefixes))]
-        self.calls = []
-
-    def __enter__(self):
-        self.saved = {n: getattr(self.lib, n) for n in self.names}
-        for n, f in self.saved.items():
-            setattr(self.lib, n, (lambda f, n: lambda *a: self.calls.append(n) or f(*a))(f, n))
-        return self.calls
-
-    def __exit__(self, *exc):
-        for n, f in self.saved.items():
-            setattr(self.lib, n, f)
-        return False
-
-
 def test_zero_weights_launch_none_of_the_new_kernels():
     hp = _hp()
     tr = _trainer(hp)
     x_a, x_b, m_a, m_b = _batch()
-    with _Calls(NEW) as calls:
+    with Calls(NEW) as calls:
         tr.dis_update(x_a, x_b, hp)
         tr.gen_update(x_a, x_b, hp, m_a, m_b)
         torch.cuda.synchronize()
     assert calls == [] and tr.loss_classifier_sr == 0
     on = _hp(adv_lambda=6, dfeat_lambda=1)
     tr = _trainer(on)
-    with _Calls(NEW) as calls:
+    with Calls(NEW) as calls:
         tr.gen_update(x_a, x_b, on, m_a, m_b)
         torch.cuda.synchronize()
     # two classifiers: 2 max-pools, 6 batch norms and 1 average each, forward and backward

@@ -5,16 +5,17 @@ tests/nsgan_oracle.py, whole steps through tests/parity.py, and that neither gan
 Bounds (those of tests/test_gpu_outda.py): a loss within 1e-5 relative of the fp64 yardstick, forward tensors within 1e-5
 normalised maximum error, gradients within 5e-5, repeated runs bitwise equal.  They are relative, so the kernel cases keep
 every reference value in fp32's normal range (asserted on the reference): a mean below 1.2e-38 cannot be held to 1e-5."""
-from ctypes import c_float, c_size_t, c_void_p
+import functools
 
 import pytest
 import torch
 
-from munit_amd import _lib, ops
+from munit_amd import ops
 from oracle import munit_oracle as O
+from tests import gan_loss_contract as G
 from tests import nsgan_oracle as N
 from tests import outda_oracle as D
-from tests.conv_contract import GUARD_BYTE, Arena, Launches, fill_random, no_nan, poison, stream
+from tests.conv_contract import Calls, no_nan
 from tests.parity import KINK_NOISE, nerr, run_step_parity
 
 pytestmark = pytest.mark.gpu
@@ -27,62 +28,15 @@ BIG = 1024 * 256 * 2 + 5
 INF, NAN = float("inf"), float("nan")
 
 
-class _Calls(object):
-    """Record the C entry points (by name prefix) called while active."""
-
-    def __init__(self, prefixes):
-        self.lib = _lib.load()
-        self.names = [n for n in _lib.SIGNATURES if n.startswith(tuple(prefixes))]
-        self.calls = []
-
-    def __enter__(self):
-        self.saved = {n: getattr(self.lib, n) for n in self.names}
-        for n, f in self.saved.items():
-            setattr(self.lib, n, (lambda f, n: lambda *a: self.calls.append(n) or f(*a))(f, n))
-        return self.calls
-
-    def __exit__(self, *exc):
-        for n, f in self.saved.items():
-            setattr(self.lib, n, f)
-        return False
-
-
 # ---- the kernels --------------------------------------------------------------------------------------------------------
-def _arrays(xs, targets):
-    n = len(xs)
-    return ((c_void_p * n)(*[x.data_ptr() for x in xs]), (c_size_t * n)(*[x.numel() for x in xs]),
-            (c_float * n)(*[float(t) for t in targets]))
-
-
-def _raw(xs, targets, dxs=None, gout=1.0, with_seg=True):
-    """munit_nsgan_fwd + _bwd through ctypes on 1-D device segments: out, seg_out, [dx_s]"""
-    lib = _lib.load()
-    n = len(xs)
-    px, pn, pt = _arrays(xs, targets)
-    out = torch.full((1,), 12345.0, device=DEV)
-    seg = torch.full((n,), 12345.0, device=DEV)
-    nws = lib.munit_nsgan_workspace_bytes(n)
-    ws = torch.empty(nws, dtype=torch.uint8, device=DEV)
-    p = lambda t: c_void_p(t.data_ptr())
-    _lib.check(lib.munit_nsgan_fwd(px, pn, pt, n, p(out), p(seg) if with_seg else None, p(ws), nws, stream()), "nsgan_fwd")
-    if dxs is None:
-        dxs = [torch.full_like(x, 12345.0) for x in xs]
-    g = torch.full((1,), gout, device=DEV)
-    pd = (c_void_p * n)(*[d.data_ptr() for d in dxs])
-    _lib.check(lib.munit_nsgan_bwd(px, pn, pt, n, p(g), pd, stream()), "nsgan_bwd")
-    torch.cuda.synchronize()
-    return out, seg, dxs
+_raw = functools.partial(G.raw, G.NSGAN)
+_segments = G.segments
 
 
 def _softplus64(x, t):
     """per-element fp64 softplus(z) and d/dx = (1 - 2 t) sigmoid(z) of fp32 data"""
     z = x.double() * (1 - 2 * t)
     return torch.clamp_min(z, 0) + torch.log1p(torch.exp(-z.abs())), (1 - 2 * t) * torch.sigmoid(z)
-
-
-def _segments(sizes, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return [(scale * torch.randn(n, generator=g)).float() for n in sizes]
 
 
 def _confident(sizes, seed, targets):
@@ -168,60 +122,12 @@ def test_a_nan_logit_stays_in_its_own_segment_and_its_own_element():
 
 def test_unaligned_segment_starts_are_bitwise_the_aligned_run():
     """Segments at float offsets 1, 2 and 3 (mod 4) of one allocation, sizes 1, 5 and 257; dx likewise."""
-    sizes, offs, targets = [1, 5, 257], [1, 6, 15], [0.0, 1.0, 0.0]
-    host = _segments(sizes, 5, 4.0)
-    aligned = [x.to(DEV) for x in host]
-    buf = torch.zeros(offs[-1] + sizes[-1] + 3, device=DEV)
-    dbuf = torch.full_like(buf, 7.0)
-    assert buf.data_ptr() % 16 == 0 and [o % 4 for o in offs] == [1, 2, 3]
-    xs, dxs = [], []
-    for x, o in zip(aligned, offs):
-        buf[o:o + x.numel()].copy_(x)
-        xs.append(buf[o:o + x.numel()])
-        dxs.append(dbuf[o:o + x.numel()])
-    out, seg, dx = _raw(aligned, targets, gout=0.75)
-    out_u, seg_u, dx_u = _raw(xs, targets, dxs=dxs, gout=0.75)
-    assert torch.equal(out, out_u) and torch.equal(seg, seg_u)
-    for a, b in zip(dx, dx_u):
-        assert torch.equal(a, b)
-    covered = torch.zeros(buf.numel(), dtype=torch.bool, device=DEV)
-    for o, n in zip(offs, sizes):
-        covered[o:o + n] = True
-    assert bool((dbuf[~covered] == 7.0).all())           # nothing written between the segments
+    G.check_unaligned_segment_starts(G.NSGAN, scale=4.0)
 
 
 @pytest.mark.parametrize("sizes", [(255, 256, 257), (1, 1026)])
 def test_guard_bands(sizes):
-    lib = _lib.load()
-    n = len(sizes)
-    nws = lib.munit_nsgan_workspace_bytes(n)
-    spans = {"gout": 4, "out": 4, "seg": 4 * n, "ws": nws}
-    for i, m in enumerate(sizes):
-        spans["x%d" % i], spans["dx%d" % i] = 4 * m, 4 * m
-    a = Arena(spans, torch.device(DEV))
-    for i in range(n):
-        fill_random(a.view("x%d" % i, torch.float32), 80 + i)
-    a.view("gout", torch.float32).fill_(1.5)
-    px = (c_void_p * n)(*[a.ptr("x%d" % i).value for i in range(n)])
-    pd = (c_void_p * n)(*[a.ptr("dx%d" % i).value for i in range(n)])
-    pn, pt = (c_size_t * n)(*sizes), (c_float * n)(*[float(i % 2) for i in range(n)])
-    inputs = ["x%d" % i for i in range(n)] + ["gout"]
-    for what, outs, launch in (
-            ("nsgan_fwd", ["out", "seg"], lambda: lib.munit_nsgan_fwd(px, pn, pt, n, a.ptr("out"), a.ptr("seg"), a.ptr("ws"), nws,
-                                                                      stream())),
-            ("nsgan_bwd", ["dx%d" % i for i in range(n)], lambda: lib.munit_nsgan_bwd(px, pn, pt, n, a.ptr("gout"), pd, stream()))):
-        L = Launches(a, inputs, "%s %s" % (what, sizes))
-        res = []
-        for k in (0, 1):
-            for o in outs:
-                poison(a.view(o, torch.float32), k)
-            a.bytes("ws").fill_(GUARD_BYTE)
-            L.after(launch(), "payload %d" % k)
-            for o in outs:
-                assert no_nan(a.view(o, torch.float32)), "%s: NaN in %s" % (what, o)
-            res.append({o: a.bytes(o).clone() for o in outs})
-        for o in outs:
-            assert torch.equal(res[0][o], res[1][o]), "%s: %s differs between two runs" % (what, o)
+    G.check_guard_bands(G.NSGAN, sizes)
 
 
 # ---- ops.nsgan_loss -------------------------------------------------------------------------------------------------------
@@ -243,7 +149,7 @@ def test_nsgan_loss_function(half):
     ref = [t.double().requires_grad_(True) for t in host]
     l_ref = sum(_sp(r[:half], 0) + _sp(r[half:], 1) for r in ref)
     g_ref = torch.autograd.grad(3.0 * l_ref, ref)
-    with _Calls(NSGAN + OTHERS) as calls:
+    with Calls(NSGAN + OTHERS) as calls:
         loss = ops.nsgan_loss(xs, [(0.0, 1.0)] * 3)
         grads = torch.autograd.grad(loss, xs, torch.tensor(3.0, device=DEV))
         torch.cuda.synchronize()
@@ -273,7 +179,7 @@ def test_more_scales_than_one_call_holds_go_in_groups(pair):
     xs = [t.to(DEV).contiguous(memory_format=torch.channels_last).requires_grad_(True) for t in host]
     ref = [t.double().requires_grad_(True) for t in host]
     l_ref = sum((_sp(r[:1], 0) + _sp(r[1:], 1)) if pair else _sp(r, 1) for r in ref)
-    with _Calls(NSGAN + OTHERS) as calls:
+    with Calls(NSGAN + OTHERS) as calls:
         loss = MsImageDis._multi_scale(ops.nsgan_loss, xs, targets)
         grads = torch.autograd.grad(loss, xs)
         torch.cuda.synchronize()
@@ -295,7 +201,7 @@ def test_nsgan_loss_refusals():
         ops.nsgan_loss([y] * 9, [0.0] * 9)
     with pytest.raises(RuntimeError, match="HIP device"):
         ops.nsgan_loss([y.cpu()], [0.0])
-    with _Calls(NSGAN) as calls:
+    with Calls(NSGAN) as calls:
         for bad in ([0.5], [(0.0, 0.5)], [2.0], [-1.0], [float("nan")]):
             with pytest.raises(RuntimeError, match="0 or 1"):
                 ops.nsgan_loss([y], bad)
@@ -372,7 +278,7 @@ def _hip_loss(net, which, fake, real):
 def test_losses_against_the_oracle(dis, which):
     hp, net, sd, fake, real = dis
     nin = LOSSES[which][2]
-    with _Calls(NSGAN + OTHERS) as calls:
+    with Calls(NSGAN + OTHERS) as calls:
         (loss, grads), km = _record(lambda: _hip_loss(net, which, fake, real))
     assert calls == ["munit_nsgan_fwd", "munit_nsgan_bwd"]
     rs = [fake.clone().requires_grad_(True), real.clone().requires_grad_(True)]
@@ -387,7 +293,7 @@ def test_losses_against_the_oracle(dis, which):
 
 def test_gen_loss_sr_is_refused_before_the_forward(dis):
     _, net, _, fake, _ = dis
-    with _Calls(("munit_",)) as calls:
+    with Calls(("munit_",)) as calls:
         with pytest.raises(NotImplementedError, match="undefined variable"):
             net.calc_gen_loss_sr(fake.float().to(DEV))
     assert calls == []
@@ -400,7 +306,7 @@ def test_the_batched_pair_path_matches_the_two_pass_path(dis, which, monkeypatch
     res = []
     for batched in (True, False):
         monkeypatch.setattr(networks, "BATCH_DIS_PAIR", batched)
-        with _Calls(("munit_avgpool3s2_fwd",)) as pools:
+        with Calls(("munit_avgpool3s2_fwd",)) as pools:
             res.append(_hip_loss(net, which, fake, real))
             torch.cuda.synchronize()
         res[-1] += (len(pools),)
@@ -432,7 +338,7 @@ def _step(hp):
     torch.manual_seed(0)
     tr = MUNIT_Trainer(dict(hp)).to(DEV)
     x_a, x_b, m_a, m_b = [t.to(DEV) for t in O.synthetic_batch(2, 64, seed=7)]
-    with _Calls(NSGAN + OTHERS) as calls:
+    with Calls(NSGAN + OTHERS) as calls:
         tr.dis_update(x_a, x_b, hp)
         tr.gen_update(x_a, x_b, hp, m_a, m_b)
         torch.cuda.synchronize()

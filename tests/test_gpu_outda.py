@@ -5,15 +5,17 @@ MsImageDis and the trainer's updates against tests/outda_oracle.py.
 Bounds (the project's own, tests/test_gpu_featda.py and tests/parity.py): a loss within 1e-5 relative of the fp64 oracle,
 forward tensors within 1e-5 normalised maximum error, gradients within 5e-5, repeated runs bitwise equal; weights after an
 Adam step within 4 lr and 2e-4 relative L2 per tensor, the Adam moments within 2 x 5e-5 relative L2."""
-from ctypes import c_float, c_size_t, c_void_p
+import functools
 
+import numpy as np
 import pytest
 import torch
 
-from munit_amd import _lib, ops
+from munit_amd import ops
 from oracle import munit_oracle as O
+from tests import gan_loss_contract as G
 from tests import outda_oracle as D
-from tests.conv_contract import GUARD_BYTE, Arena, Launches, fill_random, no_nan, poison, stream
+from tests.conv_contract import Calls, no_nan
 from tests.parity import KINK_NOISE, l2err, load_into_trainer, nerr, oracle_states, trainer_named_params
 
 pytestmark = pytest.mark.gpu
@@ -24,56 +26,9 @@ ON = dict(output_classifier_lambda=1, output_adv_lambda=1)
 BIG = 1024 * 256 * 2 + 5
 
 
-class _Calls(object):
-    """Record the C entry points (by name prefix) called while active."""
-
-    def __init__(self, prefixes):
-        self.lib = _lib.load()
-        self.names = [n for n in _lib.SIGNATURES if n.startswith(tuple(prefixes))]
-        self.calls = []
-
-    def __enter__(self):
-        self.saved = {n: getattr(self.lib, n) for n in self.names}
-        for n, f in self.saved.items():
-            setattr(self.lib, n, (lambda f, n: lambda *a: self.calls.append(n) or f(*a))(f, n))
-        return self.calls
-
-    def __exit__(self, *exc):
-        for n, f in self.saved.items():
-            setattr(self.lib, n, f)
-        return False
-
-
 # ---- the kernels --------------------------------------------------------------------------------------------------------
-def _arrays(xs, targets):
-    n = len(xs)
-    return ((c_void_p * n)(*[x.data_ptr() for x in xs]), (c_size_t * n)(*[x.numel() for x in xs]),
-            (c_float * n)(*[float(t) for t in targets]))
-
-
-def _raw(xs, targets, dxs=None, gout=1.0, with_seg=True):
-    """munit_lsgan_fwd + _bwd through ctypes on 1-D device segments: out, seg_out, [dx_s]"""
-    lib = _lib.load()
-    n = len(xs)
-    px, pn, pt = _arrays(xs, targets)
-    out = torch.full((1,), float("nan"), device=DEV)
-    seg = torch.full((n,), float("nan"), device=DEV)
-    nws = lib.munit_lsgan_workspace_bytes(n)
-    ws = torch.empty(nws, dtype=torch.uint8, device=DEV)
-    p = lambda t: c_void_p(t.data_ptr())
-    _lib.check(lib.munit_lsgan_fwd(px, pn, pt, n, p(out), p(seg) if with_seg else None, p(ws), nws, stream()), "lsgan_fwd")
-    if dxs is None:
-        dxs = [torch.full_like(x, float("nan")) for x in xs]
-    g = torch.full((1,), gout, device=DEV)
-    pd = (c_void_p * n)(*[d.data_ptr() for d in dxs])
-    _lib.check(lib.munit_lsgan_bwd(px, pn, pt, n, p(g), pd, stream()), "lsgan_bwd")
-    torch.cuda.synchronize()
-    return out, seg, dxs
-
-
-def _segments(sizes, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return [(scale * torch.randn(n, generator=g)).float() for n in sizes]
+_raw = functools.partial(G.raw, G.LSGAN)
+_segments = G.segments
 
 
 CASES = {
@@ -109,62 +64,38 @@ def test_kernels_against_fp64(case):
     assert torch.equal(out, out3) and bool(torch.isnan(seg3).all())     # seg_out == NULL: the same out, nothing written
 
 
+def test_lsgan_arithmetic_on_the_integer_lattice():
+    """Integer logits in [-8, 8], targets 0 / 1 / 0.5: every (x - t)^2 is a multiple of 0.25 and a
+    segment's sum stays below 2^24 quarter-units (4097 * 81 * 4 < 2^21), so the fp32 sum is exact in any order and the
+    expected bits come from numpy alone: the mean as float64(sum) * (1 / float64(n)), out as the float64 sum of the means in
+    index order, dx as g = 2 * gout / n, dx = g * (x - t) with one fp32 rounding per operation."""
+    sizes, gout = [1, 3, 255, 256, 257, 4097], np.float32(3.0)
+    targets = G.cycle(G.LSGAN, len(sizes))
+    rng = np.random.RandomState(17)
+    host = [rng.randint(-8, 9, size=n).astype(np.float32) for n in sizes]
+    out, seg, dxs = _raw([torch.from_numpy(x).to(DEV) for x in host], targets, gout=float(gout))
+    sums = [np.sum((x.astype(np.float64) - t) ** 2) for x, t in zip(host, targets)]
+    assert all(s * 4 == int(s * 4) and s * 4 < 2 ** 24 for s in sums)
+    means = [s * (1.0 / np.float64(n)) for s, n in zip(sums, sizes)]
+    total = np.float64(0.0)
+    for m in means:
+        total += m
+    assert seg.cpu().numpy().tobytes() == np.asarray(means, np.float64).astype(np.float32).tobytes()
+    assert out.cpu().numpy().tobytes() == np.float32(total).tobytes()
+    for x, t, n, dx in zip(host, targets, sizes, dxs):
+        g = np.float32(2.0) * gout / np.float32(n)
+        want = g * (x - np.float32(t))
+        assert want.dtype == np.float32 and dx.cpu().numpy().tobytes() == want.tobytes(), "dx of the segment of %d" % n
+
+
 def test_unaligned_segment_starts_are_bitwise_the_aligned_run():
     """Segments at float offsets 1, 2 and 3 (mod 4) of one allocation, sizes 1, 5 and 257; dx likewise."""
-    sizes, offs, targets = [1, 5, 257], [1, 6, 15], [0.0, 1.0, 0.5]
-    host = _segments(sizes, 5)
-    aligned = [x.to(DEV) for x in host]
-    buf = torch.zeros(offs[-1] + sizes[-1] + 3, device=DEV)
-    dbuf = torch.full_like(buf, 7.0)
-    assert buf.data_ptr() % 16 == 0 and [o % 4 for o in offs] == [1, 2, 3]
-    xs, dxs = [], []
-    for x, o in zip(aligned, offs):
-        buf[o:o + x.numel()].copy_(x)
-        xs.append(buf[o:o + x.numel()])
-        dxs.append(dbuf[o:o + x.numel()])
-    out, seg, dx = _raw(aligned, targets, gout=0.75)
-    out_u, seg_u, dx_u = _raw(xs, targets, dxs=dxs, gout=0.75)
-    assert torch.equal(out, out_u) and torch.equal(seg, seg_u)
-    for a, b in zip(dx, dx_u):
-        assert torch.equal(a, b)
-    covered = torch.zeros(buf.numel(), dtype=torch.bool, device=DEV)
-    for o, n in zip(offs, sizes):
-        covered[o:o + n] = True
-    assert bool((dbuf[~covered] == 7.0).all())           # nothing written between the segments
+    G.check_unaligned_segment_starts(G.LSGAN)
 
 
 @pytest.mark.parametrize("sizes", [(255, 256, 257), (1, 1026)])
 def test_guard_bands(sizes):
-    lib = _lib.load()
-    n = len(sizes)
-    nws = lib.munit_lsgan_workspace_bytes(n)
-    spans = {"gout": 4, "out": 4, "seg": 4 * n, "ws": nws}
-    for i, m in enumerate(sizes):
-        spans["x%d" % i], spans["dx%d" % i] = 4 * m, 4 * m
-    a = Arena(spans, torch.device(DEV))
-    for i in range(n):
-        fill_random(a.view("x%d" % i, torch.float32), 80 + i)
-    a.view("gout", torch.float32).fill_(1.5)
-    px = (c_void_p * n)(*[a.ptr("x%d" % i).value for i in range(n)])
-    pd = (c_void_p * n)(*[a.ptr("dx%d" % i).value for i in range(n)])
-    pn, pt = (c_size_t * n)(*sizes), (c_float * n)(*[(0.0, 1.0, 0.5)[i % 3] for i in range(n)])
-    inputs = ["x%d" % i for i in range(n)] + ["gout"]
-    for what, outs, launch in (
-            ("lsgan_fwd", ["out", "seg"], lambda: lib.munit_lsgan_fwd(px, pn, pt, n, a.ptr("out"), a.ptr("seg"), a.ptr("ws"), nws,
-                                                                      stream())),
-            ("lsgan_bwd", ["dx%d" % i for i in range(n)], lambda: lib.munit_lsgan_bwd(px, pn, pt, n, a.ptr("gout"), pd, stream()))):
-        L = Launches(a, inputs, "%s %s" % (what, sizes))
-        res = []
-        for k in (0, 1):
-            for o in outs:
-                poison(a.view(o, torch.float32), k)
-            a.bytes("ws").fill_(GUARD_BYTE)
-            L.after(launch(), "payload %d" % k)
-            for o in outs:
-                assert no_nan(a.view(o, torch.float32)), "%s: NaN in %s" % (what, o)
-            res.append({o: a.bytes(o).clone() for o in outs})
-        for o in outs:
-            assert torch.equal(res[0][o], res[1][o]), "%s: %s differs between two runs" % (what, o)
+    G.check_guard_bands(G.LSGAN, sizes)
 
 
 # ---- ops.lsgan_loss -------------------------------------------------------------------------------------------------------
@@ -180,7 +111,7 @@ def test_lsgan_loss_function(b):
     ref = [t.double().requires_grad_(True) for t in host]
     l_ref = sum(torch.mean(r[:b // 2] ** 2) + torch.mean((r[b // 2:] - 1) ** 2) for r in ref)
     g_ref = torch.autograd.grad(3.0 * l_ref, ref)
-    with _Calls(("munit_lsgan_fwd", "munit_lsgan_bwd", "munit_mse_const")) as calls:
+    with Calls(("munit_lsgan_fwd", "munit_lsgan_bwd", "munit_mse_const")) as calls:
         loss = ops.lsgan_loss(xs, [(0.0, 1.0)] * 3)
         grads = torch.autograd.grad(loss, xs, torch.tensor(3.0, device=DEV))
         torch.cuda.synchronize()
@@ -265,7 +196,7 @@ def test_losses_against_the_oracle(batches):
         loss = net.calc_dis_loss_sr(xs[0], xs[1])
         return loss, torch.autograd.grad(loss, xs + ps)
 
-    with _Calls(("munit_lsgan_fwd", "munit_lsgan_bwd", "munit_mse_const")) as calls:
+    with Calls(("munit_lsgan_fwd", "munit_lsgan_bwd", "munit_mse_const")) as calls:
         (loss, grads), km = _record(hip_dis)
     assert calls == ["munit_lsgan_fwd", "munit_lsgan_bwd"]
     rs = [sim.clone().requires_grad_(True), real.clone().requires_grad_(True)]
@@ -479,7 +410,7 @@ def test_feature_off_launches_nothing_new_and_changes_nothing():
     x_a, x_b, m_a, m_b = _batch()
     off = _hp(adaptation=dict(output_classifier_lambda=0, output_adv_lambda=0))
     tr_off = _trainer(off)
-    with _Calls(NEW) as calls:
+    with Calls(NEW) as calls:
         tr_off.dis_update(x_a, x_b, off)
         torch.manual_seed(1)
         tr_off.gen_update(x_a, x_b, off, m_a, m_b)
@@ -490,7 +421,7 @@ def test_feature_off_launches_nothing_new_and_changes_nothing():
     tr_on = _trainer(on)
     step = _hp(adaptation=dict(output_adv_lambda=0))
     tr_on.output_classif_opt_sr.flat_g.fill_(3.0)
-    with _Calls(NEW) as calls:
+    with Calls(NEW) as calls:
         tr_on.dis_update(x_a, x_b, step)
         torch.manual_seed(1)
         tr_on.gen_update(x_a, x_b, step, m_a, m_b)
@@ -499,7 +430,7 @@ def test_feature_off_launches_nothing_new_and_changes_nothing():
     assert torch.equal(tr_on.gen_opt.flat_g, tr_off.gen_opt.flat_g) and torch.equal(tr_on.gen_opt.flat_p, tr_off.gen_opt.flat_p)
     assert torch.equal(tr_on.loss_gen_total, tr_off.loss_gen_total) and torch.equal(tr_on.dis_opt.flat_p, tr_off.dis_opt.flat_p)
     assert bool((tr_on.output_classif_opt_sr.flat_g == 3.0).all())
-    with _Calls(NEW) as calls:
+    with Calls(NEW) as calls:
         tr_on.gen_update(x_a, x_b, on, m_a, m_b)
         torch.cuda.synchronize()
     assert calls.count("munit_lsgan_fwd") == calls.count("munit_lsgan_bwd") == 2      # one pair per classifier pass

@@ -19,8 +19,9 @@ from munit_amd import _lib, ops
 from oracle import munit_oracle as O
 from tests import seghead_oracle as H
 from tests import semantic_oracle as S
+from tests.conv_contract import Calls
 from tests.parity import KINK_NOISE, l2err, nerr
-from tests.test_gpu_featda import FWD_TOL, GRAD_TOL, LOSS_TOL, _Calls
+from tests.test_gpu_featda import FWD_TOL, GRAD_TOL, LOSS_TOL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
@@ -457,7 +458,7 @@ def test_zero_weight_launches_none_of_the_new_kernels(ckpt):
     tr = _trainer(hp)
     assert not tr.train_seg and not hasattr(tr, "segmentation_head")
     x_a, x_b, m_a, m_b = [t.to(DEV) for t in O.synthetic_batch(2, 64)]
-    with _Calls(NEW) as calls:
+    with Calls(NEW) as calls:
         tr.dis_update(x_a, x_b, hp)
         tr.gen_update(x_a, x_b, hp, m_a, m_b)
         torch.cuda.synchronize()
@@ -465,7 +466,7 @@ def test_zero_weight_launches_none_of_the_new_kernels(ckpt):
     on = _hp(ckpt, sem_seg_lambda=1)
     tr = _trainer(on)
     t = H.labels(2, 64, 71).to(DEV)
-    with _Calls(NEW + ("munit_batchnorm", "munit_space_to_batch")) as calls:
+    with Calls(NEW + ("munit_batchnorm", "munit_space_to_batch")) as calls:
         tr.dis_update(x_a, x_b, on)
         tr.gen_update(x_a, x_b, on, m_a, m_b)
         assert calls == []

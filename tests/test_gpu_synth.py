@@ -11,6 +11,7 @@ from munit_amd import ops
 from oracle import munit_oracle as O
 from tests import semantic_oracle as S
 from tests import synth_oracle as Y
+from tests.conv_contract import Calls
 from tests.parity import nerr
 
 pytestmark = pytest.mark.gpu
@@ -235,27 +236,6 @@ def _synth_batch():
     return x_a, x_b, m, gt_a, gt_b
 
 
-class _Calls(object):
-    """Record the C entry points (by name prefix) called while active."""
-
-    def __init__(self, prefixes):
-        from munit_amd import _lib
-        self.lib = _lib.load()
-        self.names = [n for n in _lib.SIGNATURES if n.startswith(tuple(prefixes))]
-        self.calls = []
-
-    def __enter__(self):
-        self.saved = {n: getattr(self.lib, n) for n in self.names}
-        for n, f in self.saved.items():
-            setattr(self.lib, n, (lambda f, n: lambda *a: self.calls.append(n) or f(*a))(f, n))
-        return self.calls
-
-    def __exit__(self, *exc):
-        for n, f in self.saved.items():
-            setattr(self.lib, n, f)
-        return False
-
-
 def _synth_parity(tmp_path, monkeypatch, full=0, gen_state=1, semantic_w=3):
     from munit_amd.trainer import MUNIT_Trainer
     from tests.parity import run_step_parity
@@ -277,7 +257,7 @@ def _synth_parity(tmp_path, monkeypatch, full=0, gen_state=1, semantic_w=3):
         over.update(semantic_w=semantic_w, semantic_ckpt_path=_ckpt(tmp_path, seg))
     ops.SEG_SINK = sink
     try:
-        with _Calls(SEG_NAMES + NEW_NAMES) as calls:
+        with Calls(SEG_NAMES + NEW_NAMES) as calls:
             rep = run_step_parity(size=SIZE, batch=BATCH, gen_state=gen_state, iters=1, device=DEV, hp_overrides=over)
     finally:
         ops.SEG_SINK = None
@@ -373,7 +353,7 @@ def test_synth_false_launches_neither_new_kernel(tmp_path):
         def log_metric(self, k, v):
             logged[k] = v
 
-    with _Calls(NEW_NAMES + ("munit_seg_labels", "munit_seg_ce_fwd")) as calls:
+    with Calls(NEW_NAMES + ("munit_seg_labels", "munit_seg_ce_fwd")) as calls:
         tr.dis_update(x_a, x_b, hp)
         tr.gen_update(x_a, x_b, hp, m, m, Exp())
         torch.cuda.synchronize()
