@@ -541,6 +541,43 @@ int munit_maxpool2_bwd(const float* dy, const unsigned char* idx, float* dx, int
 int munit_avgpool16_fwd(const float* x, float* y, int B, int H, int W, int C, munit_stream_t stream);
 int munit_avgpool16_bwd(const float* dy, float* dx, int B, int H, int W, int C, munit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * FID evaluation (scripts/inception_utils.py).  Everything is fp32, row-major and asynchronous
+ * on `stream`; every argument check below returns MUNIT_ERR_ARG before any launch.
+ *
+ * Batched dense product on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32):
+ *   C_p = alpha * op(A_p) * B_p + beta_eye * I   for the n <= MUNIT_GEMM_MAX problems of the host table `prob`,
+ * all in ONE launch and of one shape: op(A) is [M][K] (A itself [M][K], or [K][M] with transA != 0), B [K][N], C [M][N],
+ * any M, N, K >= 1, leading dimensions lda / ldb / ldc >= the row length (the padding is neither read nor written).  The
+ * table is read during the call.  No C may overlap any A, B or other C of the launch.  Each output element is one k-ordered
+ * fmaf chain from 0, then alpha * acc + (row == col ? beta_eye : 0): no split-K, no atomics, bitwise repeatable. */
+enum { MUNIT_GEMM_MAX = 8 };
+typedef struct munit_gemm_problem {
+  const float* A;
+  const float* B;
+  float* C;
+} munit_gemm_problem;
+int munit_gemm_f32(const munit_gemm_problem* prob, int n, int M, int N, int K, int lda, int ldb, int ldc, int transA,
+                   float alpha, float beta_eye, munit_stream_t stream);
+/* torch_cov(pool, rowvar=False) with its mean (inception_utils.py:90-120, :285): mu[D] = column mean of pool[N][D], N >= 2,
+ * sigma[D][D] = Xc^T Xc / (N - 1) with Xc = pool - mu held in ws (centred first, as the reference does).  Unlike the
+ * reference, whose `m -= mean` writes through a view, pool is not modified. */
+size_t munit_fid_moments_workspace_bytes(int N, int D);
+int munit_fid_moments(const float* pool, int N, int D, float* mu, float* sigma, void* ws, size_t ws_bytes,
+                      munit_stream_t stream);
+/* sqrt_newton_schulz (inception_utils.py:125-140) on A[b][D][D] -> sA[b][D][D], iters >= 0, the recurrence unchanged:
+ * normA = sqrt(sum(A o A)) per matrix, Y = A / normA, Z = I; iters times T = 1.5 I - 0.5 Z Y, Y <- Y T, Z <- T Z (the two
+ * in one launch); sA = Y sqrt(normA).  No early exit, no clamp, no host synchronisation: the whole loop is enqueued by
+ * this one call. */
+size_t munit_sqrt_newton_schulz_workspace_bytes(int D, int b);
+int munit_sqrt_newton_schulz(const float* A, int D, int iters, int b, float* sA, void* ws, size_t ws_bytes,
+                             munit_stream_t stream);
+/* torch_calculate_frechet_distance (inception_utils.py:205-241) with the iteration count as an argument:
+ * out[0] = |mu1 - mu2|^2 + tr sigma1 + tr sigma2 - 2 tr sqrt_newton_schulz(sigma1 sigma2, iters), a device scalar. */
+size_t munit_frechet_distance_workspace_bytes(int D);
+int munit_frechet_distance(const float* mu1, const float* sigma1, const float* mu2, const float* sigma2, int D, int iters,
+                           float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,11 @@ class ImageDesc(Structure):
                 ("crop_i", c_int), ("crop_j", c_int), ("flip", c_int), ("kind", c_int)]
 
 
+class GemmProblem(Structure):
+    """munit_gemm_problem."""
+    _fields_ = [("A", c_void_p), ("B", c_void_p), ("C", c_void_p)]
+
+
 class GridSrc(Structure):
     """munit_grid_src."""
     _fields_ = [("data", c_void_p), ("n", c_int), ("channels", c_int), ("layout", c_int)]
@@ -160,6 +165,14 @@ SIGNATURES = {
     "munit_maxpool2_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "munit_avgpool16_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "munit_avgpool16_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "munit_gemm_f32": (c_int, [POINTER(GemmProblem), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                               c_float, _P]),
+    "munit_fid_moments_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "munit_fid_moments": (c_int, [_P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "munit_sqrt_newton_schulz_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "munit_sqrt_newton_schulz": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "munit_frechet_distance_workspace_bytes": (c_size_t, [c_int]),
+    "munit_frechet_distance": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
 }
 
 _lib = None

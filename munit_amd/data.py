@@ -7,7 +7,8 @@ Mirrors the loader API of the reference (same function names, argument order and
   get_data_loader_mask_and_im(file_list, mask_list, ...)  scripts/utils.py:638-677 (MyDataset, utils.py:270-363)
   get_synthetic_data_loader(file_list_a, file_list_b, mask_list, sem_list_a, sem_list_b, ...)
                                                    scripts/utils.py:583-635   (MyDatasetSynthetic, utils.py:458-580)
-  default_txt_reader / default_flist_reader        scripts/utils.py:253-267 / scripts/data.py:13-23
+  get_fid_data_loader(file_list_a, file_list_b, ...)   scripts/utils.py:427-455 (DatasetInferenceFID, utils.py:366-424)
+  default_txt_reader / default_flist_reader       scripts/utils.py:253-267 / scripts/data.py:13-23
 
 Design (MI355X-first, not the reference's worker-process + CPU-transform pipeline):
   * host threads only DECODE files (PIL releases the GIL while decoding) into one pinned staging buffer
@@ -556,6 +557,54 @@ def get_data_loader_mask_and_im(file_list, mask_list, batch_size, train, new_siz
     if mpaths is None:
         return _WithEmptyMask(loader)
     return loader
+
+
+class FidPairLoader:
+    """Iterable of (x_a, x_b) device batches for FID evaluation: DatasetInferenceFID (scripts/utils.py:366-424) behind
+    DataLoader(shuffle=False, drop_last=True) (utils.py:448-454), on a DeviceBatchLoader without crop, flip or shuffle.
+
+    The reference's `transform` never normalises image_b: it returns `normalizer(image_a)` a second time
+    (utils.py:400-401).  Under a current torchvision, where Normalize is out of place, that yields
+        x_a = 2 v - 1              (v: the resized image of list a in [0, 1])
+        x_b = (x_a - 0.5) / 0.5    (list a's image normalised twice; list b's image is decoded, resized and dropped)
+    and this loader reproduces exactly that, x_b on the device (munit_scale: 2 x_a + (-1), the same fp32 value).  Under
+    the reference's pinned torchvision 0.2.1 Normalize works in place, and both names would hold the one doubly-normalised
+    tensor.  List b is read for its records only -- it must have at least as many as list a, as the reference's
+    __getitem__ indexes it -- and its files are not opened."""
+
+    def __init__(self, paths_a, paths_b, batch_size, new_size, num_workers=4, **kw):
+        if len(paths_b) < len(paths_a):
+            raise ValueError("FID list b has %d records, list a %d: every sample of a needs a partner" %
+                             (len(paths_b), len(paths_a)))
+        # the reference does not shard this loader: every process evaluates the whole list
+        kw.setdefault("rank", 0)
+        kw.setdefault("world_size", 1)
+        self.target_paths = list(paths_b)
+        self._loader = DeviceBatchLoader(paths_a, None, batch_size, False, new_size, new_size, new_size, num_workers,
+                                         crop=False, **kw)
+        self.image_paths = self._loader.image_paths
+        self.batch_size = self._loader.batch_size
+
+    def __len__(self):
+        return len(self._loader)
+
+    def __iter__(self):
+        lib = _lib.load()
+        for x_a in self._loader:
+            x_b = torch.full_like(x_a, -1.0)     # same (channels_last) memory order as x_a
+            with torch.cuda.device(x_a.device):
+                stream = ctypes.c_void_p(torch.cuda.current_stream(x_a.device).cuda_stream)
+                _lib.check(lib.munit_scale(ctypes.c_void_p(x_a.data_ptr()), ctypes.c_void_p(x_b.data_ptr()), x_a.numel(),
+                                           2.0, 1, stream), "scale (FID loader)")
+            yield x_a, x_b
+
+
+def get_fid_data_loader(file_list_a, file_list_b, batch_size, train, new_size=256, num_workers=4, **kw):
+    """FID evaluation loader (scripts/utils.py:427-455): yields (x_a, x_b), see FidPairLoader for what x_b is.  `train` is
+    accepted and ignored, as in the reference (no flip, no crop, no shuffle either way)."""
+    paths_a = [rec[0] for rec in default_txt_reader(file_list_a)]
+    paths_b = [rec[0] for rec in default_txt_reader(file_list_b)]
+    return FidPairLoader(paths_a, paths_b, batch_size, new_size, num_workers, **kw)
 
 
 class _SyntheticDataset:

@@ -1631,3 +1631,110 @@ class _AvgPool16(Function):
 def avgpool16(x):
     """nn.AvgPool2d((16, 16)) + .squeeze() on a map of 16..31 per axis (scripts/utils.py:1378, 1388): (B, C)."""
     return _AvgPool16.apply(x)
+
+
+# ------------------------------------------------------------------------------------------
+# FID evaluation (include/munit_hip.h: munit_gemm_f32 ...; fid.hip; munit_amd/inception_utils.py).  No autograd: the
+# reference runs all of it under no_grad.
+# ------------------------------------------------------------------------------------------
+def _rows(t, name):
+    """(rows, cols, leading dimension) of a 2-D fp32 HIP matrix whose rows are dense (a row stride beyond the row is fine)."""
+    _require(t, name)
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise RuntimeError("munit_amd.gemm: %s must be a non-empty 2-D matrix with dense rows, got shape %s strides %s"
+                           % (name, tuple(t.shape), t.stride()))
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def gemm(a, b, trans_a=False, alpha=1.0, beta_eye=0.0, out=None):
+    """alpha * op(a) @ b + beta_eye * I in exact fp32 (munit_gemm_f32): a, b (and out) are 2-D fp32 HIP matrices, or
+    sequences of up to 8 of them with one shape and one row stride each -- all products of a sequence run in ONE launch.
+    op(a) is a, or a.T with trans_a.  out must not overlap an operand.  Returns out (a list for sequences)."""
+    lib = _lib.load()
+    single = isinstance(a, torch.Tensor)
+    aa, bb = ([a], [b]) if single else (list(a), list(b))
+    n = len(aa)
+    if len(bb) != n or not 1 <= n <= 8:
+        raise RuntimeError("munit_amd.gemm: 1..8 problems per launch with as many a as b, got %d and %d" % (n, len(bb)))
+    ar, ac, lda = _rows(aa[0], "a")
+    k, nn, ldb = _rows(bb[0], "b")
+    m, ka = (ac, ar) if trans_a else (ar, ac)
+    if ka != k:
+        raise RuntimeError("munit_amd.gemm: op(a) is %d x %d, b is %d x %d" % (m, ka, k, nn))
+    if out is None:
+        cc = [torch.empty((m, nn), dtype=torch.float32, device=aa[0].device) for _ in range(n)]
+    else:
+        cc = [out] if single else list(out)
+    if len(cc) != n:
+        raise RuntimeError("munit_amd.gemm: %d outputs for %d problems" % (len(cc), n))
+    cr, cn, ldc = _rows(cc[0], "out")
+    if (cr, cn) != (m, nn):
+        raise RuntimeError("munit_amd.gemm: out is %d x %d, the product %d x %d" % (cr, cn, m, nn))
+    for i in range(1, n):
+        if _rows(aa[i], "a") != (ar, ac, lda) or _rows(bb[i], "b") != (k, nn, ldb) or _rows(cc[i], "out") != (m, nn, ldc):
+            raise RuntimeError("munit_amd.gemm: problem %d differs from problem 0 in shape or row stride" % i)
+    _same_device(*(aa + bb + cc))
+    prob = (_lib.GemmProblem * n)(*[_lib.GemmProblem(x.data_ptr(), y.data_ptr(), z.data_ptr())
+                                    for x, y, z in zip(aa, bb, cc)])
+    with _on(cc[0]):
+        _lib.check(lib.munit_gemm_f32(prob, n, m, nn, k, lda, ldb, ldc, int(bool(trans_a)), float(alpha), float(beta_eye),
+                                      _stream()), "gemm_f32")
+    return cc[0] if single else cc
+
+
+def _dense(t, name, dim):
+    _require(t, name)
+    if t.dim() != dim or not t.is_contiguous():
+        raise RuntimeError("munit_amd: %s must be a contiguous %d-D tensor, got shape %s strides %s"
+                           % (name, dim, tuple(t.shape), t.stride()))
+
+
+def fid_moments(pool):
+    """(mu, sigma) of pool (N >= 2, D): the column mean and torch_cov(pool, rowvar=False) (munit_fid_moments).  pool is
+    left unchanged."""
+    lib = _lib.load()
+    _dense(pool, "feature pool", 2)
+    n, d = pool.shape
+    with _on(pool):
+        mu = torch.empty((d,), dtype=torch.float32, device=pool.device)
+        sigma = torch.empty((d, d), dtype=torch.float32, device=pool.device)
+        ws = workspace(lib.munit_fid_moments_workspace_bytes(n, d), pool.device)
+        _lib.check(lib.munit_fid_moments(_p(pool), n, d, _p(mu), _p(sigma), _p(ws), ws.numel(), _stream()), "fid_moments")
+    return mu, sigma
+
+
+def sqrt_newton_schulz(a, iters):
+    """The reference's Newton-Schulz square root of a (b, D, D), `iters` iterations (munit_sqrt_newton_schulz): the whole
+    loop is enqueued by one call, without a host synchronisation."""
+    lib = _lib.load()
+    _dense(a, "matrix batch", 3)
+    b, d, d2 = a.shape
+    if d != d2 or b < 1 or d < 1:
+        raise RuntimeError("munit_amd.sqrt_newton_schulz: (b, D, D) expected, got %s" % (tuple(a.shape),))
+    with _on(a):
+        out = torch.empty_like(a)
+        ws = workspace(lib.munit_sqrt_newton_schulz_workspace_bytes(d, b), a.device)
+        _lib.check(lib.munit_sqrt_newton_schulz(_p(a), d, int(iters), b, _p(out), _p(ws), ws.numel(), _stream()),
+                   "sqrt_newton_schulz")
+    return out
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2, iters=400):
+    """|mu1 - mu2|^2 + tr sigma1 + tr sigma2 - 2 tr sqrt_newton_schulz(sigma1 sigma2, iters) as a 0-d device tensor
+    (munit_frechet_distance)."""
+    lib = _lib.load()
+    _dense(mu1, "mu1", 1)
+    _dense(mu2, "mu2", 1)
+    _dense(sigma1, "sigma1", 2)
+    _dense(sigma2, "sigma2", 2)
+    d = mu1.shape[0]
+    if d < 1 or mu2.shape != mu1.shape or tuple(sigma1.shape) != (d, d) or tuple(sigma2.shape) != (d, d):
+        raise RuntimeError("munit_amd.frechet_distance: shapes %s %s %s %s do not belong together"
+                           % (tuple(mu1.shape), tuple(sigma1.shape), tuple(mu2.shape), tuple(sigma2.shape)))
+    _same_device(mu1, sigma1, mu2, sigma2)
+    with _on(mu1):
+        out = torch.empty((), dtype=torch.float32, device=mu1.device)
+        ws = workspace(lib.munit_frechet_distance_workspace_bytes(d), mu1.device)
+        _lib.check(lib.munit_frechet_distance(_p(mu1), _p(sigma1), _p(mu2), _p(sigma2), d, int(iters), _p(out), _p(ws),
+                                              ws.numel(), _stream()), "frechet_distance")
+    return out
