@@ -401,18 +401,32 @@ class _ApplyRefreshesImages:
     """nn.Module.apply with a tail: the reference's weights_init writes through `m.weight.data` (utils.py:1093-1115), which
     bumps no version counter, so the prepared weight images kept with the parameters (ops._prepared) would go stale unseen.
     After any apply() on a network or on the trainer the optimizers that own its parameters rebuild their images (one launch
-    each; nothing happens before the parameters are bound to a device buffer)."""
+    each; nothing happens before the parameters are bound to a device buffer).  Before it, and before _apply() (.to(),
+    .float(), ...) moves the weights, the same optimizers settle a step that is still in flight on another stream
+    (FusedAdam.step_on)."""
 
-    def apply(self, fn):
-        out = super().apply(fn)
+    def _owners(self):
+        """The optimizers that own this network's parameters."""
         opts = {}
         for p in self.parameters():
             o = getattr(p, "_munit_opt", None)
             if o is not None:
                 opts[id(o)] = o
-        for o in opts.values():
+        return list(opts.values())
+
+    def apply(self, fn):
+        owners = self._owners()
+        for o in owners:
+            o.settle()
+        out = super().apply(fn)
+        for o in owners:
             o.invalidate_prepared()
         return out
+
+    def _apply(self, fn, *args, **kwargs):
+        for o in self._owners():
+            o.settle()
+        return super()._apply(fn, *args, **kwargs)
 
 
 class AdaINGen(_ApplyRefreshesImages, nn.Module):
@@ -545,6 +559,14 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         # (networks.py:84-85, 104), so a module pre-hook would not see them
         self.__dict__["before_forward"] = None
 
+    def follow(self, gate):
+        """The optimizer that owns the parameters hands over its gate (trainer.StepGate): forward() orders its stream behind
+        a step still in flight, state_dict() and load_state_dict() settle it.  Forward and hooks hold the gate alone, so a
+        deepcopy of this module takes a fresh, idle gate with it and nothing of the optimizer or the trainer."""
+        self.__dict__["before_forward"] = gate.wait
+        self.register_state_dict_pre_hook(gate.settle)
+        self.register_load_state_dict_pre_hook(gate.settle)
+
     def _make_net(self):
         dim = self.dim
         cnn_x = [Conv2dBlock(self.input_dim, dim, 4, 2, 1, norm="none", activation=self.activ,
@@ -560,7 +582,7 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         return ops.avgpool3s2(x)
 
     def forward(self, x):
-        if self.before_forward is not None:      # data parallel: order this stream behind a deferred optimizer step (trainer._wait_dis)
+        if self.before_forward is not None:      # data parallel: order this stream behind a deferred optimizer step (follow)
             self.before_forward()
         x = ops.nhwc(x)
         outputs = []

@@ -74,10 +74,54 @@ from .segmentation import SegmentationHead, colorize, load_segmentation_head, se
 from .utils import get_model_list, get_scheduler, load_segmentation_model, normalize_config, weights_init
 
 
+class StepGate:
+    """An optimizer step that is still in flight on another stream (FusedAdam.step_on), and who has waited for it.
+    `pending` is the event recorded behind the step, or None; `waited` the handles of the streams already ordered behind it;
+    `device` the device both belong to.  The gate refers to no trainer, optimizer, module or tensor, so the modules that
+    consult it (MsImageDis) can be copied without dragging any of those along: a copy gets a fresh, idle gate."""
+
+    def __init__(self):
+        self.pending, self.waited, self.device = None, set(), None
+        self.event = None                     # recorded anew by every deferred step; dropped when the optimizer is re-bound
+
+    def arm(self, event, device=None):
+        self.event = self.pending = event
+        self.waited, self.device = set(), device
+
+    def wait(self, *_):
+        """Order the current stream behind the pending step (no-op when none is pending, or when this stream has waited:
+        every stream that reaches the weights waits once)."""
+        ev = self.pending
+        if ev is None:
+            return
+        st = torch.cuda.current_stream(self.device)
+        if st.cuda_stream not in self.waited:
+            st.wait_event(ev)
+            self.waited.add(st.cuda_stream)
+
+    def settle(self, *_):
+        """A host-side reader or writer of the optimizer's buffers is about to start: the current stream waits, nothing pends."""
+        if self.pending is not None:
+            self.wait()
+            self.pending, self.waited = None, set()
+
+    def reset(self):
+        self.settle()
+        self.event = self.device = None
+
+    def __deepcopy__(self, memo):
+        return StepGate()
+
+
 class FusedAdam(Optimizer):
     """torch.optim.Adam semantics (L2-coupled weight decay, amsgrad off; trainer.py:109-120)
     executed as one HIP kernel over a flat parameter buffer.  state_dict()/load_state_dict()
-    speak torch.optim.Adam's format so `optimizer.pt` files interchange with the reference."""
+    speak torch.optim.Adam's format so `optimizer.pt` files interchange with the reference.
+
+    `gate` (StepGate) orders everything behind a step that step_on() left in flight on another stream: every method below that
+    reads or writes the flat buffers settles it first (one attribute test while nothing is pending), and the modules whose
+    parameters live here consult it (MsImageDis.follow, _ApplyRefreshesImages).  Only code that reads flat_p / flat_g /
+    flat_m / flat_v directly calls settle() itself."""
 
     def __init__(self, params, lr, betas, weight_decay, eps=1e-8):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
@@ -85,6 +129,7 @@ class FusedAdam(Optimizer):
         self._step = 0
         self.flat_p = self.flat_g = self.flat_m = self.flat_v = None
         self._views = None
+        self.gate = StepGate()
         # prepared weight images (ops._prepared): items registered on first use, refreshed in one launch per step
         self._prep_items = []
         self._prep_table = None
@@ -101,6 +146,7 @@ class FusedAdam(Optimizer):
 
     def bind(self, device):
         """(Re)build the flat buffers on `device`, re-pointing every parameter at its slice."""
+        self.gate.reset()                     # the old buffers are read below; the event belonged to their device
         offs, total = [], 0
         for p in self._plist:
             offs.append(total)
@@ -149,7 +195,9 @@ class FusedAdam(Optimizer):
     # ---- prepared weight images ----------------------------------------------------------
     def register_prepared(self, item):
         """Called by ops._prepared the first time a layer needs a re-laid-out image of one of this optimizer's
-        weights (backward-data transpose, sub-pixel phase merge)."""
+        weights (backward-data transpose, sub-pixel phase merge).  Host state only: a step in flight keeps the table it was
+        launched with alive (refresh_prepared's record_stream), so nothing waits here -- a settle from inside the first
+        discriminator forward of a gen_update would also release the other branch stream from its wait."""
         self._prep_items.append(item)
         self._prep_table = None
 
@@ -167,20 +215,46 @@ class FusedAdam(Optimizer):
             host = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))),
                                     dtype=torch.uint8)
             self._prep_table = host.to(self.flat_p.device)
+        # read on the current stream, which need not be the one it was allocated on (step_on): dropping it stays safe
+        self._prep_table.record_stream(torch.cuda.current_stream(self.flat_p.device))
         ops.prepare_weights_batch(self._prep_table, n)
 
     def invalidate_prepared(self):
         """Call after ANY write to the weights that is not an optimizer step, a load_state_dict or an in-place op on the
         parameter / the flat buffer itself (those are seen through the tensors' version counters): `p.data.copy_(...)`,
         EMA through `.data`, a raw kernel.  Rebuilds every registered image from the current weights."""
+        self.gate.settle()
         self.refresh_prepared()
 
     # ---- optimizer API ----------------------------------------------------------------
+    def settle(self):
+        """Order the current stream behind a step that step_on() left in flight; call before reading or writing flat_p /
+        flat_g / flat_m / flat_v directly.  Every other way in (the methods here, the owning modules' forward, state_dict,
+        load_state_dict and apply) does it itself."""
+        self.gate.settle()
+
+    def step_on(self, stream, before=None, step=None):
+        """A step that runs on `stream` while the caller's stream goes on: `stream` is ordered behind the caller's, runs
+        `before()` (the gradient exchange) and then `step()` (default self.step; the prepared-image refresh included), and the
+        gate is armed with an event recorded behind them."""
+        gate = self.gate
+        gate.settle()
+        ops.stream_wait(stream, torch.cuda.current_stream(stream.device))
+        with torch.cuda.stream(stream):
+            if before is not None:
+                before()
+            (step or self.step)()
+            ev = torch.cuda.Event() if gate.event is None else gate.event
+            ev.record(stream)
+        gate.arm(ev, stream.device)
+
     def zero_grad(self, set_to_none=False):
+        self.gate.settle()
         self.flat_g.zero_()
 
     @torch.no_grad()
     def step(self, closure=None):
+        self.gate.settle()
         g = self.param_groups[0]
         self._step += 1
         ops.adam_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, g["lr"], g["betas"][0], g["betas"][1],
@@ -188,6 +262,7 @@ class FusedAdam(Optimizer):
         self.refresh_prepared()
 
     def state_dict(self):
+        self.gate.settle()
         state = {}
         for i, (m, v) in enumerate(self._views):
             state[i] = {"step": torch.tensor(float(self._step)),
@@ -201,6 +276,7 @@ class FusedAdam(Optimizer):
         return {"state": state if self._step > 0 else {}, "param_groups": groups}
 
     def load_state_dict(self, sd):
+        self.gate.settle()
         st = sd["state"]
         with torch.no_grad():
             for i, (m, v) in enumerate(self._views):
@@ -232,6 +308,7 @@ class FusedExtraAdam(FusedAdam):
             self.flat_saved.copy_(old)
 
     def _update(self, mode):
+        self.gate.settle()
         g = self.param_groups[0]
         self._step += 1
         ops.extraadam_step(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.flat_saved, g["lr"],
@@ -280,6 +357,23 @@ def comm_stream(dev):
     if key not in GradExchange._comm:
         GradExchange._comm[key] = torch.cuda.Stream(device=dev)
     return GradExchange._comm[key]
+
+
+def all_reduce_mean(flat, world, ranges=None, works=()):
+    """Mean of `flat` over the `world` ranks, in place, on the current stream: all-reduce (of `ranges` only, when stages that
+    went out earlier cover the rest: `works`, waited for here), then one scale by 1 / world."""
+    import torch.distributed as dist
+    if ranges is None:
+        dist.all_reduce(flat)
+    for a, b in ranges or ():
+        dist.all_reduce(flat[a:b])
+    for w in works:
+        w.wait()                              # on a device: the current stream waits for the communication stream
+    if world > 1:
+        if flat.is_cuda:
+            ops.scale_(flat, 1.0 / world)
+        else:
+            flat.mul_(1.0 / world)
 
 
 class GradExchange:
@@ -366,16 +460,8 @@ class GradExchange:
 
     def finish(self):
         """Call on the stream that holds the complete gradient (after backward and the joins of the producing streams)."""
-        import torch.distributed as dist
-        for a, b in self.rest:                # a stage whose hooks never fired (no tensor required grad) goes now
-            dist.all_reduce(self.flat[a:b])
-        for w in self.works:
-            w.wait()                          # on a device: the caller's stream waits for the communication stream
-        if self.world > 1:
-            if self.flat.is_cuda:
-                ops.scale_(self.flat, 1.0 / self.world)
-            else:
-                self.flat.mul_(1.0 / self.world)
+        # a stage whose hooks never fired (no tensor required grad) goes now, with what no stage covers
+        all_reduce_mean(self.flat, self.world, self.rest, self.works)
 
 BRANCH_STREAMS = not os.environ.get("MUNIT_NO_BRANCH_STREAMS")   # bench.py clears it while it times single kernels
 
@@ -504,9 +590,13 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
 
         def make_opt(*modules):
             """the optimizer over the trainable parameters of `modules`, in their order"""
-            return optimizer([p for m in modules for p in m.parameters() if p.requires_grad], lr=lr,
-                             betas=(hyperparameters["beta1"], hyperparameters["beta2"]),
-                             weight_decay=hyperparameters["weight_decay"])
+            opt = optimizer([p for m in modules for p in m.parameters() if p.requires_grad], lr=lr,
+                            betas=(hyperparameters["beta1"], hyperparameters["beta2"]),
+                            weight_decay=hyperparameters["weight_decay"])
+            for m in modules:
+                if isinstance(m, MsImageDis):   # their forward and (load_)state_dict wait for a step of opt still in flight
+                    m.follow(opt.gate)
+            return opt
         self.domain_classif_ab = hyperparameters.get("domain_adv_w", 0) > 0
         self.use_classifier_sr = hyperparameters["adaptation"]["dfeat_lambda"] > 0
         self.train_seg = hyperparameters["adaptation"]["sem_seg_lambda"] > 0
@@ -584,11 +674,6 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self.scheduler_seg = get_scheduler(self.segmentation_opt, hyperparameters)
 
         self._consts = {}
-        # deferred discriminator exchange + step (data parallel, _defer_dis_step)
-        self._dis_pending, self._dis_event, self._dis_waited = None, None, set()
-        for d in (self.dis_a, self.dis_b):
-            d.__dict__["before_forward"] = self._wait_dis     # every path into MsImageDis.forward, direct calls included
-            d.register_state_dict_pre_hook(self._wait_dis)
         self._bind(torch.device("cpu"))
 
     # ------------------------------------------------------------------------------------
@@ -791,7 +876,6 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self._trunk_ranges = self.gen_opt.ranges_of(lambda p: id(p) in trunk)
 
     def _apply(self, fn, *args, **kwargs):
-        self._settle_dis()
         out = super()._apply(fn, *args, **kwargs)
         p = next(self.dis_a.parameters())
         self._bind(p.device)
@@ -1003,15 +1087,9 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
     def _all_reduce_mean(flat):
         """Data-parallel exchange: one all-reduce (RCCL over xGMI) of the flat gradient.  MUNIT_FORCE_ALLREDUCE=1
         issues it at world size 1 too (a 1-GPU box then exercises the RCCL path; the result is unchanged)."""
-        import torch.distributed as dist
         world = dp_world()
         if world:
-            dist.all_reduce(flat)
-            if world > 1:
-                if flat.is_cuda:
-                    ops.scale_(flat, 1.0 / world)
-                else:
-                    flat.mul_(1.0 / world)
+            all_reduce_mean(flat, world)
 
     # ---- gen_update (trainer.py:336-561) -----------------------------------------------
     def gen_update(self, x_a, x_b, hyperparameters, mask_a=None, mask_b=None, comet_exp=None, synth=False,
@@ -1200,8 +1278,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
     def dis_update(self, x_a, x_b, hyperparameters, comet_exp=None):
         ops.set_compute(self.precision)
         hp = hyperparameters
-        self._settle_dis()
-        self.dis_opt.zero_grad()
+        self.dis_opt.zero_grad()               # waits for the last update's step, should it still be in flight (_defer_dis_step)
         s_a = torch.randn(x_a.size(0), self.style_dim, 1, 1)
         s_b = torch.randn(x_b.size(0), self.style_dim, 1, 1)
         dev = x_a.device
@@ -1247,42 +1324,10 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         (Adam + the refresh of the prepared weight images) are enqueued on the communication stream, behind the backward pass
         that just ended on the caller's stream.  The caller's stream goes on: in the reference's iteration the next thing
         is gen_update (scripts/train.py:182-187), whose first ~15 ms -- two encodes, four decodes -- touch no discriminator
-        weight, so the exchange runs beside them.  Whatever reads or writes the discriminators next waits for the recorded event
-        (`_wait_dis`: the top of MsImageDis.forward, dis_update, save / resume / state_dict)."""
-        import torch.distributed as dist
-        comm = comm_stream(dev)
-        ops.stream_wait(comm, torch.cuda.current_stream(dev))
-        world = dp_world()
-        with torch.cuda.stream(comm):
-            dist.all_reduce(self.dis_opt.flat_g)          # RCCL is ordered behind, and hands back to, the CURRENT stream = comm
-            if world > 1:
-                ops.scale_(self.dis_opt.flat_g, 1.0 / world)
-            self.dis_opt_step()
-            ev = self._dis_event
-            if ev is None:
-                ev = self._dis_event = torch.cuda.Event()
-            ev.record(comm)
-        self._dis_pending = ev
-
-    def _wait_dis(self, *_):
-        """Order the current stream behind a deferred discriminator step (no-op when none is pending on this stream: every
-        stream that reaches the discriminators waits once)."""
-        ev = self._dis_pending
-        if ev is None:
-            return
-        st = torch.cuda.current_stream(self.dis_opt.flat_p.device)
-        key = st.cuda_stream
-        if key in self._dis_waited:
-            return
-        st.wait_event(ev)
-        self._dis_waited.add(key)
-
-    def _settle_dis(self):
-        """A new discriminator update (or a host-side reader) is about to start: the caller's stream waits, nothing pends."""
-        if self._dis_pending is not None:
-            self._wait_dis()
-            self._dis_pending = None
-        self._dis_waited = set()
+        weight, so the exchange runs beside them.  Whatever reads or writes the discriminators next waits at the optimizer's
+        gate (StepGate: the top of MsImageDis.forward, state_dict / load_state_dict, apply, every method of the optimizer)."""
+        self.dis_opt.step_on(comm_stream(dev), before=lambda: self._all_reduce_mean(self.dis_opt.flat_g),
+                             step=self.dis_opt_step)
 
     def _fwd_key(self, x_a, x_b):
         """Identity of a generator forward: the input tensors (storage, layout, in-place version) and the state of the
@@ -1372,7 +1417,6 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         return {k: v.detach().clone(memory_format=torch.contiguous_format).cpu() for k, v in sd.items()}
 
     def save(self, snapshot_dir, iterations):
-        self._settle_dis()
         gen_name = os.path.join(snapshot_dir, "gen_%08d.pt" % (iterations + 1))
         dis_name = os.path.join(snapshot_dir, "dis_%08d.pt" % (iterations + 1))
         opt_name = os.path.join(snapshot_dir, "optimizer.pt")
@@ -1385,7 +1429,6 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         torch.save({"gen": self.gen_opt.state_dict(), "dis": self.dis_opt.state_dict()}, opt_name)
 
     def resume(self, checkpoint_dir, hyperparameters):
-        self._settle_dis()
         last_model_name = get_model_list(checkpoint_dir, "gen")
         state_dict = torch.load(last_model_name, map_location="cpu", weights_only=True)
         if self.gen_state == 0:

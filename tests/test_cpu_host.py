@@ -532,7 +532,7 @@ def test_trainer_method_surface_is_the_reference_s():
 
 def test_data_parallel_host_hooks_without_a_device():
     """Host wiring of the data-parallel schedule on a CPU-built trainer (no kernel runs): the discriminators call the
-    trainer's wait at the top of forward() -- calc_gen_loss / calc_dis_loss reach forward() directly, as the reference's do
+    wait of their optimizer's gate at the top of forward() -- calc_gen_loss / calc_dis_loss reach forward() directly, as the reference's do
     (networks.py:84-85, 104), so a module pre-hook would miss them --, the wait and the settle are no-ops while nothing is
     pending, apply() on the trainer or on a sub-network works before any device buffer exists, the content encoders hand out the
     tensor that enters their residual trunk only when asked, and the optimizer-step deferral is not taken without a process group."""
@@ -540,10 +540,11 @@ def test_data_parallel_host_hooks_without_a_device():
     from munit_amd.utils import weights_init
     tr = T.MUNIT_Trainer(O.default_hp(64, 1, 1))
     for d in (tr.dis_a, tr.dis_b):
-        assert d.before_forward == tr._wait_dis
-    assert tr._dis_pending is None and tr._wait_dis() is None
-    tr._settle_dis()
-    assert tr._dis_waited == set() and tr.last_exchange is None
+        assert d.before_forward == tr.dis_opt.gate.wait
+    gate = tr.dis_opt.gate
+    assert gate.pending is None and gate.wait() is None
+    tr.dis_opt.settle()
+    assert gate.pending is None and gate.waited == set() and tr.last_exchange is None
     w0 = tr.dis_a.cnns[0][0].conv.weight.detach().clone()
     torch.manual_seed(5)
     tr.dis_a.apply(weights_init("gaussian"))            # sub-network apply with the image refresh tail: no optimizer buffer on a device yet
@@ -556,6 +557,250 @@ def test_data_parallel_host_hooks_without_a_device():
     assert T.OVERLAP_EXCHANGE
     # the state_dict of a discriminator goes through the wait as well (registered pre-hook) and is unchanged by it
     assert list(tr.dis_a.state_dict().keys())[:2] == ["cnns.0.0.conv.weight", "cnns.0.0.conv.bias"]
+
+
+class _Event(object):
+    """Stand-in for the event a deferred step records."""
+
+
+class _Stream(object):
+    """Stand-in for a device stream: a handle, and the events it was told to wait for."""
+
+    def __init__(self, handle):
+        self.cuda_stream, self.waits = handle, []
+
+    def wait_event(self, ev):
+        self.waits.append(ev)
+
+
+def _streams(monkeypatch, *handles):
+    """Stand-in streams; the first is current, `use(s)` makes another one current (where StepGate asks torch for it)."""
+    sts = [_Stream(h) for h in handles]
+    cur = [sts[0]]
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: cur[0])
+    return sts, lambda s: cur.__setitem__(0, s)
+
+
+def _reached(fn):
+    """Every object a callable holds on to: through __self__, __func__, __closure__, a hook wrapper's `hook`, a partial's
+    parts, and the attributes of a StepGate."""
+    from munit_amd.trainer import StepGate
+    seen, todo = {}, [fn]
+    while todo:
+        o = todo.pop()
+        if o is None or id(o) in seen:
+            continue
+        seen[id(o)] = o
+        todo += [getattr(o, a, None) for a in ("__self__", "__func__", "__wrapped__", "hook", "func")]
+        todo += [c.cell_contents for c in (getattr(o, "__closure__", None) or ())]
+        todo += list(getattr(o, "args", None) or ()) if hasattr(o, "func") else []
+        if isinstance(o, StepGate):
+            for v in vars(o).values():
+                todo += list(v) if isinstance(v, (set, list, tuple)) else [v]
+    return list(seen.values())
+
+
+def test_a_copy_of_a_discriminator_takes_an_idle_gate_and_nothing_of_the_trainer():
+    """copy.deepcopy of dis_a / dis_b (EMA, snapshot copies): the memo holds neither the trainer nor an optimizer, the copy's
+    forward hook and its state_dict / load_state_dict hooks reach no MUNIT_Trainer and no FusedAdam, and they hold a gate of
+    their own on which nothing is pending -- also when the original's gate is armed."""
+    import copy
+    from munit_amd import trainer as T
+    tr = T.MUNIT_Trainer(O.default_hp(64, 1, 1))
+    tr.dis_opt.gate.arm(_Event())
+    for d in (tr.dis_a, tr.dis_b):
+        memo = {}
+        c = copy.deepcopy(d, memo)
+        assert not {id(tr), id(tr.gen_opt), id(tr.dis_opt)} & set(memo)
+        hooks = [c.before_forward] + list(c._state_dict_pre_hooks.values()) + list(c._load_state_dict_pre_hooks.values())
+        assert len(hooks) == 3 and all(h is not None for h in hooks)
+        gates = set()
+        for h in hooks:
+            objs = _reached(h)
+            assert not [o for o in objs if isinstance(o, (T.MUNIT_Trainer, T.FusedAdam))], h
+            gates |= {id(o) for o in objs if isinstance(o, T.StepGate)}
+        gate = c.before_forward.__self__
+        assert gates == {id(gate)} and isinstance(gate, T.StepGate) and gate is not tr.dis_opt.gate
+        assert gate.pending is None and gate.event is None and gate.waited == set()
+        for p in c.parameters():                       # the copy's parameters belong to no optimizer
+            assert getattr(p, "_munit_opt", None) is None
+    assert tr.dis_opt.gate.pending is not None          # the original is as it was
+    # the hooks of the original hold the gate as well, nothing larger
+    for h in [tr.dis_a.before_forward] + list(tr.dis_a._state_dict_pre_hooks.values()):
+        assert not [o for o in _reached(h) if isinstance(o, (T.MUNIT_Trainer, T.FusedAdam))]
+
+
+def test_step_gate_waits_once_per_stream_and_settles(monkeypatch):
+    """StepGate on stand-in events and streams: arm, then one wait_event per stream however often it asks; settle waits on
+    the current stream if it has not yet and leaves nothing pending and nobody recorded; an idle gate calls nothing."""
+    import copy
+    from munit_amd.trainer import StepGate
+    (a, b, c), use = _streams(monkeypatch, 11, 22, 33)
+    gate = StepGate()
+    gate.wait()
+    gate.settle()
+    assert gate.pending is None and gate.waited == set() and not (a.waits or b.waits or c.waits)
+    ev = _Event()
+    gate.arm(ev)
+    assert gate.pending is ev and gate.waited == set()
+    gate.wait()
+    assert a.waits == [ev] and gate.waited == {11}
+    gate.wait()
+    assert a.waits == [ev]                              # the second wait on the same stream calls nothing
+    use(b)
+    gate.wait()
+    assert b.waits == [ev] and a.waits == [ev] and gate.waited == {11, 22}
+    use(c)
+    gate.settle()                                       # this stream has not waited yet: it does, then nothing pends
+    assert c.waits == [ev] and gate.pending is None and gate.waited == set()
+    gate.arm(ev)
+    use(a)
+    gate.wait()
+    gate.settle()                                       # this one has: no second wait
+    assert a.waits == [ev, ev] and gate.pending is None and gate.waited == set()
+    gate.wait()
+    gate.settle()
+    assert a.waits == [ev, ev] and b.waits == [ev] and c.waits == [ev]
+    # a copy is a fresh gate; re-binding the optimizer drops the event with the device it belonged to
+    gate.arm(ev, "dev0")
+    twin = copy.deepcopy(gate)
+    assert twin is not gate and twin.pending is None and twin.event is None and twin.device is None and twin.waited == set()
+    gate.reset()
+    assert a.waits == [ev, ev, ev] and gate.pending is None and gate.event is None and gate.device is None
+
+
+def test_every_host_side_entry_settles_the_optimizers_gate(monkeypatch):
+    """With a step pending on dis_opt's gate (stand-in event), each host-side way to the discriminators' weights or the
+    optimizer's buffers waits exactly once on the current stream and leaves the gate idle; the generator's optimizer has a
+    gate of its own and does not wait for the discriminators'."""
+    from munit_amd import ops, trainer as T
+    from munit_amd.utils import weights_init
+    tr = T.MUNIT_Trainer(O.default_hp(64, 1, 1))
+    (st,), _ = _streams(monkeypatch, 7)
+    gate = tr.dis_opt.gate
+    assert tr.gen_opt.gate is not gate and isinstance(tr.gen_opt.gate, T.StepGate)
+    osd = tr.dis_opt.state_dict()
+    msd = {k: v.detach().clone() for k, v in tr.dis_a.state_dict().items()}
+    entries = [
+        ("dis_opt.state_dict", lambda: tr.dis_opt.state_dict()),
+        ("dis_opt.load_state_dict", lambda: tr.dis_opt.load_state_dict(osd)),
+        ("dis_opt.zero_grad", lambda: tr.dis_opt.zero_grad()),
+        ("dis_opt.invalidate_prepared", lambda: tr.dis_opt.invalidate_prepared()),
+        ("dis_opt.settle", lambda: tr.dis_opt.settle()),
+        ("dis_a.state_dict", lambda: tr.dis_a.state_dict()),
+        ("dis_a.load_state_dict", lambda: tr.dis_a.load_state_dict(msd)),
+        ("dis_b.load_state_dict", lambda: tr.dis_b.load_state_dict(msd)),
+        ("dis_a.apply", lambda: tr.dis_a.apply(weights_init("gaussian"))),
+        ("trainer.apply", lambda: tr.apply(weights_init("kaiming"))),
+        ("trainer.state_dict", lambda: tr.state_dict()),
+        ("trainer.to", lambda: tr.to("cpu")),
+        ("dis_opt.bind", lambda: tr.dis_opt.bind(torch.device("cpu"))),
+    ]
+    for name, entry in entries:
+        ev = _Event()
+        gate.arm(ev)
+        del st.waits[:]
+        entry()
+        assert st.waits == [ev], (name, st.waits)
+        assert gate.pending is None and gate.waited == set(), name
+        entry()                                         # nothing pending: nothing waits
+        assert st.waits == [ev], name
+    # the step methods settle as well (the kernel itself is not under test)
+    steps = []
+    monkeypatch.setattr(ops, "adam_step", lambda *a: steps.append(a[0]))
+    ev = _Event()
+    gate.arm(ev)
+    del st.waits[:]
+    tr.gen_opt.step()
+    assert steps == [tr.gen_opt.flat_p] and st.waits == [] and gate.pending is ev      # not the generator's business
+    tr.dis_opt.step()
+    assert steps[-1] is tr.dis_opt.flat_p and st.waits == [ev] and gate.pending is None
+
+
+def test_step_on_orders_exchange_step_and_event_on_the_given_stream(monkeypatch):
+    """FusedAdam.step_on on stand-ins: the stream is ordered behind the caller's, `before` and the step run under it, the
+    event is recorded on it after them, and only then is the gate armed; the next entry waits for that event."""
+    import contextlib
+    from munit_amd import ops, trainer as T
+    tr = T.MUNIT_Trainer(O.default_hp(64, 1, 1))
+    (main, comm), _ = _streams(monkeypatch, 1, 2)
+    comm.device = torch.device("cpu")
+    log = []
+
+    class Ev(_Event):
+        def record(self, stream):
+            log.append(("record", stream.cuda_stream))
+
+    @contextlib.contextmanager
+    def under(stream):
+        log.append(("enter", stream.cuda_stream))
+        yield
+        log.append(("exit", stream.cuda_stream))
+
+    monkeypatch.setattr(torch.cuda, "Event", Ev)
+    monkeypatch.setattr(torch.cuda, "stream", under)
+    monkeypatch.setattr(ops, "stream_wait", lambda s, on: log.append(("stream_wait", s.cuda_stream, on.cuda_stream)))
+    monkeypatch.setattr(ops, "adam_step", lambda *a: log.append(("adam_step", tr.dis_opt.gate.pending)))
+    opt = tr.dis_opt
+    opt.step_on(comm, before=lambda: log.append(("before", opt.gate.pending)))
+    assert log == [("stream_wait", 2, 1), ("enter", 2), ("before", None), ("adam_step", None), ("record", 2), ("exit", 2)], log
+    ev = opt.gate.pending
+    assert isinstance(ev, Ev) and opt.gate.event is ev and opt.gate.device == comm.device and opt._step == 1
+    opt.zero_grad()
+    assert main.waits == [ev] and opt.gate.pending is None
+    # the step to run is the caller's choice (the trainer passes dis_opt_step: ExtraAdam extrapolates on even iterations)
+    del log[:]
+    opt.step_on(comm, step=lambda: log.append(("my step",)))
+    assert [e[0] for e in log] == ["stream_wait", "enter", "my step", "record", "exit"] and opt.gate.pending is ev
+    opt.bind(torch.device("cpu"))                       # re-binding settles and drops the event
+    assert main.waits == [ev, ev] and opt.gate.pending is None and opt.gate.event is None
+
+
+def test_the_three_mean_all_reduces_are_one_function(monkeypatch):
+    """MUNIT_Trainer._all_reduce_mean, GradExchange.finish and the exchange of the deferred discriminator step all go
+    through trainer.all_reduce_mean; the function itself issues the collectives in the order given, waits for the stages that
+    went out earlier and scales once."""
+    import torch.distributed as dist
+    from munit_amd import trainer as T
+    real = T.all_reduce_mean
+    calls = []
+    monkeypatch.setattr(T, "all_reduce_mean", lambda *a, **k: calls.append((a, k)))
+    monkeypatch.setattr(T, "dp_world", lambda: 2)
+    flat = torch.arange(12, dtype=torch.float32)
+    T.MUNIT_Trainer._all_reduce_mean(flat)
+    assert len(calls) == 1 and calls[0][0][0] is flat and calls[0][0][1] == 2
+    xch = T.GradExchange(flat, 2)
+    xch.stages.append({"ranges": [(4, 8)], "pending": 0, "fired": True})
+    xch.works.append("work")
+    xch.finish()
+    assert len(calls) == 2
+    a, k = calls[1]
+    assert a[0] is flat and a[1] == 2 and list(a[2:]) + list(k.values()) == [[(0, 4), (8, 12)], ["work"]]
+    tr = T.MUNIT_Trainer(O.default_hp(64, 1, 1))
+    kept = {}
+    monkeypatch.setattr(T, "comm_stream", lambda dev: "comm")
+    monkeypatch.setattr(tr.dis_opt, "step_on", lambda stream, before=None, step=None: kept.update(stream=stream, before=before, step=step))
+    tr._defer_dis_step(torch.device("cpu"))
+    assert kept["stream"] == "comm" and kept["step"] == tr.dis_opt_step and len(calls) == 2
+    kept["before"]()
+    assert len(calls) == 3 and calls[2][0][0] is tr.dis_opt.flat_g and calls[2][0][1] == 2
+    # the function: whole buffer / ranges in order, then the waits, then one scale; world 1 does not scale
+    log = []
+    monkeypatch.setattr(dist, "all_reduce", lambda t, *a, **k: log.append(("all_reduce", t.data_ptr(), t.numel())))
+
+    class Work(object):
+        def wait(self):
+            log.append(("wait",))
+
+    x = torch.full((12,), 3.0)
+    real(x, 2)
+    assert log == [("all_reduce", x.data_ptr(), 12)] and torch.equal(x, torch.full((12,), 1.5))
+    del log[:]
+    real(x, 2, [(0, 4), (8, 12)], [Work()])
+    assert log == [("all_reduce", x.data_ptr(), 4), ("all_reduce", x[8:].data_ptr(), 4), ("wait",)]
+    assert torch.equal(x, torch.full((12,), 0.75))
+    real(x, 1)
+    assert torch.equal(x, torch.full((12,), 0.75))
 
 
 

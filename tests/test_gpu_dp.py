@@ -35,7 +35,7 @@ def _step(trainer, hp, batch, record=False):
 
     run(lambda: trainer.dis_update(x_a, x_b, hp))
     # no read of the discriminator buffers here: in data-parallel mode their exchange and optimizer step are still in flight on
-    # the communication stream (trainer._defer_dis_step) while gen_update's generator forward runs -- gen_update freezes the
+    # the communication stream (FusedAdam.step_on) while gen_update's generator forward runs -- gen_update freezes the
     # discriminators, so their gradient and weights are read after it
     run(lambda: trainer.gen_update(x_a, x_b, hp, m_a, m_b))
     torch.cuda.synchronize()
@@ -68,7 +68,7 @@ def _worker(rank, world, tmpdir):
     init = [(o, o.flat_p.detach().clone()) for o in (tr.gen_opt, tr.dis_opt)]
 
     def fresh(guided):
-        tr._settle_dis()
+        tr.dis_opt.settle()
         torch.cuda.synchronize()
         with torch.no_grad():
             for o, p0 in init:
@@ -87,9 +87,9 @@ def _worker(rank, world, tmpdir):
         stages = tr.last_exchange.stages
         assert len(stages) == 2 and all(st["fired"] for st in stages), stages
         assert stages[0]["ranges"] == [tuple(r) for r in tr._early_ranges] and stages[1]["ranges"] == [tuple(r) for r in tr._trunk_ranges]
-        assert tr._dis_pending is not None           # the discriminator step was deferred ...
+        assert tr.dis_opt.gate.pending is not None   # the discriminator step was deferred ...
         # ... and gen_update's discriminator forwards (calc_gen_loss -> forward, on the two branch streams) waited for it
-        assert len(tr._dis_waited) >= (2 if T.BRANCH_STREAMS else 1), tr._dis_waited
+        assert len(tr.dis_opt.gate.waited) >= (2 if T.BRANCH_STREAMS else 1), tr.dis_opt.gate.waited
         sd_g = {k: v.detach().cpu().clone() for k, v in tr.gen.state_dict().items()}
         sd_d = {k: v.detach().cpu().clone() for k, v in tr.dis_a.state_dict().items()}
         # the same step with ONE all-reduce after backward and the discriminator step in line: bitwise the same averaged
@@ -98,7 +98,7 @@ def _worker(rank, world, tmpdir):
         T.OVERLAP_EXCHANGE = False
         out2 = _step(tr, hp_g, batch)
         T.OVERLAP_EXCHANGE = True
-        assert tr._dis_pending is None and tr.last_exchange is None
+        assert tr.dis_opt.gate.pending is None and not tr.dis_opt.gate.waited and tr.last_exchange is None
         assert torch.equal(out[1], out2[1]) and torch.equal(out[0], out2[0]) and torch.equal(out[2], out2[2]), guided
         for (k, a), b in zip(sd_g.items(), tr.gen.state_dict().values()):
             assert torch.equal(a, b.detach().cpu()), (guided, k)
@@ -215,7 +215,7 @@ def _semantic_worker(rank, world, tmpdir, ckpt, no_overlap):
     assert tr.segmentation_model is not None
     g_dis, g_gen, dis_p, _ = _step(tr, hp, batch)
     if no_overlap:
-        assert tr.last_exchange is None and tr._dis_pending is None
+        assert tr.last_exchange is None and tr.dis_opt.gate.pending is None
         fired = []
     else:
         stages = tr.last_exchange.stages
@@ -322,7 +322,7 @@ dist.init_process_group("nccl", init_method="file://" + %(rdzv)r, rank=0, world_
 assert T.FORCE_ALLREDUCE
 got = run()                                      # same steps with the RCCL all-reduce of both flat gradients issued: staged
 # generator exchange, discriminator exchange + Adam on the communication stream beside the next generator forward
-assert got.last_exchange is not None and len(got.last_exchange.stages) == 2 and got._dis_pending is not None
+assert got.last_exchange is not None and len(got.last_exchange.stages) == 2 and got.dis_opt.gate.pending is not None
 for a, b in zip(ref.parameters(), got.parameters()):
     assert torch.equal(a, b)
 assert torch.equal(ref.dis_opt.flat_m, got.dis_opt.flat_m) and torch.equal(ref.gen_opt.flat_v, got.gen_opt.flat_v)
@@ -363,6 +363,146 @@ def test_nccl_backend_world1_step(tmp_path):
     if os.path.isdir(keep):
         with open(os.path.join(keep, "nccl_world1_allreduce.json"), "w") as f:
             f.write(line + "\n")
+
+
+_GATE_WORKER = r"""
+import os, sys, torch, torch.distributed as dist
+sys.path.insert(0, %(root)r)
+os.environ["MUNIT_FORCE_ALLREDUCE"] = "1"
+import bench
+from munit_amd import trainer as T
+from munit_amd.utils import weights_init
+torch.cuda.set_device(0)
+dev = torch.device("cuda", 0)
+dist.init_process_group("nccl", init_method="file://" + %(rdzv)r, rank=0, world_size=1, device_id=dev)
+assert T.FORCE_ALLREDUCE and T.OVERLAP_EXCHANGE
+hp = bench.bench_hp(64, 2)
+x_a, x_b, m_a, m_b = (t.to(dev) for t in bench.make_batch(2, 64, 0))
+torch.manual_seed(1234)
+tr = T.MUNIT_Trainer(hp); tr.to(dev)
+opt, gate = tr.dis_opt, tr.dis_opt.gate
+init = [(o, o.flat_p.detach().clone()) for o in (tr.gen_opt, tr.dis_opt)]
+sd0 = {k: v.detach().clone() for k, v in tr.dis_a.state_dict().items()}
+
+def restore(state):
+    opt.settle()
+    torch.cuda.synchronize()
+    with torch.no_grad():
+        for o, p0, m0, v0, step in state:
+            o.flat_p.copy_(p0)
+            o.flat_m.zero_() if m0 is None else o.flat_m.copy_(m0)
+            o.flat_v.zero_() if v0 is None else o.flat_v.copy_(v0)
+            o._step = step
+            o.invalidate_prepared()
+    torch.cuda.synchronize()
+
+def fresh():                  # every case is the FIRST update of the same trainer
+    restore([(o, p0, None, None, 0) for o, p0 in init])
+
+def update(deferred):
+    T.OVERLAP_EXCHANGE = deferred
+    torch.manual_seed(11)
+    tr.dis_update(x_a, x_b, hp)
+    T.OVERLAP_EXCHANGE = True
+    assert (gate.pending is not None) == deferred, deferred   # deferred: the step is in flight on the communication stream
+
+def probe():
+    with torch.no_grad():
+        outs = [o.clone() for o in tr.dis_a(x_a)]
+    torch.cuda.synchronize()
+    return outs
+
+def same(a, b, what):
+    assert len(a) == len(b), what
+    for i, (s, t) in enumerate(zip(a, b)):
+        assert torch.equal(s, t), (what, i)
+
+def same_state(a, b, what):
+    assert a["param_groups"] == b["param_groups"] and list(a["state"]) == list(b["state"]) and len(a["state"]) > 0, what
+    for i in a["state"]:
+        for k in ("step", "exp_avg", "exp_avg_sq"):
+            assert torch.equal(a["state"][i][k], b["state"][i][k]), (what, i, k)
+
+# ---- 1. optimizer state: state_dict(), and flat_p after settle(), against the step in line
+fresh(); update(False)
+torch.cuda.synchronize()
+ref_sd, ref_p = opt.state_dict(), opt.flat_p.clone()
+fresh(); update(True)
+same_state(opt.state_dict(), ref_sd, "state_dict")
+assert gate.pending is None
+fresh(); update(True)
+opt.settle()
+got_p = opt.flat_p.clone()
+assert torch.equal(got_p, ref_p) and not torch.equal(got_p, init[1][1])
+print("case 1 ok")
+
+# ---- 2. load_state_dict on a discriminator
+fresh()
+ref_out = probe()                                             # a settled trainer that holds sd0
+fresh(); update(True)
+tr.dis_a.load_state_dict(sd0)
+assert gate.pending is None
+out = probe()
+for k, v in tr.dis_a.state_dict().items():
+    assert torch.equal(v, sd0[k]), k
+same(out, ref_out, "load_state_dict")
+print("case 2 ok")
+
+# ---- 3. apply on a discriminator
+fresh()
+torch.manual_seed(5); tr.dis_a.apply(weights_init("gaussian"))
+torch.cuda.synchronize()
+ref_w = [p.detach().clone() for p in tr.dis_a.parameters()]
+ref_out = probe()
+assert not torch.equal(ref_w[0], sd0["cnns.0.0.conv.weight"])
+fresh(); update(True)
+torch.manual_seed(5); tr.dis_a.apply(weights_init("gaussian"))
+assert gate.pending is None
+out = probe()
+same([p.detach() for p in tr.dis_a.parameters()], ref_w, "apply: weights")
+same(out, ref_out, "apply: forward")
+print("case 3 ok")
+
+# ---- 4. a move to the host and back, then one more update
+fresh(); update(True)
+ev0 = gate.event
+assert ev0 is not None and gate.pending is ev0
+tr.cpu(); tr.to(dev)
+assert gate.pending is None and gate.event is None and tr.dis_opt.gate is gate and opt.flat_p.device == dev
+torch.cuda.synchronize()
+assert torch.equal(opt.flat_p, ref_p)                         # the move took the stepped weights along
+state = [(o, o.flat_p.clone(), o.flat_m.clone(), o.flat_v.clone(), o._step) for o in (tr.gen_opt, opt)]
+update(True)                                                  # defers again
+assert gate.event is not None and gate.event is not ev0
+opt.settle()
+got_p = opt.flat_p.clone()
+restore(state); update(False)
+torch.cuda.synchronize()
+assert torch.equal(got_p, opt.flat_p) and not torch.equal(got_p, ref_p)
+print("case 4 ok")
+dist.barrier()
+dist.destroy_process_group()
+print("gate ok")
+"""
+
+
+def test_host_side_entries_wait_for_the_deferred_discriminator_step(tmp_path):
+    """RCCL at world size 1 with MUNIT_FORCE_ALLREDUCE=1 -- the smallest configuration in which dis_update really leaves its
+    exchange + optimizer step in flight on the communication stream.  Right after such an update, with no synchronize and no
+    settle in between: dis_opt.state_dict() (and flat_p after dis_opt.settle()) is bitwise the in-line step's; dis_a.load_state_dict
+    leaves the loaded weights and the forward of a settled trainer holding them; a seeded dis_a.apply(weights_init) gives the
+    settled trainer's weights and forward; after trainer.cpu(); trainer.to(device) the next update defers again, on a new
+    event, and ends bitwise where the in-line step from the same state ends.  One child process, one trainer, 64 x 64, batch 2."""
+    import subprocess
+    script = tmp_path / "gate_w.py"
+    script.write_text(_GATE_WORKER % dict(root=ROOT, rdzv=str(tmp_path / "rdzv")))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    # the neighbouring _NCCL_WORKER child (two trainers, six updates) takes 9.6 s on an MI355X box, this one 7.0 s; the limit is
+    # three times the neighbour's time, which covers this one's resets of the trainer between the cases
+    p = subprocess.run([sys.executable, str(script)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=ROOT, env=env,
+                       timeout=30)
+    out = p.stdout.decode()
+    assert p.returncode == 0 and out.strip().endswith("gate ok"), out[-3000:]
 
 
 def test_bench_under_torchrun_one_rank():

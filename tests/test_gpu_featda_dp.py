@@ -621,7 +621,7 @@ def _final_worker(rank, world, tmpdir, name, ckpt, no_overlap):
                 out["losses"]["%d %s %s" % (len(out["calls"]), method, k)] = float(v.detach())
 
     run_iteration(tr, hp, FINAL_IT, dreal, pairs(), on_call)
-    tr._settle_dis()
+    tr.dis_opt.settle()
     torch.cuda.synchronize()
     opts = {"gen": tr.gen_opt, "dis": tr.dis_opt}
     mods = {}

@@ -292,8 +292,8 @@ def test_iterations_against_the_composed_oracle(fx, seg_model, tmp_path, name):
     for s in SINKS:
         assert getattr(ops, s) is None, s
     assert tr._fwd_cache is None
-    tr._settle_dis()
-    assert tr._dis_pending is None and tr._dis_waited == set()
+    tr.dis_opt.settle()
+    assert tr.dis_opt.gate.pending is None and tr.dis_opt.gate.waited == set()
     owned = [tr.gen, tr.dis_a, tr.dis_b]
     owned += [tr.domain_classifier_sr_a, tr.domain_classifier_sr_b] if feat is not None else []
     owned += [tr.output_classifier_sr_a, tr.output_classifier_sr_b] if out is not None else []

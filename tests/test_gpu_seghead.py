@@ -510,8 +510,8 @@ def test_featureda_iteration_with_the_head(tmp_path):
     for s in ("MASK_SINK", "L1_SINK", "SEG_SINK", "DANN_SINK"):
         assert getattr(ops, s) is None, s
     assert tr._fwd_cache is None
-    tr._settle_dis()
-    assert tr._dis_pending is None and tr._dis_waited == set()
+    tr.dis_opt.settle()
+    assert tr.dis_opt.gate.pending is None and tr.dis_opt.gate.waited == set()
     for m in (tr.gen, tr.dis_a, tr.dis_b, tr.domain_classifier_sr_a, tr.domain_classifier_sr_b, tr.segmentation_head):
         assert all(q.requires_grad for q in m.parameters())
     for name, opt in (("gen", tr.gen_opt), ("dis", tr.dis_opt), ("feat", tr.classif_opt_sr), ("seg", tr.segmentation_opt)):

@@ -29,7 +29,7 @@ def run(overlap, guided):
     torch.cuda.synchronize()
     out = [tr.gen_opt.flat_p.clone(), tr.gen_opt.flat_m.clone(), tr.gen_opt.flat_v.clone(), tr.dis_opt.flat_p.clone(),
            tr.dis_opt.flat_m.clone(), tr.dis_opt.flat_v.clone()]
-    return out, float(tr.loss_gen_total.detach()), float(tr.loss_dis_total.detach()), (tr.last_exchange is not None, tr._dis_pending is not None)
+    return out, float(tr.loss_gen_total.detach()), float(tr.loss_dis_total.detach()), (tr.last_exchange is not None, tr.dis_opt.gate.pending is not None)
 rc = 0
 for guided in (1, 0):
     ref, lg, ld, f0 = run(False, guided)
