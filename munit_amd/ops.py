@@ -10,8 +10,10 @@ gradient storage) backward-weight accumulates straight into it (beta = 1) and au
 None; otherwise the gradient is returned the ordinary way (used by the op-level tests).
 """
 import collections
+import contextlib
 import ctypes
 import os
+import types
 from ctypes import byref, c_float, c_int, c_void_p
 
 import torch
@@ -24,16 +26,18 @@ _ws_cache = {}
 # bench.py sets this to a list to time every convolution pass (forward, backward-data, backward-weight) with HIP events on
 # the launch stream: entries are (pass 0/1/2, the layer's _Plan, start event, end event).
 PROFILE = None
-# tests/parity.py sets this to a list to record, in call order, the sign pattern (output > 0) behind every ReLU /
-# LeakyReLU of a forward pass, so that the fp64 oracle can take the same branch at every kink.
+# The four kink sinks of the parity harness.  Each is None (recording off: one `is not None` test per op) or a list that the
+# ops append to in call order, so that the fp64 oracle can take the same branch at every kink.  `kinks` below is the only code
+# that assigns to them; everything else only reads them.
+# MASK_SINK: the sign pattern (output > 0) behind every ReLU / LeakyReLU of a forward pass
 MASK_SINK = None
-# likewise for the other kink of the objective: the sign of (input - target) behind every L1 term, in call order
+# L1_SINK: the other kink of the objective, the sign of (input - target) behind every L1 term
 L1_SINK = None
-# likewise for the frozen segmentation network of the semantic loss (munit_amd/segmentation.py): its ReLU sign patterns,
-# max-pool winners and pseudo-labels, in call order, kept apart so that the generator's kink order above is untouched
+# SEG_SINK: the frozen segmentation network of the semantic loss (munit_amd/segmentation.py): its ReLU sign patterns,
+# max-pool winners and pseudo-labels, kept apart so that the generator's kink order above is untouched
 SEG_SINK = None
-# likewise for the feature classifiers of adv_lambda / dfeat_lambda (networks.domainClassifier): the max-pool winners, the
-# ReLU sign patterns behind batch_norm and the block tails, in call order
+# DANN_SINK: the feature classifiers of adv_lambda / dfeat_lambda (networks.domainClassifier): the max-pool winners, the
+# ReLU sign patterns behind batch_norm and the block tails
 DANN_SINK = None
 # Data-parallel batch norm (adaptation.data_parallel: 1): the world size of the process group whose ranks share the batch
 # statistics of training-mode batch_norm, 0 = every process normalises its own batch.  Set by the trainer around the feature
@@ -49,6 +53,28 @@ def _count(pl, which):
     if FLOPS is not None:
         FLOPS["alg"] += pl.flop
         FLOPS["exec"] += pl.flop_exec[which]
+
+
+@contextlib.contextmanager
+def kinks(**channels):
+    """Record the kinks of the ops run inside the block: `with kinks(mask=True, l1=True) as k:` -> k.mask, k.l1.
+    Keywords mask / l1 / seg / dann name MASK_SINK / L1_SINK / SEG_SINK / DANN_SINK.  True records into a fresh list, a list
+    records into that list, None switches the channel off; a channel that is not named keeps what it has.  The object
+    yielded carries the four active lists (or None).  On exit, also when the block raises, every channel is back at its
+    value on entry, so blocks nest."""
+    global MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK
+    saved = {"mask": MASK_SINK, "l1": L1_SINK, "seg": SEG_SINK, "dann": DANN_SINK}
+    for name, v in channels.items():
+        if name not in saved:
+            raise TypeError("munit_amd: kinks() has no channel %r (mask, l1, seg, dann)" % name)
+        if v is not True and v is not None and not isinstance(v, list):
+            raise TypeError("munit_amd: kinks(%s=...) takes True, a list or None, got %r" % (name, v))
+    now = dict(saved, **{name: [] if v is True else v for name, v in channels.items()})
+    try:
+        MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK = now["mask"], now["l1"], now["seg"], now["dann"]
+        yield types.SimpleNamespace(**now)
+    finally:
+        MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK = saved["mask"], saved["l1"], saved["seg"], saved["dann"]
 
 
 # Arithmetic of the conv / linear contractions: "f32" (exact fp32 MFMA, the reference's arithmetic) or "bf16"

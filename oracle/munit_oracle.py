@@ -25,6 +25,7 @@ ground truth).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Optional, Tuple
 
@@ -43,7 +44,7 @@ LN_EPS = 1e-5  # LayerNorm default (networks.py:852)
 # --------------------------------------------------------------------------------------
 class KinkMasks:
     """Optional test hook (tests/parity.py): sign patterns of every ReLU / LeakyReLU, in call order, recorded from
-    another run of the same network.  While one is installed in KINK_MASKS, `activation` takes the recorded branch
+    another run of the same network.  While one is installed in KINK_MASKS (`pinned`), `activation` takes the recorded branch
     instead of its own comparison, so two runs that differ only by rounding differentiate the SAME piecewise-linear
     function (a pre-activation within rounding noise of 0 otherwise switches an upstream gradient element on or
     off).  Values change by at most that noise; the default (None) is the plain activation."""
@@ -92,6 +93,19 @@ class KinkMasks:
 
 
 KINK_MASKS: Optional[KinkMasks] = None
+
+
+@contextlib.contextmanager
+def pinned(km: Optional[KinkMasks]):
+    """Install `km` as KINK_MASKS for the block (the only writer of that global); the previous value is back on exit, also
+    when the block raises.  Blocks nest: `with pinned(None):` inside an outer block runs unpinned, and pinned(None) at the
+    top level is the plain oracle."""
+    global KINK_MASKS
+    before, KINK_MASKS = KINK_MASKS, km
+    try:
+        yield km
+    finally:
+        KINK_MASKS = before
 
 
 def activation(x: Tensor, kind: str) -> Tensor:

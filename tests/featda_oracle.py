@@ -4,7 +4,7 @@ training-mode BatchNorm2d with the running statistics, the three targets of comp
 domain_classifier_sr_update, trainer.py:1237-1265), and the step oracle that adds the fooling term (oracle_trainer_class).
 The optimizer arithmetic is oracle.munit_oracle's.
 
-A classifier is a dict of tensors under the reference's state_dict keys.  `pins` (optional): what ops.DANN_SINK recorded
+A classifier is a dict of tensors under the reference's state_dict keys.  `pins` (optional): what ops.kinks(dann=True) recorded
 from a HIP run of the same classifier call -- per call the first max-pool's winners, the ReLU sign pattern behind bn1 and
 behind the block tail, then the same three of the second half -- so that both runs differentiate the same piecewise-linear
 function; `audit` reports how far from its kink a pinned element that disagrees with the oracle's own choice lies."""

@@ -1,6 +1,6 @@
 """fp64 torch-CPU restatement of the non-saturating GAN loss (dis.gan_type: nsgan) of MsImageDis, scripts/networks.py:79-139,
 in the reference's literal form: per scale mean(binary_cross_entropy(sigmoid(x), target)), summed over the scales.  The network
-is oracle.munit_oracle's dis_forward, so the kinks of a HIP run are pinned through its KINK_MASKS as for every other loss.
+is oracle.munit_oracle's dis_forward, so the kinks of a HIP run are pinned through O.pinned as for every other loss.
 
 `swapped()` puts the d-loss and the g-loss in place of oracle.munit_oracle's LSGAN ones while active, so OracleTrainer and
 tests/parity.run_step_parity evaluate an nsgan step (tests/outda_oracle.py swaps O.dis_loss_g the same way).

@@ -1,7 +1,9 @@
 """Shared parity harness (tests/, __graft_entry__.smoke(), bench.py's checker leg): runs the
 HIP trainer and the CPU oracle on the same deterministic weights and inputs and reports
 normalised errors.  The oracle is the CHECKER here, never the thing measured or shipped."""
+import contextlib
 import math
+import types
 
 import numpy as np
 import os
@@ -39,8 +41,8 @@ class GradCheck:
     tensor upstream of x_ab (measured in round 1, tools/diag_grad.py / diag_xab.py; torch's own CPU fp32 run against
     fp64 shows the same signature).  That is a property of comparing two roundings of a non-smooth function, not of
     the kernels, and it used to be absorbed by a 5e-2 / 1e-1 per-tensor bound.  Now the HIP forward records the sign
-    pattern behind every ReLU / LeakyReLU (ops.MASK_SINK) and the fp64 oracle takes the same branches
-    (oracle.KINK_MASKS), so both sides differentiate the same piecewise-linear function and the comparison is tight:
+    pattern behind every ReLU / LeakyReLU (ops.MASK_SINK, written by ops.kinks) and the fp64 oracle takes the same branches
+    (oracle.KINK_MASKS, written by O.pinned), so both sides differentiate the same piecewise-linear function and the comparison is tight:
         pinned:    EVERY tensor <= 5e-5 normalised max AND <= 5e-5 relative L2, median L2 <= 1e-5 -- 200x below SURVEY.md 8c's
                    1e-2.  Measured on MI355X with all Winograd layers (tools/parity_report.py): 3 iterations at 64x64 worst
                    3.9e-6 max / 3.2e-6 L2, median 1.5e-6; gen_state 0: 4.3e-6 / 4.1e-6; 128x128: 3.1e-6 / 2.6e-6 -- below
@@ -92,6 +94,43 @@ class GradCheck:
 # of elements that may sit that close to a kink.
 KINK_NOISE = 5e-5
 KINK_FRAC = 1e-3
+
+
+def record(fn, seed=None, **channels):
+    """Run `fn` (HIP work) under ops.kinks -- by default mask=True, l1=True -- with the host RNG at `seed` if one is given,
+    then wait for the side streams and the device.  Returns (fn's result, O.KinkMasks of the recorded masks and L1 signs on
+    the CPU (None when both of those channels are off), the object ops.kinks yielded: .seg / .dann for those who record them)."""
+    from munit_amd import ops
+    if seed is not None:
+        torch.manual_seed(seed)
+    with ops.kinks(**dict({"mask": True, "l1": True}, **channels)) as k:
+        out = fn()
+    ops.join_side_streams()
+    torch.cuda.synchronize()
+    if k.mask is None and k.l1 is None:
+        return out, None, k
+    return out, O.KinkMasks([m.cpu() for m in k.mask or ()], None if k.l1 is None else [m.cpu() for m in k.l1]), k
+
+
+@contextlib.contextmanager
+def pinned(km, what=None, done=True, frac=True, check=True):
+    """Run the block (oracle work) with `km` pinned (O.pinned) and, on clean exit, audit it: every recorded pattern was
+    consumed, and the recorded branches differ from the oracle's own only within rounding noise of a kink (KINK_NOISE) and on a
+    small share of the elements (KINK_FRAC) -- a HIP mask that is wrong on a pre-activation of real size would be followed by
+    the pinned oracle, so it is caught here.  Yields an object whose worst_rel / disagree_frac hold the measured values after
+    the block.  km=None: no pinning, no audit.  check=False: the two bounds are reported, not asserted.  done=False /
+    frac=False drop that one condition: only for a site with a stated, measured reason."""
+    audit = types.SimpleNamespace(worst_rel=0.0, disagree_frac=0.0)
+    with O.pinned(km):
+        yield audit
+    if km is None:
+        return
+    audit.worst_rel, audit.disagree_frac = km.worst_rel, km.n_disagree / max(1, km.n_total)
+    assert not done or km.done(), ("the oracle ran fewer activations / L1 terms than the HIP forward recorded", what)
+    if check:
+        assert km.worst_rel <= KINK_NOISE, ("recorded mask differs from the oracle's own branch at a pre-activation of real size",
+                                            what, km.worst_rel, km.worst_at)
+        assert not frac or km.n_disagree <= KINK_FRAC * km.n_total, (what, km.n_disagree, km.n_total)
 
 
 def oracle_states(hp, dtype):
@@ -150,7 +189,6 @@ def run_step_parity(size=64, batch=2, gen_state=1, iters=1, device="cuda:0", ora
     direct convolutions) on the same weights, inputs and pinned kinks, and reports per tensor how far that fp32 evaluation of the
     reference is from fp64 (rep["ref32"]: list per iteration of (name, hip_max, hip_l2, ref32_max, ref32_l2)) -- the yardstick
     for what any fp32 implementation can reach at that network state."""
-    from munit_amd import ops
     from munit_amd.trainer import MUNIT_Trainer
 
     hp = O.default_hp(size, batch, gen_state)
@@ -204,32 +242,14 @@ def run_step_parity(size=64, batch=2, gen_state=1, iters=1, device="cuda:0", ora
 
         def hip(fn, seed):
             """run one HIP update with the host RNG at `seed`, recording the ReLU / LeakyReLU sign patterns"""
-            torch.manual_seed(seed)
-            ops.MASK_SINK = [] if pin_kinks else None
-            ops.L1_SINK = [] if pin_kinks else None
-            try:
-                fn()
-                masks, signs = ops.MASK_SINK, ops.L1_SINK
-            finally:
-                ops.MASK_SINK = ops.L1_SINK = None
-            return O.KinkMasks([m.cpu() for m in masks], [m.cpu() for m in signs]) if pin_kinks else None
+            return record(fn, seed, mask=pin_kinks or None, l1=pin_kinks or None)[1]
 
         def oracle(fn, masks):
-            O.KINK_MASKS = masks
-            try:
+            with pinned(masks, check=check) as audit:
                 out = fn()
-                assert masks is None or masks.done(), "the oracle ran fewer activations than the HIP forward recorded"
-            finally:
-                O.KINK_MASKS = None
             if masks is not None:
-                # the recorded branches may differ from the oracle's own only within rounding noise of a kink: a HIP mask
-                # that is wrong on a pre-activation of real size would be followed by the pinned oracle, so it is caught here
-                rep["kink_worst_rel"] = max(rep.get("kink_worst_rel", 0.0), masks.worst_rel)
-                rep["kink_disagree_frac"] = max(rep.get("kink_disagree_frac", 0.0), masks.n_disagree / max(1, masks.n_total))
-                if check:
-                    assert masks.worst_rel <= KINK_NOISE, ("recorded mask differs from the oracle's own branch at a "
-                                                           "pre-activation of real size", masks.worst_rel, masks.worst_at)
-                    assert masks.n_disagree <= KINK_FRAC * masks.n_total, (masks.n_disagree, masks.n_total)
+                rep["kink_worst_rel"] = max(rep.get("kink_worst_rel", 0.0), audit.worst_rel)
+                rep["kink_disagree_frac"] = max(rep.get("kink_disagree_frac", 0.0), audit.disagree_frac)
             return out
 
         km = hip(lambda: tr.dis_update(dx_a, dx_b, hp), 100 + it)

@@ -146,7 +146,7 @@ def unphase4(t):
 
 
 def head_pins(sink):
-    """ops.DANN_SINK of head forwards (6 records each), laid back out"""
+    """the ops.kinks(dann=True) list of head forwards (6 records each), laid back out"""
     assert len(sink) % PINS_PER_FORWARD == 0, len(sink)
     return D.Pins([unphase4(t.cpu()) for t in sink])
 

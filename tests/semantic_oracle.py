@@ -192,7 +192,7 @@ def audit(kinks, pins, rel=1e-5):
 
 def oracle_trainer_class(seg_model, sink, base=None):
     """An OracleTrainer (or `base`, a subclass of it) whose gen_losses adds the semantic term (trainer.py:504-509, 552) on
-    its own translations self._last["x_ab"] / ["x_ba"].  `sink`: a callable returning ops.SEG_SINK as the HIP gen_update
+    its own translations self._last["x_ab"] / ["x_ba"].  `sink`: a callable returning the ops.kinks(seg=...) list as the HIP gen_update
     left it (label pass kinks, labels, logits pass kinks); the oracle takes the device's labels and kink branches and audits
     them (`audit` allows a disagreement only at rounding-noise margins; labels only where the top-2 gap is that small).
     Stacked under tests/synth_oracle.py's class for a whole iteration: an instance whose `synth_call` is True (the call

@@ -82,7 +82,7 @@ def oracle_trainer_class(seg_model, sink, gts, base=None):
     """An OracleTrainer (or `base`, a subclass of it) whose gen_losses adds, after the base terms, the pair reconstruction
     term (recon_synth_w, through oracle.munit_oracle.l1_masked so that the step's last two pinned L1 sign patterns are
     consumed) and the semantic term against the ground truth `gts` = (gt_a, gt_b) (semantic_w) on its own translations.
-    `sink`: a callable returning ops.SEG_SINK as the HIP gen_update left it -- with a ground truth only the logits pass
+    `sink`: a callable returning the ops.kinks(seg=...) list as the HIP gen_update left it -- with a ground truth only the logits pass
     records; its kinks are pinned and audited as tests/semantic_oracle.py does.
     Stacked over tests/semantic_oracle.py's class for a whole iteration: an instance whose `synth_call` is False (the call
     being replayed is the real gen_update) adds neither term and leaves the semantic one to that class."""

@@ -855,3 +855,104 @@ def test_kernel_names_reported_by_the_library_exist_in_the_committed_trace():
                 seen.add(exact)
                 assert exact[:44] in text, (name, exact, os.path.basename(traces[-1]))
     assert "conv_lanes_wgrad_pk_kernel" in seen and "conv_wino_kernel<0, 0>" in seen and len(seen) >= 10, seen
+
+
+# ---- the parity harness's own plumbing: ops.kinks, O.pinned, tests/parity.pinned ------------------------------------------
+SINKS = ("MASK_SINK", "L1_SINK", "SEG_SINK", "DANN_SINK")
+
+
+def _sinks():
+    from munit_amd import ops
+    return tuple(getattr(ops, s) for s in SINKS)
+
+
+def test_kinks_records_into_fresh_and_passed_lists_and_restores():
+    from munit_amd import ops
+    assert _sinks() == (None,) * 4
+    mine = ["held by the oracle side"]
+    with ops.kinks(mask=True, seg=mine) as k:
+        assert k.mask == [] and ops.MASK_SINK is k.mask                 # True: a fresh list, and the global is that list
+        assert ops.SEG_SINK is mine and k.seg is mine                   # a passed list is used as is
+        assert ops.L1_SINK is None and ops.DANN_SINK is None and k.l1 is None and k.dann is None    # not named: left alone
+        ops.MASK_SINK.append(1)
+        with ops.kinks(l1=True) as inner:                               # not named here: the outer lists stay active
+            assert ops.MASK_SINK is k.mask and inner.mask is k.mask and inner.seg is mine and inner.l1 == []
+        assert ops.L1_SINK is None
+    assert _sinks() == (None,) * 4 and k.mask == [1] and mine == ["held by the oracle side"]
+
+
+def test_kinks_none_switches_a_channel_off_inside_a_recording_block():
+    from munit_amd import ops
+    with ops.kinks(mask=True, l1=True) as k:
+        ops.MASK_SINK.append("before")
+        with ops.kinks(mask=None) as off:
+            assert ops.MASK_SINK is None and off.mask is None
+            assert ops.L1_SINK is k.l1 and off.l1 is k.l1
+        assert ops.MASK_SINK is k.mask and k.mask == ["before"]         # the outer list is back, with its contents
+    assert _sinks() == (None,) * 4
+
+
+def test_kinks_restores_when_the_block_raises_and_refuses_unknown_names():
+    from munit_amd import ops
+    outer = []
+    with ops.kinks(dann=outer):
+        with pytest.raises(ZeroDivisionError):
+            with ops.kinks(mask=True, l1=True, seg=True, dann=None):
+                assert ops.DANN_SINK is None and ops.SEG_SINK == []
+                1 / 0
+        assert _sinks() == (None, None, None, outer) and ops.DANN_SINK is outer
+    assert _sinks() == (None,) * 4
+    with pytest.raises(TypeError):
+        with ops.kinks(masks=True):
+            pass
+    with pytest.raises(TypeError):
+        with ops.kinks(mask=False):
+            pass
+    assert _sinks() == (None,) * 4
+
+
+def test_oracle_pinned_installs_restores_and_nests():
+    km, inner = O.KinkMasks([]), O.KinkMasks([])
+    assert O.KINK_MASKS is None
+    with O.pinned(None):                                                # the unpinned mode: a no-op block
+        assert O.KINK_MASKS is None
+    with pytest.raises(ZeroDivisionError):
+        with O.pinned(km):
+            assert O.KINK_MASKS is km
+            1 / 0
+    assert O.KINK_MASKS is None                                         # restored on exception
+    with O.pinned(km):
+        with O.pinned(None):
+            assert O.KINK_MASKS is None
+        assert O.KINK_MASKS is km                                       # a nested pinned(None) restores the outer masks
+        with O.pinned(inner):
+            assert O.KINK_MASKS is inner
+        assert O.KINK_MASKS is km
+    assert O.KINK_MASKS is None
+
+
+def test_parity_pinned_audits_what_the_oracle_consumed():
+    from tests import parity
+    x = torch.tensor([[1.0, -2.0], [0.5, -0.25]], dtype=torch.float64)
+    with parity.pinned(O.KinkMasks([x > 0]), "agrees") as audit:        # every mask consumed, every branch the oracle's own
+        y = O.activation(x, "relu")
+    assert torch.equal(y, x.clamp_min(0)) and audit.worst_rel == 0.0 and audit.disagree_frac == 0.0
+    assert O.KINK_MASKS is None
+    with pytest.raises(AssertionError, match="fewer activations"):      # one recorded mask left over: done()
+        with parity.pinned(O.KinkMasks([x > 0, x > 0]), "left over"):
+            O.activation(x, "relu")
+    flipped = x > 0
+    flipped[0, 1] = True                                                # the recorded branch is wrong where |x| is the tensor's maximum
+    with pytest.raises(AssertionError, match="pre-activation of real size"):
+        with parity.pinned(O.KinkMasks([flipped]), "flipped") as audit:
+            O.activation(x, "relu")
+    assert audit.worst_rel == 1.0 and audit.disagree_frac == 0.25 and O.KINK_MASKS is None
+    with parity.pinned(O.KinkMasks([flipped]), "reported, not asserted", check=False) as audit:
+        O.activation(x, "relu")
+    assert audit.worst_rel == 1.0
+    with pytest.raises(ZeroDivisionError):                              # a block that raises is not audited; the masks still leave
+        with parity.pinned(O.KinkMasks([x > 0, x > 0])):
+            1 / 0
+    assert O.KINK_MASKS is None
+    with parity.pinned(None) as audit:                                  # no masks: no pinning, no audit
+        assert O.KINK_MASKS is None

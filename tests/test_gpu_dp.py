@@ -26,12 +26,10 @@ def _step(trainer, hp, batch, record=False):
     kinks = []
 
     def run(fn):
-        ops.MASK_SINK, ops.L1_SINK = ([], []) if record else (None, None)
-        try:
+        # ops.kinks, not parity.record: no wait between the two updates (see below)
+        with ops.kinks(mask=record or None, l1=record or None) as k:
             fn()
-            kinks.append(([m.cpu() for m in ops.MASK_SINK], [m.cpu() for m in ops.L1_SINK]) if record else None)
-        finally:
-            ops.MASK_SINK = ops.L1_SINK = None
+        kinks.append(([m.cpu() for m in k.mask], [m.cpu() for m in k.l1]) if record else None)
 
     run(lambda: trainer.dis_update(x_a, x_b, hp))
     # no read of the discriminator buffers here: in data-parallel mode their exchange and optimizer step are still in flight on
@@ -125,7 +123,8 @@ def test_two_rank_step_matches_the_oracle_on_the_joint_batch(tmp_path):
     import bench
     from munit_amd.trainer import MUNIT_Trainer
     from oracle import munit_oracle as O
-    from tests.parity import GradCheck, KINK_FRAC, KINK_NOISE, oracle_states, trainer_named_params
+    from tests import parity
+    from tests.parity import GradCheck, oracle_states, trainer_named_params
     mp.spawn(_worker, args=(2, str(tmp_path)), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "rank0.pt", weights_only=True)
     r1 = torch.load(tmp_path / "rank1.pt", weights_only=True)
@@ -152,14 +151,8 @@ def test_two_rank_step_matches_the_oracle_on_the_joint_batch(tmp_path):
         (m0, s0), (m1, s1) = r0["kinks"][phase], r1["kinks"][phase]
         assert len(m0) == len(m1) and len(s0) == len(s1)
         km = O.KinkMasks([torch.cat([a, b], 0) for a, b in zip(m0, m1)], [torch.cat([a, b], 0) for a, b in zip(s0, s1)])
-        O.KINK_MASKS = km
-        try:
-            out = fn()
-            assert km.done()
-        finally:
-            O.KINK_MASKS = None
-        assert km.worst_rel <= KINK_NOISE and km.n_disagree <= KINK_FRAC * km.n_total, (km.worst_rel, km.n_disagree, km.n_total)
-        return out
+        with parity.pinned(km, ("dis_update", "gen_update")[phase]):
+            return fn()
 
     orc.update_learning_rate()
     gc = GradCheck(pinned=True)

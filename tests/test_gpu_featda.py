@@ -146,11 +146,9 @@ def test_maxpool2_against_torch(hw, lattice):
     dy = torch.randn(yr.shape, generator=g)
     (dxr,) = torch.autograd.grad(yr, [xr], dy.double())
     xd = _nhwc(x).requires_grad_(True)
-    ops.DANN_SINK = sink = []
-    try:
+    with ops.kinks(dann=True) as k:
         y = ops.maxpool2(xd)
-    finally:
-        ops.DANN_SINK = None
+    sink = k.dann
     assert torch.equal(y.cpu().double(), yr.detach())
     # dx into a buffer full of NaN: every element written once, zeros on the losers and in the dropped row / column
     lib = _lib.load()
@@ -325,11 +323,9 @@ def _run_module(net, c, t, need_weight_grads=True):
     """one forward + backward of mean((net(c) - t)^2) with the kinks recorded: loss, output, d code, weight gradients"""
     ops.set_compute("f32")
     cd = _nhwc(c).requires_grad_(True)
-    ops.DANN_SINK = sink = []
-    try:
+    with ops.kinks(dann=True) as k:
         out = net(cd, need_weight_grads)
-    finally:
-        ops.DANN_SINK = None
+    sink = k.dann
     loss = ops.mse_const(out, t)
     ps = [p for p in net.parameters()]
     grads = torch.autograd.grad(loss, [cd] + (ps if need_weight_grads else []), allow_unused=True)
@@ -477,12 +473,10 @@ def test_the_sequence_of_updates_against_the_oracle(optimizer):
     for it, synth in ((0, False), (1, True)):
         tr.iterations = it
         c_a, c_b = _codes(tr, x_a, x_b)
-        ops.DANN_SINK = sink = []
-        try:
+        with ops.kinks(dann=True) as k:
             tr.gen_update(x_a, x_b, hp, m_a, m_b, synth=synth)
-        finally:
-            ops.DANN_SINK = None
         torch.cuda.synchronize()
+        sink = k.dann
         assert len(sink) == 2 * D.PINS_PER_CALL
         l_ref, _, _ = D.fool_term(sd_a, sd_b, c_a, c_b, pins=_pins(sink))
         rel = abs(float(tr.loss_classifier_sr) - float(l_ref)) / abs(float(l_ref))
@@ -499,12 +493,10 @@ def test_the_sequence_of_updates_against_the_oracle(optimizer):
         _compare_classifiers(tr, sd_a, sd_b, "after gen_update %d" % it, hp["lr"])      # weights untouched, running statistics moved
         # the classifier's own update on the generator's NEW weights
         c_a, c_b = _codes(tr, x_a, x_b)
-        ops.DANN_SINK = sink = []
-        try:
+        with ops.kinks(dann=True) as k:
             tr.domain_classifier_sr_update(x_a, x_b, synth, hp["adaptation"]["dfeat_lambda"], it)
-        finally:
-            ops.DANN_SINK = None
         torch.cuda.synchronize()
+        sink = k.dann
         l_ref = D.classifier_update(sd_a, sd_b, opt, c_a, c_b, synth, hp["adaptation"]["dfeat_lambda"], it,
                                     pins=_pins(sink))
         rel = abs(float(tr.loss_classifier_sr_update) - float(l_ref)) / abs(float(l_ref))
@@ -534,23 +526,17 @@ def _step_parity(monkeypatch, iters, **over):
         synth = shared["n"] % 2 == 1
         shared["n"] += 1
         shared["sd"] = _oracle_of(self)
-        ops.DANN_SINK = shared["sink"] = []
-        try:
+        with ops.kinks(dann=True) as k:
             plain(self, xa, xb, hp, mask_a, mask_b, synth=synth)
-        finally:
-            ops.DANN_SINK = None
+        shared["sink"] = k.dann
         shared["reused"].append(self.fwd_reused)
         torch.cuda.synchronize()
         # the oracle of this gen_update runs next and moves shared["sd"]'s running statistics: compared afterwards
-        keep = ops.MASK_SINK, ops.L1_SINK           # the classifier's own update is not part of the compared step
-        ops.MASK_SINK = ops.L1_SINK = None
-        try:
+        with ops.kinks(mask=None, l1=None):         # the classifier's own update is not part of the compared step
             shared["stats"] = {pre + k: v.clone() for pre, m in (("a.", self.domain_classifier_sr_a),
                                                                   ("b.", self.domain_classifier_sr_b))
                                for k, v in m.state_dict().items()}
             self.domain_classifier_sr_update(xa, xb, synth, hp["adaptation"]["dfeat_lambda"], self.iterations)
-        finally:
-            ops.MASK_SINK, ops.L1_SINK = keep
 
     monkeypatch.setattr(MUNIT_Trainer, "gen_update", gen_update)
     hp_over = {"gen": {"n_res": 1}, "dis": {"num_scales": 1}, "adaptation": {"adv_lambda": 6, "dfeat_lambda": 1}}

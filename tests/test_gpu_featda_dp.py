@@ -20,7 +20,7 @@ from munit_amd import _lib
 from tests import featda_oracle as D
 from tests.conv_contract import ERR_WORKSPACE, GUARD_BYTE, Arena, fill_random, no_nan, poison, stream
 from tests.kernel_contract import ERR_ARG, refused
-from tests.parity import nerr
+from tests.parity import nerr, pinned, record
 from tests.test_gpu_featda import FWD_TOL, GRAD_TOL, LOSS_TOL, _bn_ref, _contract, _rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -285,13 +285,7 @@ def _feat_worker(rank, world, tmpdir, no_overlap):
             return (tr._content_enc(1)(ops.nhwc(x_a)).cpu().double(), tr._content_enc(2)(ops.nhwc(x_b)).cpu().double())
 
     def recorded(fn):
-        ops.DANN_SINK = sink = []
-        try:
-            fn()
-        finally:
-            ops.DANN_SINK = None
-        torch.cuda.synchronize()
-        return [t.cpu() for t in sink]
+        return [t.cpu() for t in record(fn, mask=None, l1=None, dann=True)[2].dann]
 
     for it, synth in ((0, False), (1, True)):
         rec = {"sd_a": _cpu_state(tr.domain_classifier_sr_a), "sd_b": _cpu_state(tr.domain_classifier_sr_b), "codes": codes(),
@@ -305,12 +299,8 @@ def _feat_worker(rank, world, tmpdir, no_overlap):
     tr.dis_update(x_a, x_b, hp)
     out["fool"] = {"sd_a": _cpu_state(tr.domain_classifier_sr_a), "sd_b": _cpu_state(tr.domain_classifier_sr_b),
                    "codes": codes()}
-    ops.MASK_SINK, ops.L1_SINK = [], []
-    try:
-        out["fool"]["sink"] = recorded(lambda: tr.gen_update(x_a, x_b, hp, m_a, m_b))
-        out["fool"]["kinks"] = ([m.cpu() for m in ops.MASK_SINK], [m.cpu() for m in ops.L1_SINK])
-    finally:
-        ops.MASK_SINK = ops.L1_SINK = None
+    _, km, k = record(lambda: tr.gen_update(x_a, x_b, hp, m_a, m_b), dann=True)
+    out["fool"]["sink"], out["fool"]["kinks"] = [t.cpu() for t in k.dann], (km.masks, km.l1_signs)
     out["fool"]["loss"] = float(tr.loss_classifier_sr.detach())
     if not no_overlap:
         assert tr.last_exchange is not None and tr.last_exchange.fired      # the staged exchange ran inside backward
@@ -341,7 +331,7 @@ def _generator_gradient_check(hp2, orc_cls, r0, r1, joint, kinks0, kinks1, attac
     tests/parity.GradCheck's pinned ones."""
     from munit_amd.trainer import MUNIT_Trainer
     from oracle import munit_oracle as O
-    from tests.parity import KINK_FRAC, KINK_NOISE, GradCheck, oracle_states, trainer_named_params
+    from tests.parity import GradCheck, oracle_states, trainer_named_params
     torch.manual_seed(0)
     tr = MUNIT_Trainer(dict(hp2)).to(DEV)
     gnames, dnames = trainer_named_params(tr)
@@ -355,13 +345,8 @@ def _generator_gradient_check(hp2, orc_cls, r0, r1, joint, kinks0, kinks1, attac
     (m0, s0), (m1, s1) = kinks0, kinks1
     assert len(m0) == len(m1) > 0 and len(s0) == len(s1)
     km = O.KinkMasks([torch.cat([a, b], 0) for a, b in zip(m0, m1)], [torch.cat([a, b], 0) for a, b in zip(s0, s1)])
-    O.KINK_MASKS = km
-    try:
+    with pinned(km, "gen_update on the joint batch"):
         g_ref = orc.gen_update(*joint)
-        assert km.done()
-    finally:
-        O.KINK_MASKS = None
-    assert km.worst_rel <= KINK_NOISE and km.n_disagree <= KINK_FRAC * km.n_total, (km.worst_rel, km.n_disagree, km.n_total)
     tr.gen_opt.flat_g.copy_(r0["gen_g"].to(DEV))
     gc, n_checked = GradCheck(pinned=True), 0
     for (n, p), g in zip(gnames, g_ref):
@@ -464,7 +449,6 @@ def _out_hp(batch):
 
 
 def _out_worker(rank, world, tmpdir, no_overlap):
-    from munit_amd import ops
     from oracle import munit_oracle as O
     T, dist = _init(rank, world, tmpdir, "out", no_overlap)
     dev = torch.device(DEV)
@@ -474,14 +458,9 @@ def _out_worker(rank, world, tmpdir, no_overlap):
     x_a, x_b, m_a, m_b = [t[rank:rank + 1].to(dev) for t in O.synthetic_batch(2, 64, seed=7)]
     x_as, x_bs = [t[rank:rank + 1].to(dev) for t in O.synthetic_batch(2, 64, seed=8)[:2]]
     out = {"sd_a": _cpu_state(tr.output_classifier_sr_a), "sd_b": _cpu_state(tr.output_classifier_sr_b)}
-    ops.MASK_SINK, ops.L1_SINK = [], []
-    try:
-        tr.output_domain_classifier_sr_update(x_a, x_as, x_b, x_bs, hp, 0)
-        torch.cuda.synchronize()
-        out["masks"] = [m.cpu() for m in ops.MASK_SINK]
-        assert not ops.L1_SINK
-    finally:
-        ops.MASK_SINK = ops.L1_SINK = None
+    km = record(lambda: tr.output_domain_classifier_sr_update(x_a, x_as, x_b, x_bs, hp, 0))[1]
+    out["masks"] = km.masks
+    assert not km.l1_signs
     out["loss"] = float(tr.loss_output_classifier_sr_update)
     out["grads"] = [p._munit_grad.detach().cpu().clone(memory_format=torch.contiguous_format)
                     for p in tr.output_classif_opt_sr._plist]
@@ -489,13 +468,8 @@ def _out_worker(rank, world, tmpdir, no_overlap):
     out["sd_a_end"], out["sd_b_end"] = _cpu_state(tr.output_classifier_sr_a), _cpu_state(tr.output_classifier_sr_b)
     torch.manual_seed(11)
     tr.dis_update(x_a, x_b, hp)
-    ops.MASK_SINK, ops.L1_SINK = [], []
-    try:
-        tr.gen_update(x_a, x_b, hp, m_a, m_b)
-        torch.cuda.synchronize()
-        out["kinks"] = ([m.cpu() for m in ops.MASK_SINK], [m.cpu() for m in ops.L1_SINK])
-    finally:
-        ops.MASK_SINK = ops.L1_SINK = None
+    km = record(lambda: tr.gen_update(x_a, x_b, hp, m_a, m_b))[1]
+    out["kinks"] = (km.masks, km.l1_signs)
     assert float(tr.loss_output_classifier_sr.detach()) > 0
     out["fool_loss"] = float(tr.loss_output_classifier_sr.detach())
     out["gen_g"] = tr.gen_opt.flat_g.detach().cpu().clone()
@@ -515,7 +489,7 @@ def test_two_rank_output_level_update_matches_the_oracle_on_the_joined_batch(tmp
     averaged generator gradient of gen_update against the fp64 step oracle with the output term on the joined batch."""
     from oracle import munit_oracle as O
     from tests import outda_oracle as U
-    from tests.parity import KINK_NOISE, GradCheck
+    from tests.parity import GradCheck
     _spawn(_out_worker, tmp_path, monkeypatch, 0)
     r0, r1 = [torch.load(tmp_path / ("out_rank%d.pt" % k), weights_only=True) for k in range(2)]
     for key in ("cls_p", "gen_p", "gen_g", "dis_p", "cls_p_end"):
@@ -531,12 +505,8 @@ def test_two_rank_output_level_update_matches_the_oracle_on_the_joined_batch(tmp
     x_as, x_bs = [t.double() for t in O.synthetic_batch(2, 64, seed=8)[:2]]
     assert len(r0["masks"]) == len(r1["masks"]) > 0
     km = O.KinkMasks([torch.cat([u, v], 0) for u, v in zip(r0["masks"], r1["masks"])], [])
-    O.KINK_MASKS = km
-    try:
+    with pinned(km, "output classifier update on the joined batch"):
         loss, grads = U.classifier_update(sd_a, sd_b, opt, x_a, x_as, x_b, x_bs, hp)
-    finally:
-        O.KINK_MASKS = None
-    assert km.done() and km.worst_rel <= KINK_NOISE, km.worst_rel
     got = 0.5 * (r0["loss"] + r1["loss"])
     rel = abs(got - float(loss)) / abs(float(loss))
     names = ["a." + k for k in sd_a] + ["b." + k for k in sd_b]
@@ -602,20 +572,14 @@ def _final_worker(rank, world, tmpdir, name, ckpt, no_overlap):
             with torch.no_grad():
                 out["codes"] = (tr._content_enc(1)(ops.nhwc(args[0])).cpu().double(),
                                 tr._content_enc(2)(ops.nhwc(args[1])).cpu().double())
-            ops.DANN_SINK = []
-        if method == "output_domain_classifier_sr_update":
+        out_cls = method == "output_domain_classifier_sr_update"
+        if out_cls:
             out["sd_a"], out["sd_b"] = _cpu_state(tr.output_classifier_sr_a), _cpu_state(tr.output_classifier_sr_b)
-            ops.MASK_SINK, ops.L1_SINK = [], []
-        try:
-            run()
-            ops.join_side_streams()
-            torch.cuda.synchronize()
-            if real_cls:
-                out["sink"] = [t.cpu() for t in ops.DANN_SINK]
-            if method == "output_domain_classifier_sr_update":
-                out["masks"] = [m.cpu() for m in ops.MASK_SINK]
-        finally:
-            ops.DANN_SINK = ops.MASK_SINK = ops.L1_SINK = None
+        _, km, k = record(run, mask=out_cls or None, l1=out_cls or None, dann=real_cls or None)
+        if real_cls:
+            out["sink"] = [t.cpu() for t in k.dann]
+        if out_cls:
+            out["masks"] = km.masks
         for k, v in vars(tr).items():                            # every loss the trainer holds after this call
             if k.startswith("loss_") and torch.is_tensor(v):
                 out["losses"]["%d %s %s" % (len(out["calls"]), method, k)] = float(v.detach())
@@ -681,13 +645,9 @@ def test_two_rank_iteration_of_the_final_test_configurations(tmp_path, monkeypat
         sd_b = {k: v.double().clone() for k, v in r0["sd_b"].items()}
         real, synth = C.inputs(hp)
         km = O.KinkMasks([torch.cat([u, v], 0) for u, v in zip(r0["masks"], r1["masks"])], [])
-        O.KINK_MASKS = km
-        try:
+        with pinned(km, name):
             ref = float(U.classifier_update(sd_a, sd_b, U.ClassifierOptimizer(sd_a, sd_b, hp), real[0].double(),
                                             synth[0].double(), real[1].double(), synth[1].double(), hp)[0])
-        finally:
-            O.KINK_MASKS = None
-        assert km.done() and km.worst_rel <= 5e-5, km.worst_rel
     got = 0.5 * (r0["losses"][key] + r1["losses"][key])
     rel = abs(got - ref) / abs(ref)
     print("two-rank %s iteration %d: %s, %d losses finite, %s %.6f (mean over the ranks) oracle %.6f rel %.2e"

@@ -31,12 +31,11 @@ import pytest
 import torch
 
 from munit_amd import ops
-from oracle import munit_oracle as O
 from tests import featda_oracle as F
 from tests import final_configs as C
 from tests import outda_oracle as D
 from tests import semantic_oracle as S
-from tests.parity import KINK_FRAC, KINK_NOISE, l2err, load_into_trainer, nerr, oracle_states, trainer_named_params
+from tests.parity import KINK_NOISE, l2err, load_into_trainer, nerr, oracle_states, pinned, record, trainer_named_params
 from tests.test_gpu_featda import FWD_TOL, GRAD_TOL, LOSS_TOL
 
 sys.path.insert(0, os.path.join(C.ROOT, "examples"))
@@ -184,21 +183,12 @@ def test_iterations_against_the_composed_oracle(fx, seg_model, tmp_path, name):
         sync()
         for s in SINKS:
             assert getattr(ops, s) is None, s
-        ops.MASK_SINK, ops.L1_SINK, ops.SEG_SINK, ops.DANN_SINK = [], [], [], []
-        try:
-            torch.manual_seed(seed[0])
-            run()
-            ops.join_side_streams()
-            torch.cuda.synchronize()
-            km = O.KinkMasks([m.cpu() for m in ops.MASK_SINK], [m.cpu() for m in ops.L1_SINK])
-            seg_sink[0], shared["sink"] = ops.SEG_SINK, ops.DANN_SINK
-        finally:
-            ops.MASK_SINK = ops.L1_SINK = ops.SEG_SINK = ops.DANN_SINK = None
+        _, km, k = record(run, seed[0], seg=True, dann=True)
+        seg_sink[0], shared["sink"] = k.seg, k.dann
         torch.manual_seed(seed[0])
         sa, sb = styles(hp["batch_size"])
-        pins = None
-        O.KINK_MASKS = km
-        try:
+        # the classifier's own update pins through `pins`: its encoders run without a tape, their codes are values, not kinks
+        with pinned(None if method == "domain_classifier_sr_update" else km, what) as audit:
             if method == "dis_update":
                 assert not seg_sink[0] and not shared["sink"]
                 orc.dis_update(ox[0], ox[1], sa, sb)
@@ -234,7 +224,6 @@ def test_iterations_against_the_composed_oracle(fx, seg_model, tmp_path, name):
             elif method == "domain_classifier_sr_update":
                 assert not seg_sink[0] and args[2] == is_synth
                 pins = F.trainer_pins(shared["sink"])
-                O.KINK_MASKS = None              # the encoders run without a tape: their codes are values, not kinks to pin
                 (ga, ka), (gb, kb) = orc._views()
                 with torch.no_grad():
                     c_a, c_b = ga.encode(ox[0], ka)[0], gb.encode(ox[1], kb)[0]
@@ -248,14 +237,7 @@ def test_iterations_against_the_composed_oracle(fx, seg_model, tmp_path, name):
                 assert args[1] is dsynth[0] and args[3] is dsynth[1]
                 orc.output_domain_classifier_sr_update(oreal[0], osynth[0], oreal[1], osynth[1])
                 names = ("loss_output_classifier_sr_update",)
-        finally:
-            O.KINK_MASKS = None
-        if pins is None:
-            assert km.done(), (what, "the oracle ran fewer activations or L1 terms than the HIP call recorded")
-            assert km.worst_rel <= KINK_NOISE, (what, km.worst_rel, km.worst_at)
-            assert km.n_disagree <= KINK_FRAC * km.n_total, (what, km.n_disagree, km.n_total)
-            worst["kink"] = max(worst["kink"], km.worst_rel)
-            worst["kink_frac"] = max(worst["kink_frac"], km.n_disagree / max(1, km.n_total))
+        worst["kink"], worst["kink_frac"] = max(worst["kink"], audit.worst_rel), max(worst["kink_frac"], audit.disagree_frac)
         compare(what, names)
         if method == "domain_classifier_sr_update":
             moments(what, tr.classif_opt_sr, fopt.m, fopt.v)

@@ -16,7 +16,7 @@ from tests import gan_loss_contract as G
 from tests import nsgan_oracle as N
 from tests import outda_oracle as D
 from tests.conv_contract import Calls, no_nan
-from tests.parity import KINK_NOISE, nerr, run_step_parity
+from tests.parity import nerr, pinned, record, run_step_parity
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -226,30 +226,6 @@ def _module(hp, tag):
     return net.to(DEV), sd
 
 
-def _record(fn):
-    """run fn with the kinks recorded; returns (result, KinkMasks)"""
-    ops.MASK_SINK, ops.L1_SINK = [], []
-    try:
-        out = fn()
-        ops.join_side_streams()
-        torch.cuda.synchronize()
-        masks, signs = ops.MASK_SINK, ops.L1_SINK
-    finally:
-        ops.MASK_SINK = ops.L1_SINK = None
-    return out, O.KinkMasks([m.cpu() for m in masks], [s.cpu() for s in signs])
-
-
-def _pinned(fn, km):
-    O.KINK_MASKS = km
-    try:
-        out = fn()
-    finally:
-        O.KINK_MASKS = None
-    assert km.done(), "the oracle ran fewer activations than the HIP pass recorded"
-    assert km.worst_rel <= KINK_NOISE, (km.worst_rel, km.worst_at)
-    return out
-
-
 @pytest.fixture(scope="module")
 def dis():
     ops.set_compute("f32")
@@ -279,10 +255,11 @@ def test_losses_against_the_oracle(dis, which):
     hp, net, sd, fake, real = dis
     nin = LOSSES[which][2]
     with Calls(NSGAN + OTHERS) as calls:
-        (loss, grads), km = _record(lambda: _hip_loss(net, which, fake, real))
+        (loss, grads), km, _ = record(lambda: _hip_loss(net, which, fake, real))
     assert calls == ["munit_nsgan_fwd", "munit_nsgan_bwd"]
     rs = [fake.clone().requires_grad_(True), real.clone().requires_grad_(True)]
-    l_ref = _pinned(lambda: LOSSES[which][1](sd, rs[0], rs[1], hp["dis"]), km)
+    with pinned(km, which):
+        l_ref = LOSSES[which][1](sd, rs[0], rs[1], hp["dis"])
     g_ref = torch.autograd.grad(l_ref, rs[:nin] + list(sd.values()))
     rel = abs(float(loss.detach()) - float(l_ref.detach())) / abs(float(l_ref.detach()))
     errs = [nerr(g, r) for g, r in zip(grads, g_ref)]

@@ -801,3 +801,21 @@ def test_optimizer_entry_point_contract(n):
 def test_image_entry_point_contract(B, h, w):
     from tests import kernel_contract as K
     K.check_image(B, h, w)
+
+
+def test_kinks_records_one_relu_mask_and_two_l1_signs():
+    """ops.kinks around a conv with a ReLU and an L1 term: the mask is the sign of the output, the L1 term records, a nested
+    kinks(mask=None) switches only that channel off, and every sink is None afterwards."""
+    from munit_amd import ops
+    cl = lambda t: t.float().to(dev()).contiguous(memory_format=torch.channels_last)
+    x, w = cl(rnd((1, 4, 8, 8), 1)), cl(rnd((4, 4, 3, 3), 2, 0.2))
+    a, b = cl(rnd((1, 4, 8, 8), 3)), cl(rnd((1, 4, 8, 8), 4))
+    with ops.kinks(mask=True, l1=True) as k:
+        y = ops.conv2d(x, w, None, 1, 1, "reflect", False, "relu")
+        ops.l1_mean(a, b)
+        with ops.kinks(mask=None):
+            ops.conv2d(x, w, None, 1, 1, "reflect", False, "relu")
+            ops.l1_mean(a, b)
+    assert len(k.mask) == 1 and torch.equal(k.mask[0], y > 0) and 0 < int(k.mask[0].sum()) < y.numel()
+    assert len(k.l1) == 2 and torch.equal(k.l1[0], a > b) and torch.equal(k.l1[1], a > b)
+    assert (ops.MASK_SINK, ops.L1_SINK, ops.SEG_SINK, ops.DANN_SINK) == (None, None, None, None)

@@ -16,7 +16,7 @@ from oracle import munit_oracle as O
 from tests import gan_loss_contract as G
 from tests import outda_oracle as D
 from tests.conv_contract import Calls, no_nan
-from tests.parity import KINK_NOISE, l2err, load_into_trainer, nerr, oracle_states, trainer_named_params
+from tests.parity import l2err, load_into_trainer, nerr, oracle_states, pinned, record, trainer_named_params
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -154,30 +154,6 @@ def _module(hp, tag):
     return net.to(DEV), sd
 
 
-def _record(fn):
-    """run fn with the kinks recorded; returns (result, KinkMasks)"""
-    ops.MASK_SINK, ops.L1_SINK = [], []
-    try:
-        out = fn()
-        ops.join_side_streams()
-        torch.cuda.synchronize()
-        masks, signs = ops.MASK_SINK, ops.L1_SINK
-    finally:
-        ops.MASK_SINK = ops.L1_SINK = None
-    return out, O.KinkMasks([m.cpu() for m in masks], [s.cpu() for s in signs])
-
-
-def _pinned(fn, km):
-    O.KINK_MASKS = km
-    try:
-        out = fn()
-    finally:
-        O.KINK_MASKS = None
-    assert km.done(), "the oracle ran fewer activations than the HIP pass recorded"
-    assert km.worst_rel <= KINK_NOISE, (km.worst_rel, km.worst_at)
-    return out
-
-
 @pytest.mark.parametrize("batches", [(1, 1), (2, 2), (3, 3), (2, 1)])
 def test_losses_against_the_oracle(batches):
     """(sim batch, real batch): equal batches take the one-forward path (batch 1: the n = 1 segment and the odd start of
@@ -197,10 +173,11 @@ def test_losses_against_the_oracle(batches):
         return loss, torch.autograd.grad(loss, xs + ps)
 
     with Calls(("munit_lsgan_fwd", "munit_lsgan_bwd", "munit_mse_const")) as calls:
-        (loss, grads), km = _record(hip_dis)
+        (loss, grads), km, _ = record(hip_dis)
     assert calls == ["munit_lsgan_fwd", "munit_lsgan_bwd"]
     rs = [sim.clone().requires_grad_(True), real.clone().requires_grad_(True)]
-    l_ref = _pinned(lambda: D.dis_loss_sr(sd, rs[0], rs[1], hp["dis"]), km)
+    with pinned(km, "calc_dis_loss_sr"):
+        l_ref = D.dis_loss_sr(sd, rs[0], rs[1], hp["dis"])
     g_ref = torch.autograd.grad(l_ref, rs + list(sd.values()))
     rel = abs(float(loss.detach()) - float(l_ref.detach())) / abs(float(l_ref.detach()))
     errs = [nerr(g, r) for g, r in zip(grads, g_ref)]
@@ -213,9 +190,10 @@ def test_losses_against_the_oracle(batches):
         loss = net.calc_gen_loss_sr(x)
         return loss, torch.autograd.grad(loss, [x] + ps)
 
-    (loss, grads), km = _record(hip_gen)
+    (loss, grads), km, _ = record(hip_gen)
     r = sim.clone().requires_grad_(True)
-    l_ref = _pinned(lambda: D.gen_loss_sr(sd, r, hp["dis"]), km)
+    with pinned(km, "calc_gen_loss_sr"):
+        l_ref = D.gen_loss_sr(sd, r, hp["dis"])
     g_ref = torch.autograd.grad(l_ref, [r] + list(sd.values()))
     rel = abs(float(loss.detach()) - float(l_ref.detach())) / abs(float(l_ref.detach()))
     errs = [nerr(g, q) for g, q in zip(grads, g_ref)]
@@ -305,10 +283,10 @@ def _sequence(hp, synth=False):
                 assert float((a - r).abs().max()) <= 4.0 * lr and l2err(a, r) <= 2e-4, (what, grp, n, worst)
 
     def run(what, seed, hip, oracle):
-        torch.manual_seed(seed)
-        _, km = _record(hip)
-        out = _pinned(oracle, km)
-        worst["kink"] = max(worst["kink"], km.worst_rel)
+        km = record(hip, seed)[1]
+        with pinned(km, what) as audit:
+            out = oracle()
+        worst["kink"] = max(worst["kink"], audit.worst_rel)
         return out
 
     sd_on = hp["adaptation"]["output_adv_lambda"]

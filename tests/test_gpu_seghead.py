@@ -283,11 +283,9 @@ def _module(fc_seed=5):
 
 def _run_module(net, c, t, sc):
     ops.set_compute("f32")
-    ops.DANN_SINK = sink = []
-    try:
+    with ops.kinks(dann=True) as k:
         out = net(cl(c))
-    finally:
-        ops.DANN_SINK = None
+    sink = k.dann
     loss = ops.seg_cross_entropy_direct(out, t.reshape(t.shape[0], t.shape[2], t.shape[3]).float().to(DEV).contiguous(), sc)
     ps = list(net.parameters())
     grads = torch.autograd.grad(loss, ps)
@@ -387,12 +385,10 @@ def test_update_against_the_oracle(ckpt, gen_state):
                 for k, v in H.state_of(tr.segmentation_head).items():
                     sd[k].copy_(v)
         tr.iterations = call
-        ops.DANN_SINK = sink = []
-        try:
+        with ops.kinks(dann=True) as k:
             tr.segmentation_head_update(x_a, x_b, t_a.to(DEV), t_b.to(DEV), lamb)
-        finally:
-            ops.DANN_SINK = None
         torch.cuda.synchronize()
+        sink = k.dann
         assert len(sink) == 2 * H.PINS_PER_FORWARD
         pins = H.head_pins(sink)
         l_ref, g_ref = H.head_update(sd, opt, c_a, c_b, t_a, t_b, lamb, 64, pins)

@@ -54,12 +54,9 @@ def test_maxpool_first_max_rule(b, c, h, w):
     dy = torch.randn(yr.shape, generator=g, dtype=torch.float64)
     yr.backward(dy)
     xd = cl(x).requires_grad_(True)
-    ops.SEG_SINK = []
-    try:
+    with ops.kinks(seg=True) as k:
         y = ops.maxpool3s2(xd)
-        win = ops.SEG_SINK[0].cpu().long()            # (b, ho, wo, c): window position kh*3 + kw
-    finally:
-        ops.SEG_SINK = None
+    win = k.seg[0].cpu().long()                       # (b, ho, wo, c): window position kh*3 + kw
     assert torch.equal(y.cpu().double(), yr.detach())
     # the rule, restated: first maximal element of the window in kh-major order (torch's CPU kernel agrees)
     ho, wo = y.shape[2:]
@@ -153,13 +150,10 @@ def test_seg_conv_fwd_dgrad(case):
     xd = cl(x).requires_grad_(True)
     link = ops.ResidualLink()
     link.park(cl(add))
-    ops.SEG_SINK = []
-    try:
+    with ops.kinks(seg=True) as k:
         yd = ops.frozen_conv(xd, cl(wt), bias.float().to(DEV), cl(_even(wt)) if stride == 2 else cl(wt), stride, pad, act,
                              link_in=link)
-        sink = list(ops.SEG_SINK)
-    finally:
-        ops.SEG_SINK = None
+    sink = k.seg
     assert len(sink) == (1 if act == "relu" else 0)
 
     def ref(dtype):
@@ -268,12 +262,9 @@ def test_network_logits_and_input_grad(model, sd, monkeypatch, b, size):
     monkeypatch.setattr(ops, "conv2d_wgrad_raw", rec_wgrad)
     x = S.rand_images(b, size, size)
     xd = cl(x).requires_grad_(True)
-    ops.SEG_SINK = []
-    try:
+    with ops.kinks(seg=True) as k:
         z = model(xd)
-        pins = S.seg_pins(ops.SEG_SINK)
-    finally:
-        ops.SEG_SINK = None
+    pins = S.seg_pins(k.seg)
     # the oracle takes the device's branch at every ReLU and max-pool kink; the audit allows a disagreement with the
     # oracle's own choice only at rounding-noise margins
     xr = x.clone().requires_grad_(True)
@@ -362,12 +353,9 @@ def _maxpool_check(x, seed):
     dy = torch.randn(yr.shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
     yr.backward(dy)
     xd = cl(x).requires_grad_(True)
-    ops.SEG_SINK = []
-    try:
+    with ops.kinks(seg=True) as k:
         y = ops.maxpool3s2(xd)
-        win = ops.SEG_SINK[0].cpu().long()
-    finally:
-        ops.SEG_SINK = None
+    win = k.seg[0].cpu().long()
     assert tuple(y.shape) == tuple(yr.shape)
     assert torch.equal(y.cpu().double(), yr.detach()), (b, c, h, w)
     ho, wo = y.shape[2:]
@@ -421,12 +409,9 @@ def test_add_relu_zero_sums_and_grid_wrap():
     rf[1::7] = -0.0                         # negative zero
     rf[-3:] = 1.0 - af[-3:]                 # the last vector of four: live values
     ad, rd = cl(a).requires_grad_(True), cl(r).requires_grad_(True)
-    ops.SEG_SINK = []
-    try:
+    with ops.kinks(seg=True) as k:
         y = ops.add_relu(ad, rd)
-        mask = ops.SEG_SINK[0]
-    finally:
-        ops.SEG_SINK = None
+    mask = k.seg[0]
     want = (a.float().double() + r.float().double()).clamp_min(0).float()
     assert torch.equal(y.cpu(), want)
     assert torch.equal(mask, y > 0) and torch.equal(mask.cpu(), want > 0)
@@ -549,13 +534,10 @@ def _semantic_parity(tmp_path, monkeypatch, size, batch, full, gen_state=1, **kw
     sink = []
     cls = S.oracle_trainer_class(seg, lambda: sink)
     monkeypatch.setattr(O, "OracleTrainer", cls)
-    ops.SEG_SINK = sink
-    try:
+    with ops.kinks(seg=sink):
         rep = run_step_parity(size=size, batch=batch, gen_state=gen_state, iters=1, device=DEV,
                               hp_overrides={"semantic_w": 3, "semantic_ckpt_path": _ckpt(tmp_path, seg),
                                             "adaptation": {"full_adaptation": full}}, **kw)
-    finally:
-        ops.SEG_SINK = None
     assert cls.audit_bad == 0
     assert "loss_sem_seg" in rep and rep["loss_sem_seg"] > 0
     return rep
@@ -717,7 +699,6 @@ def test_semantic_off_launches_no_seg_kernel(tmp_path, model):
     tr = _trainer(hp, 0)
     assert tr.segmentation_model is None
     xa, xb, ma, mb = _inputs(2, 64, 3)
-    ops.SEG_SINK = []
     calls = []
     from munit_amd import _lib
     lib = _lib.load()
@@ -728,12 +709,12 @@ def test_semantic_off_launches_no_seg_kernel(tmp_path, model):
         for n in names:
             f = saved[n]
             setattr(lib, n, (lambda f, n: lambda *a: calls.append(n) or f(*a))(f, n))
-        _step(tr, hp, xa, xb, ma, mb)
-        assert ops.SEG_SINK == [] and calls == []
+        with ops.kinks(seg=True) as k:
+            _step(tr, hp, xa, xb, ma, mb)
+        assert k.seg == [] and calls == []
     finally:
         for n, f in saved.items():
             setattr(lib, n, f)
-        ops.SEG_SINK = None
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ import pytest
 import torch
 
 from oracle import munit_oracle as O
-from tests.parity import KINK_FRAC, KINK_NOISE, nerr, run_step_parity
+from tests.parity import KINK_FRAC, KINK_NOISE, nerr, pinned, run_step_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -90,9 +90,8 @@ def test_conv_at_baseline_shape(case):
     # sample by sample: torch's fp64 CPU convolution unfolds the input (Cin*k*k*Ho*Wo doubles per sample: 6.7 GB for the
     # config-#4 up-sampling layer); the parameter gradients accumulate over the loop exactly as over a batch
     ys, dy = [], None
-    O.KINK_MASKS = kinks
-    try:
-        nref = B // 2 if twin else B
+    nref = B // 2 if twin else B
+    with pinned(kinks, case[0]):
         for i in range(nref):
             xi = xr[i:i + 1]
             yi = O.conv_block(O.upsample2(xi) if ups else xi, wr, br, stride, pad, "reflect", None, act)
@@ -102,8 +101,6 @@ def test_conv_at_baseline_shape(case):
                     dy = torch.cat([dy, dy])
             yi.backward(dy[i:i + 1])
             ys.append(yi.detach())
-    finally:
-        O.KINK_MASKS = None
     yr = torch.cat(ys + ys) if twin else torch.cat(ys)
     if twin:      # the reference saw each distinct sample once: its parameter gradients count half of what the device sums
         with torch.no_grad():
@@ -111,10 +108,6 @@ def test_conv_at_baseline_shape(case):
             br.grad *= 2
             xr.grad[B // 2:] = xr.grad[:B // 2]
         assert torch.equal(y[B // 2:], y[:B // 2]), "twin samples differ in the forward"
-    if kinks is not None:
-        assert kinks.done() and kinks.worst_rel <= KINK_NOISE, (kinks.worst_rel, kinks.worst_at)
-        assert kinks.n_disagree <= KINK_FRAC * kinks.n_total, (kinks.n_disagree, kinks.n_total)
-
     assert tuple(y.shape) == tuple(yr.shape)
     e = nerr(y, yr)
     assert e <= FWD_TOL, ("fwd", e)

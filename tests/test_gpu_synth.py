@@ -84,12 +84,9 @@ def test_pair_loss_and_gradients(shape, kind):
 
 def test_pair_loss_records_its_two_sign_patterns_in_order():
     x_a, x_b, x_ab, x_ba = (cl(t) for t in _pair_case((2, 5, 7, 3), "box"))
-    ops.L1_SINK = []
-    try:
+    with ops.kinks(l1=True) as k:
         ops.pair_l1(x_a, x_b, x_ab, x_ba)
-        rec = list(ops.L1_SINK)
-    finally:
-        ops.L1_SINK = None
+    rec = k.l1
     assert len(rec) == 2 and torch.equal(rec[0], x_ab > x_b) and torch.equal(rec[1], x_ba > x_a)
 
 
@@ -255,12 +252,8 @@ def _synth_parity(tmp_path, monkeypatch, full=0, gen_state=1, semantic_w=3):
     over = {"recon_synth_w": 1, "adaptation": {"full_adaptation": full}}
     if semantic_w:
         over.update(semantic_w=semantic_w, semantic_ckpt_path=_ckpt(tmp_path, seg))
-    ops.SEG_SINK = sink
-    try:
-        with Calls(SEG_NAMES + NEW_NAMES) as calls:
-            rep = run_step_parity(size=SIZE, batch=BATCH, gen_state=gen_state, iters=1, device=DEV, hp_overrides=over)
-    finally:
-        ops.SEG_SINK = None
+    with ops.kinks(seg=sink), Calls(SEG_NAMES + NEW_NAMES) as calls:
+        rep = run_step_parity(size=SIZE, batch=BATCH, gen_state=gen_state, iters=1, device=DEV, hp_overrides=over)
     print("synthetic step full=%d gen_state=%d semantic_w=%d: pair %.6f sem %.6f grad %.2e max %.2e L2"
           % (full, gen_state, semantic_w, rep["loss_gen_recon_synth"], rep.get("loss_sem_seg", 0.0), rep["grad_nerr"],
              rep["grad_l2"]))

@@ -18,8 +18,7 @@ batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 full = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 seg, sink = S.make_model(0), []
 O.OracleTrainer = S.oracle_trainer_class(seg, lambda: sink)
-ops.SEG_SINK = sink
-with tempfile.TemporaryDirectory() as d:
+with tempfile.TemporaryDirectory() as d, ops.kinks(seg=sink):
     ck = os.path.join(d, "seg.pth")
     torch.save(seg.state_dict(), ck)
     rep = run_step_parity(size=size, batch=batch, gen_state=1, iters=1, device="cuda:0", check=False, ref32=True,
