@@ -126,29 +126,53 @@ LABEL_TABLE = tuple(LABEL_CLASSES.get(v, v) for v in range(256))
 KIND_MASK, KIND_LABEL = 0, 1         # munit_image_desc.kind as munit_label_preprocess reads it
 
 
+def _pack(groups, draws):
+    """Lay out one batch for the device: [descriptors, group after group][pad to 256][payloads in the same order] (every
+    payload 16-byte aligned).  groups: ordered (arrays, kind, resized) triples, every group with one array per sample or
+    none at all (its descriptors stay zero); draws[b] = (flip, rs_h, rs_w, crop_i, crop_j, out_h, out_w) is shared by
+    sample b's descriptors of every group; `resized` says whether a group's descriptors carry the draw's (rs_h, rs_w) or
+    zeros.  Returns (descs, offsets in descriptor order, total)."""
+    B = len(groups[0][0])
+    descs = (ImageDesc * (len(groups) * B))()
+    cur = (ctypes.sizeof(descs) + 255) // 256 * 256
+    offs = []
+    for g, (items, kind, resized) in enumerate(groups):
+        for b, (a, dr) in enumerate(zip(items, draws)):
+            flip, rs_h, rs_w, i, j, _, _ = dr
+            if not resized:
+                rs_h = rs_w = 0
+            descs[g * B + b] = ImageDesc(cur, a.shape[0], a.shape[1], rs_h, rs_w, i, j, flip, kind)
+            offs.append(cur)
+            cur += (a.nbytes + 15) // 16 * 16
+    return descs, offs, cur
+
+
+def _image_groups(arrays, masks):
+    return [(arrays, 0, True), (masks if masks is not None else (), KIND_MASK, False)]
+
+
+def _synth_groups(images_a, images_b, masks, sems_a, sems_b):
+    return [(images_a, 0, True), (images_b, 0, True), (masks, KIND_MASK, True), (sems_a, KIND_LABEL, True),
+            (sems_b, KIND_LABEL, True)]
+
+
 def pack_batch(arrays, masks, draws):
     """Lay out one batch for the device.  Layout of the staging buffer:
-    [B image descs][B mask descs][pad to 256][image bytes ...][mask bytes ...] (every item 16-byte aligned).
+    [B image descs][B mask descs][pad to 256][image bytes ...][mask bytes ...] (every item 16-byte aligned); the mask
+    descriptors are reserved (zero) also without masks, and munit_mask_preprocess reads no (rs_h, rs_w) from them.
     draws[b] = (flip, rs_h, rs_w, crop_i, crop_j, out_h, out_w).  Returns (descs, offsets, mask offsets, total)."""
-    B = len(arrays)
-    dsz = ctypes.sizeof(ImageDesc)
-    cur = (2 * B * dsz + 255) // 256 * 256
-    offs, moffs = [], []
-    for a in arrays:
-        offs.append(cur)
-        cur += (a.nbytes + 15) // 16 * 16
-    if masks is not None:
-        for m in masks:
-            moffs.append(cur)
-            cur += (m.nbytes + 15) // 16 * 16
-    descs = (ImageDesc * (2 * B))()
-    for b, (a, dr) in enumerate(zip(arrays, draws)):
-        flip, rs_h, rs_w, i, j, _, _ = dr
-        descs[b] = ImageDesc(offs[b], a.shape[0], a.shape[1], rs_h, rs_w, i, j, flip, 0)
-        if masks is not None:
-            m = masks[b]
-            descs[B + b] = ImageDesc(moffs[b], m.shape[0], m.shape[1], 0, 0, i, j, flip, 0)
-    return descs, offs, moffs, cur
+    descs, offs, total = _pack(_image_groups(arrays, masks), draws)
+    return descs, offs[:len(arrays)], offs[len(arrays):], total
+
+
+def pack_synth_batch(images_a, images_b, masks, sems_a, sems_b, draws):
+    """Lay out one batch of synthetic pairs for the device.  Layout of the staging buffer:
+    [2B image descs: a..., b...][3B plane descs: masks..., semantic_a..., semantic_b...][pad to 256]
+    [a images][b images][masks][semantic_a maps][semantic_b maps] (every item 16-byte aligned).
+    draws[b] = (flip, rs_h, rs_w, crop_i, crop_j, out_h, out_w): ONE draw per sample, shared by its five descriptors;
+    the planes carry the resized IMAGE's (rs_h, rs_w), which munit_label_preprocess resizes them to.
+    Returns (descs, offsets in descriptor order, total)."""
+    return _pack(_synth_groups(images_a, images_b, masks, sems_a, sems_b), draws)
 
 
 class _StagingRing:
@@ -173,42 +197,55 @@ class _StagingRing:
         self.events[k] = event
 
 
-def launch_transform(arrays, masks, draws, device, stream, ring=None, pool=None):
-    """Stage decoded uint8 images (H,W,3) [and masks (H,W)] in pinned memory, upload them with one async copy
-    and run the device transform on `stream`.  Returns (outputs, ready event, buffers to keep alive until the
-    event): outputs = images (B,3,h,w) channels_last, or (images, masks (B,1,h,w)).  ring: _StagingRing to take the
-    pinned buffer from (else a fresh one); pool: unused (the copies run in the calling thread, see below)."""
-    lib = _lib.load()
-    B = len(arrays)
+def _lay_out(groups, n_img, draws, unequal):
+    """Host half of _launch, no device needed: check the images (the first n_img groups; sample b's image of every group
+    goes with draws[b]) and pack the batch.  `unequal`: the caller's message for crop sizes that differ inside the batch.
+    Returns (descs, offsets, total, out_h, out_w)."""
     th, tw = draws[0][5], draws[0][6]
-    if any((d[5], d[6]) != (th, tw) for d in draws):
-        raise ValueError("crop=False needs equally sized images inside a batch")
-    for a, d in zip(arrays, draws):
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError("images must be uint8 (H, W, 3) arrays")
+    for b, d in enumerate(draws):
+        imgs = [items[b] for items, _, _ in groups[:n_img]]
+        for x in imgs:
+            if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
+                raise ValueError("images must be uint8 (H, W, 3) arrays")
+        for x in imgs[1:]:                        # one draw, and so one resized size, serves all images of a sample
+            if x.shape != imgs[0].shape:
+                raise ValueError("the images of a synthetic pair differ in size: %s vs %s" % (imgs[0].shape[:2], x.shape[:2]))
+        if (d[5], d[6]) != (th, tw):
+            raise ValueError(unequal)
         if d[3] < 0 or d[4] < 0 or d[3] + th > d[1] or d[4] + tw > d[2]:
             raise ValueError("crop window (%d,%d,%d,%d) outside the resized image (%d,%d)" % (d[3], d[4], th, tw, d[1], d[2]))
-    descs, offs, moffs, total = pack_batch(arrays, masks, draws)
+    return _pack(groups, draws) + (th, tw)
+
+
+def _fill(buf, descs, offs, groups):
+    """Host half of _launch, second part: the descriptors and every payload into the uint8 array `buf`, nothing beyond the
+    batch's `total`."""
+    ctypes.memmove(buf.ctypes.data, ctypes.addressof(descs), ctypes.sizeof(descs))
+    for a, o in zip([a for items, _, _ in groups for a in items], offs):
+        buf[o:o + a.nbytes] = a.reshape(-1)     # a large contiguous copy: numpy drops the GIL for it
+
+
+def _launch(groups, n_img, draws, unequal, plane_pass, device, stream, ring):
+    """Stage one packed batch (_pack's groups: n_img groups of images, then the single-band planes) in pinned memory, upload
+    it with one async copy and run the device transform on `stream`: munit_image_preprocess once over all images, then
+    `plane_pass` ("munit_mask_preprocess" / "munit_label_preprocess", with its *_workspace_bytes) once over all planes.
+    ring: _StagingRing to take the pinned buffer from (else a fresh one).  Returns (images (n,3,h,w) channels_last, planes
+    (m,1,h,w) or None, ready event, buffers to keep alive until the event)."""
+    descs, offs, total, th, tw = _lay_out(groups, n_img, draws, unequal)
+    lib = _lib.load()
     slot = None
     if ring is not None:
         slot, stage = ring.take(total)
     else:
         stage = torch.empty(total, dtype=torch.uint8).pin_memory()
-    sv = stage.numpy()
-    ctypes.memmove(sv.ctypes.data, ctypes.addressof(descs), ctypes.sizeof(descs))
-
-    def put(a, o):
-        sv[o:o + a.nbytes] = a.reshape(-1)     # a large contiguous copy: numpy drops the GIL for it
-
     # The copies run HERE, in the producer thread: the decode pool's queue already holds the files of the next `ahead`
     # batches, and copies submitted behind them made every upload wait for all of that decode work (a latency bubble per
-    # batch).  2 B contiguous memcpys of a few MB each, with the GIL released, cost less than that wait.  (`pool` is kept in
-    # the signature for callers that pass it.)
-    jobs = list(zip(arrays, offs)) + (list(zip(masks, moffs)) if masks is not None else [])
-    for a, o in jobs:
-        put(a, o)
+    # batch).  A few contiguous memcpys of a few MB each, with the GIL released, cost less than that wait.
+    _fill(stage.numpy(), descs, offs, groups)
+    n_images = n_img * len(draws)
+    n_planes = len(offs) - n_images
     ksize = 3
-    for a, d in zip(arrays, draws):
+    for a, d in zip(groups[0][0], draws):       # a sample's images are equally sized (_lay_out): its first one decides
         ksize = max(ksize, lib.munit_image_ksize(a.shape[0], d[1]), lib.munit_image_ksize(a.shape[1], d[2]))
     vp = ctypes.c_void_p
     with torch.cuda.stream(stream):
@@ -220,61 +257,53 @@ def launch_transform(arrays, masks, draws, device, stream, ring=None, pool=None)
             ring.mark(slot, copied)
         st = vp(stream.cuda_stream)
         base = dev.data_ptr()
-        images = torch.empty((B, 3, th, tw), device=device, dtype=torch.float32, memory_format=torch.channels_last)
-        nws = lib.munit_image_preprocess_workspace_bytes(B, th, tw, ksize)
-        ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=device)
-        rc = lib.munit_image_preprocess(vp(base), vp(base), B, th, tw, ksize, vp(images.data_ptr()),
-                                        vp(ws.data_ptr()), ctypes.c_size_t(nws), st)
-        if rc:
-            raise RuntimeError("munit_image_preprocess: " + lib.munit_last_error().decode())
-        keep = (dev, ws) if slot is not None else (stage, dev, ws)    # a ring slot outlives the batch by itself
-        out = images
-        if masks is not None:
-            out_masks = torch.empty((B, 1, th, tw), device=device, dtype=torch.float32)
-            nwm = lib.munit_mask_preprocess_workspace_bytes(B, th, tw)
-            wsm = torch.empty(max(nwm, 1), dtype=torch.uint8, device=device)
-            rc = lib.munit_mask_preprocess(vp(base), vp(base + B * ctypes.sizeof(ImageDesc)), B, th, tw,
-                                           vp(out_masks.data_ptr()), vp(wsm.data_ptr()), ctypes.c_size_t(nwm), st)
+        keep = (dev,) if slot is not None else (stage, dev)    # a ring slot outlives the batch by itself
+
+        def run(name, first_desc, out, *extra):
+            n = out.shape[0]
+            nws = getattr(lib, name + "_workspace_bytes")(n, th, tw, *extra)
+            ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=device)
+            rc = getattr(lib, name)(vp(base), vp(base + first_desc * ctypes.sizeof(ImageDesc)), n, th, tw, *extra,
+                                    vp(out.data_ptr()), vp(ws.data_ptr()), ctypes.c_size_t(nws), st)
             if rc:
-                raise RuntimeError("munit_mask_preprocess: " + lib.munit_last_error().decode())
-            keep = keep + (wsm,)
-            out = (images, out_masks)
+                raise RuntimeError(name + ": " + lib.munit_last_error().decode())
+            return (ws,)
+
+        images = torch.empty((n_images, 3, th, tw), device=device, dtype=torch.float32, memory_format=torch.channels_last)
+        keep += run("munit_image_preprocess", 0, images, ksize)
+        planes = None
+        if n_planes:
+            planes = torch.empty((n_planes, 1, th, tw), device=device, dtype=torch.float32)
+            keep += run(plane_pass, n_images, planes)
         ev = torch.cuda.Event()
         ev.record(stream)
-    return out, ev, keep
+    return images, planes, ev, keep
+
+
+def launch_transform(arrays, masks, draws, device, stream, ring=None):
+    """Stage decoded uint8 images (H,W,3) [and masks (H,W)] in pinned memory, upload them with one async copy
+    and run the device transform on `stream` (_launch).  Returns (outputs, ready event, buffers to keep alive until the
+    event): outputs = images (B,3,h,w) channels_last, or (images, masks (B,1,h,w)).  ring: _StagingRing to take the
+    pinned buffer from (else a fresh one)."""
+    images, out_masks, ev, keep = _launch(_image_groups(arrays, masks), 1, draws,
+                                          "crop=False needs equally sized images inside a batch", "munit_mask_preprocess",
+                                          device, stream, ring)
+    return (images if masks is None else (images, out_masks)), ev, keep
+
+
+def _require_device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("munit_amd.data: the transforms run on the GPU (libmunit_hip.so); no HIP device is "
+                           "visible and there is no CPU fallback")
 
 
 def transform_batch(arrays, masks, draws, device=None):
     """Synchronous convenience wrapper of launch_transform on the current stream's device."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("munit_amd.data: the transforms run on the GPU (libmunit_hip.so); no HIP device is "
-                           "visible and there is no CPU fallback")
+    _require_device()
     device = device or torch.device("cuda", torch.cuda.current_device())
     out, ev, keep = launch_transform(arrays, masks, draws, device, torch.cuda.current_stream(device))
     ev.synchronize()
     return out
-
-
-def pack_synth_batch(images_a, images_b, masks, sems_a, sems_b, draws):
-    """Lay out one batch of synthetic pairs for the device.  Layout of the staging buffer:
-    [2B image descs: a..., b...][3B plane descs: masks..., semantic_a..., semantic_b...][pad to 256]
-    [a images][b images][masks][semantic_a maps][semantic_b maps] (every item 16-byte aligned).
-    draws[b] = (flip, rs_h, rs_w, crop_i, crop_j, out_h, out_w): ONE draw per sample, shared by its five descriptors;
-    the planes carry the resized IMAGE's (rs_h, rs_w), which munit_label_preprocess resizes them to.
-    Returns (descs, offsets in descriptor order, total)."""
-    B = len(images_a)
-    dsz = ctypes.sizeof(ImageDesc)
-    groups = [(images_a, 0), (images_b, 0), (masks, KIND_MASK), (sems_a, KIND_LABEL), (sems_b, KIND_LABEL)]
-    cur = (5 * B * dsz + 255) // 256 * 256
-    descs = (ImageDesc * (5 * B))()
-    offs = []
-    for g, (items, kind) in enumerate(groups):
-        for b, (a, dr) in enumerate(zip(items, draws)):
-            flip, rs_h, rs_w, i, j, _, _ = dr
-            descs[g * B + b] = ImageDesc(cur, a.shape[0], a.shape[1], rs_h, rs_w, i, j, flip, kind)
-            offs.append(cur)
-            cur += (a.nbytes + 15) // 16 * 16
-    return descs, offs, cur
 
 
 def launch_synth_transform(images_a, images_b, masks, sems_a, sems_b, draws, device, stream, ring=None):
@@ -283,65 +312,15 @@ def launch_synth_transform(images_a, images_b, masks, sems_a, sems_b, draws, dev
     the 2B images and munit_label_preprocess once over the 3B planes.  Returns ((x_as, x_bs, mask_s, sem_a, sem_b),
     ready event, buffers to keep alive): the images are the two halves of one (2B,3,h,w) channels_last batch, the other
     three the thirds of one (3B,1,h,w) batch."""
-    lib = _lib.load()
-    B = len(images_a)
-    th, tw = draws[0][5], draws[0][6]
-    for a, b_, d in zip(images_a, images_b, draws):
-        for x in (a, b_):
-            if x.dtype != np.uint8 or x.ndim != 3 or x.shape[2] != 3:
-                raise ValueError("images must be uint8 (H, W, 3) arrays")
-        if a.shape != b_.shape:
-            raise ValueError("the images of a synthetic pair differ in size: %s vs %s" % (a.shape[:2], b_.shape[:2]))
-        if (d[5], d[6]) != (th, tw):
-            raise ValueError("every sample of a batch needs the same crop size")
-        if d[3] < 0 or d[4] < 0 or d[3] + th > d[1] or d[4] + tw > d[2]:
-            raise ValueError("crop window (%d,%d,%d,%d) outside the resized image (%d,%d)" % (d[3], d[4], th, tw, d[1], d[2]))
     for m in list(masks) + list(sems_a) + list(sems_b):
         if m.dtype != np.uint8 or m.ndim != 2 or m.size == 0:
             raise ValueError("masks and label maps must be non-empty uint8 (H, W) arrays")
-    descs, offs, total = pack_synth_batch(images_a, images_b, masks, sems_a, sems_b, draws)
-    slot = None
-    if ring is not None:
-        slot, stage = ring.take(total)
-    else:
-        stage = torch.empty(total, dtype=torch.uint8).pin_memory()
-    sv = stage.numpy()
-    ctypes.memmove(sv.ctypes.data, ctypes.addressof(descs), ctypes.sizeof(descs))
-    # copied here, in the calling (producer) thread, for the reason given in launch_transform
-    for a, o in zip(list(images_a) + list(images_b) + list(masks) + list(sems_a) + list(sems_b), offs):
-        sv[o:o + a.nbytes] = a.reshape(-1)
-    ksize = 3
-    for a, d in zip(images_a, draws):
-        ksize = max(ksize, lib.munit_image_ksize(a.shape[0], d[1]), lib.munit_image_ksize(a.shape[1], d[2]))
-    vp = ctypes.c_void_p
-    with torch.cuda.stream(stream):
-        dev = torch.empty(total, dtype=torch.uint8, device=device)
-        dev.copy_(stage[:total], non_blocking=True)     # the one H2D transfer of the batch
-        if slot is not None:
-            copied = torch.cuda.Event()
-            copied.record(stream)
-            ring.mark(slot, copied)
-        st = vp(stream.cuda_stream)
-        base = dev.data_ptr()
-        images = torch.empty((2 * B, 3, th, tw), device=device, dtype=torch.float32, memory_format=torch.channels_last)
-        nws = lib.munit_image_preprocess_workspace_bytes(2 * B, th, tw, ksize)
-        ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=device)
-        rc = lib.munit_image_preprocess(vp(base), vp(base), 2 * B, th, tw, ksize, vp(images.data_ptr()),
-                                        vp(ws.data_ptr()), ctypes.c_size_t(nws), st)
-        if rc:
-            raise RuntimeError("munit_image_preprocess: " + lib.munit_last_error().decode())
-        planes = torch.empty((3 * B, 1, th, tw), device=device, dtype=torch.float32)
-        nwl = lib.munit_label_preprocess_workspace_bytes(3 * B, th, tw)
-        wsl = torch.empty(max(nwl, 1), dtype=torch.uint8, device=device)
-        rc = lib.munit_label_preprocess(vp(base), vp(base + 2 * B * ctypes.sizeof(ImageDesc)), 3 * B, th, tw,
-                                        vp(planes.data_ptr()), vp(wsl.data_ptr()), ctypes.c_size_t(nwl), st)
-        if rc:
-            raise RuntimeError("munit_label_preprocess: " + lib.munit_last_error().decode())
-        keep = (dev, ws, wsl, images, planes) if slot is not None else (stage, dev, ws, wsl, images, planes)
-        ev = torch.cuda.Event()
-        ev.record(stream)
+    images, planes, ev, keep = _launch(_synth_groups(images_a, images_b, masks, sems_a, sems_b), 2, draws,
+                                       "every sample of a batch needs the same crop size", "munit_label_preprocess",
+                                       device, stream, ring)
+    B = len(draws)
     out = (images[:B], images[B:], planes[:B], planes[B:2 * B], planes[2 * B:])
-    return out, ev, keep
+    return out, ev, keep + (images, planes)
 
 
 class _Dataset:
@@ -412,9 +391,7 @@ class DeviceBatchLoader:
         return flip, rs_h, rs_w, i, j, th, tw
 
     def _ensure_device(self):
-        if not torch.cuda.is_available():
-            raise RuntimeError("munit_amd.data: the transforms run on the GPU (libmunit_hip.so); no HIP device is "
-                               "visible and there is no CPU fallback")
+        _require_device()
         if self.device is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if self._pool is None:
@@ -439,7 +416,7 @@ class DeviceBatchLoader:
         arrays = [f.result() for f in futs]
         masks = None if mfuts is None else [f.result() for f in mfuts]
         draws = [self.draw(a.shape[1], a.shape[0], rng) for a in arrays]
-        return launch_transform(arrays, masks, draws, self.device, self._stream, ring, self._pool)
+        return launch_transform(arrays, masks, draws, self.device, self._stream, ring)
 
     def _launch_batch(self, indices, rng):
         """Decode one batch with the thread pool, draw its random parameters, launch the device transform."""
@@ -518,14 +495,6 @@ class DeviceBatchLoader:
                     q.get(timeout=0.05)
                 except queue.Empty:
                     pass
-
-
-
-def _world():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(), dist.get_world_size()
-    return 0, 1
 
 
 def get_data_loader_list(root, file_list, batch_size, train, new_size=None, height=256, width=256, num_workers=4,

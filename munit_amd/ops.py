@@ -713,62 +713,110 @@ def layer_norm(x, gamma, beta, relu=False, eps=1e-5):
     return _LayerNorm.apply(x, gamma, beta, relu, eps)
 
 
-class _AvgPool3s2(Function):
+# The six pools (csrc/pointwise.hip, seg.hip, dann.hip) differ in data only.  fwd / bwd: the library symbols; tag: what their
+# failures are reported as; noun: what _require calls the input; extent(h, w): the output map's (ho, wo), None where the
+# output has the input's shape; form: "map" (an NHWC map), "bc11" ((B, C, 1, 1)) or "bc" (plain (B, C)); flat: the library
+# takes (B, H*W, C), not (B, H, W, C); sink: None, or the NAME of the kinks channel ("seg" / "dann") that records the pool's
+# uint8 winners (B, Ho, Wo, C) -- the name, because `kinks` rebinds the sink globals while the ops run; check: an optional
+# precondition on the NHWC input's shape.
+_Pool = collections.namedtuple("_Pool", "fwd bwd tag noun extent form flat sink check")
+
+
+def _half_up(h, w):
+    return (h - 1) // 2 + 1, (w - 1) // 2 + 1
+
+
+def _maxpool2_check(shape):
+    b, c, h, w = shape
+    if h < 2 or w < 2 or c % 4:
+        raise RuntimeError("munit_amd.maxpool2: needs H, W >= 2 and C %% 4 == 0, got %s" % (tuple(shape),))
+
+
+_POOLS = {
+    "avgpool3s2": _Pool("munit_avgpool3s2_fwd", "munit_avgpool3s2_bwd", "avgpool", "avgpool input", _half_up, "map", False,
+                        None, None),
+    "global_avgpool": _Pool("munit_gap_fwd", "munit_gap_bwd", "gap", "global-avgpool input", lambda h, w: (1, 1), "bc11", True,
+                            None, None),
+    "maxpool3s2": _Pool("munit_maxpool3s2_fwd", "munit_maxpool3s2_bwd", "maxpool3s2", "maxpool input", _half_up, "map", False,
+                        "seg", None),
+    "avgpool7": _Pool("munit_avgpool7_fwd", "munit_avgpool7_bwd", "avgpool7", "avgpool7 input", None, "map", False, None, None),
+    "maxpool2": _Pool("munit_maxpool2_fwd", "munit_maxpool2_bwd", "maxpool2", "maxpool input", lambda h, w: (h // 2, w // 2),
+                      "map", False, "dann", _maxpool2_check),
+    "avgpool16": _Pool("munit_avgpool16_fwd", "munit_avgpool16_bwd", "avgpool16", "avgpool16 input", None, "bc", False, None,
+                       None),
+}
+
+
+class _Pooling(Function):
     @staticmethod
     @_guarded
-    def forward(ctx, x):
-        _require(x, "avgpool input")
+    def forward(ctx, x, pool):
         lib = _lib.load()
+        _require(x, pool.noun)
         x = nhwc(x)
         b, c, h, w = x.shape
-        y = empty_nhwc(b, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1, x)
-        _lib.check(lib.munit_avgpool3s2_fwd(_p(x), _p(y), b, h, w, c, _stream()), "avgpool_fwd")
-        ctx.shape = (b, c, h, w)
+        if pool.check is not None:
+            pool.check(x.shape)
+        if pool.form == "bc":
+            y = torch.empty((b, c), device=x.device, dtype=torch.float32)
+        elif pool.extent is None:
+            y = torch.empty_like(x)
+        else:
+            ho, wo = pool.extent(h, w)
+            y = empty_nhwc(b, c, ho, wo, x)
+        idx = torch.empty((b, ho, wo, c), dtype=torch.uint8, device=x.device) if pool.sink else None
+        winners = () if idx is None else (_p(idx),)
+        dims = (b, h * w, c) if pool.flat else (b, h, w, c)
+        _lib.check(getattr(lib, pool.fwd)(_p(x), _p(y), *winners, *dims, _stream()), pool.tag + "_fwd")
+        sink = SEG_SINK if pool.sink == "seg" else DANN_SINK if pool.sink == "dann" else None    # the globals, as they are now
+        if sink is not None:
+            sink.append(idx)
+        ctx.pool, ctx.shape, ctx.dims = pool, x.shape, dims
+        ctx.save_for_backward(idx)
         return y
 
     @staticmethod
     @_guarded
     def backward(ctx, dy):
         lib = _lib.load()
+        pool = ctx.pool
+        (idx,) = ctx.saved_tensors
         b, c, h, w = ctx.shape
-        dy = nhwc(dy)
+        dy = nhwc(dy) if pool.form == "map" else dy.contiguous()
         dx = empty_nhwc(b, c, h, w, dy)
-        _lib.check(lib.munit_avgpool3s2_bwd(_p(dy), _p(dx), b, h, w, c, _stream()), "avgpool_bwd")
-        return dx
+        winners = () if idx is None else (_p(idx),)
+        _lib.check(getattr(lib, pool.bwd)(_p(dy), *winners, _p(dx), *ctx.dims, _stream()), pool.tag + "_bwd")
+        return dx, None
 
 
 def avgpool3s2(x):
     """nn.AvgPool2d(3, stride=2, padding=1, count_include_pad=False) (networks.py:32-34)."""
-    return _AvgPool3s2.apply(x)
-
-
-class _GlobalAvgPool(Function):
-    @staticmethod
-    @_guarded
-    def forward(ctx, x):
-        _require(x, "global-avgpool input")
-        lib = _lib.load()
-        x = nhwc(x)
-        b, c, h, w = x.shape
-        y = empty_nhwc(b, c, 1, 1, x)
-        _lib.check(lib.munit_gap_fwd(_p(x), _p(y), b, h * w, c, _stream()), "gap_fwd")
-        ctx.shape = (b, c, h, w)
-        return y
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, dy):
-        lib = _lib.load()
-        b, c, h, w = ctx.shape
-        dy = dy.contiguous()
-        dx = empty_nhwc(b, c, h, w, dy)
-        _lib.check(lib.munit_gap_bwd(_p(dy), _p(dx), b, h * w, c, _stream()), "gap_bwd")
-        return dx
+    return _Pooling.apply(x, _POOLS["avgpool3s2"])
 
 
 def global_avgpool(x):
     """nn.AdaptiveAvgPool2d(1) (networks.py:471)."""
-    return _GlobalAvgPool.apply(x)
+    return _Pooling.apply(x, _POOLS["global_avgpool"])
+
+
+def maxpool3s2(x):
+    """nn.MaxPool2d(3, 2, 1) (scripts/resnet.py); ties go to the first maximal element in window order."""
+    return _Pooling.apply(x, _POOLS["maxpool3s2"])
+
+
+def avgpool7(x):
+    """nn.AvgPool2d(7, stride=1, padding=3), padding counted (scripts/resnet.py): every window's divisor is 49."""
+    return _Pooling.apply(x, _POOLS["avgpool7"])
+
+
+def maxpool2(x):
+    """nn.MaxPool2d(2) (scripts/utils.py:1374): floor output size, ties to the first maximal element in window order."""
+    return _Pooling.apply(x, _POOLS["maxpool2"])
+
+
+def avgpool16(x):
+    """nn.AvgPool2d((16, 16)) + .squeeze() on a map of 16..31 per axis (scripts/utils.py:1378, 1388): (B, C)."""
+    return _Pooling.apply(x, _POOLS["avgpool16"])
 
 
 class _L1Mean(Function):
@@ -1154,41 +1202,6 @@ def frozen_conv(x, weight, bias, w_dgrad, stride, pad, act="none", link_in=None,
     return _FrozenConv.apply(x, weight, bias, w_dgrad, stride, pad, act, link_in, link_out)
 
 
-class _MaxPool3s2(Function):
-    @staticmethod
-    @_guarded
-    def forward(ctx, x):
-        lib = _lib.load()
-        _require(x, "maxpool input")
-        x = nhwc(x)
-        b, c, h, w = x.shape
-        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        y = empty_nhwc(b, c, ho, wo, x)
-        idx = torch.empty((b, ho, wo, c), dtype=torch.uint8, device=x.device)
-        _lib.check(lib.munit_maxpool3s2_fwd(_p(x), _p(y), _p(idx), b, h, w, c, _stream()), "maxpool3s2_fwd")
-        if SEG_SINK is not None:
-            SEG_SINK.append(idx)
-        ctx.shape = x.shape
-        ctx.save_for_backward(idx)
-        return y
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, dy):
-        lib = _lib.load()
-        (idx,) = ctx.saved_tensors
-        b, c, h, w = ctx.shape
-        dy = nhwc(dy)
-        dx = empty_nhwc(b, c, h, w, dy)
-        _lib.check(lib.munit_maxpool3s2_bwd(_p(dy), _p(idx), _p(dx), b, h, w, c, _stream()), "maxpool3s2_bwd")
-        return dx
-
-
-def maxpool3s2(x):
-    """nn.MaxPool2d(3, 2, 1) (scripts/resnet.py); ties go to the first maximal element in window order."""
-    return _MaxPool3s2.apply(x)
-
-
 class _AddRelu(Function):
     """BasicBlock tail relu(a + r).  link: park the gradient of r there (the identity skip: the block's first convolution
     adds it in its backward-data epilogue) and return none for r.  dann: a block of the feature classifier (its signs go to
@@ -1349,34 +1362,6 @@ def seg_cross_entropy_direct(logits, gt, scale=4, norm=None):
     w*scale) float32 truncated like .type(torch.long) (trainer.py:1305-1317): no mask, no class merge.  Sum of the pixel
     losses / norm (default: all pixels, i.e. the mean).  A label outside 0..K-1 makes the loss NaN (include/munit_hip.h)."""
     return _seg_ce(_SEG_DIRECT, logits, gt, None, scale, norm)
-
-
-class _AvgPool7(Function):
-    @staticmethod
-    @_guarded
-    def forward(ctx, x):
-        lib = _lib.load()
-        _require(x, "avgpool7 input")
-        x = nhwc(x)
-        b, c, h, w = x.shape
-        y = torch.empty_like(x)
-        _lib.check(lib.munit_avgpool7_fwd(_p(x), _p(y), b, h, w, c, _stream()), "avgpool7_fwd")
-        return y
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, dy):
-        lib = _lib.load()
-        dy = nhwc(dy)
-        b, c, h, w = dy.shape
-        dx = torch.empty_like(dy)
-        _lib.check(lib.munit_avgpool7_bwd(_p(dy), _p(dx), b, h, w, c, _stream()), "avgpool7_bwd")
-        return dx
-
-
-def avgpool7(x):
-    """nn.AvgPool2d(7, stride=1, padding=3), padding counted (scripts/resnet.py): every window's divisor is 49."""
-    return _AvgPool7.apply(x)
 
 
 def seg_labels(logits, scale=8):
@@ -1592,71 +1577,6 @@ def batch_norm(x, gamma, beta, running_mean, running_var, relu=False, eps=1e-5, 
                                            _p(gamma), _p(beta), int(bool(relu)), 1, c_float(eps), c_float(momentum), None, 0,
                                            _stream()), "batchnorm_fwd (eval)")
     return y
-
-
-class _MaxPool2(Function):
-    @staticmethod
-    @_guarded
-    def forward(ctx, x):
-        lib = _lib.load()
-        _require(x, "maxpool input")
-        x = nhwc(x)
-        b, c, h, w = x.shape
-        if h < 2 or w < 2 or c % 4:
-            raise RuntimeError("munit_amd.maxpool2: needs H, W >= 2 and C %% 4 == 0, got %s" % (tuple(x.shape),))
-        y = empty_nhwc(b, c, h // 2, w // 2, x)
-        idx = torch.empty((b, h // 2, w // 2, c), dtype=torch.uint8, device=x.device)
-        _lib.check(lib.munit_maxpool2_fwd(_p(x), _p(y), _p(idx), b, h, w, c, _stream()), "maxpool2_fwd")
-        if DANN_SINK is not None:
-            DANN_SINK.append(idx)
-        ctx.shape = x.shape
-        ctx.save_for_backward(idx)
-        return y
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, dy):
-        lib = _lib.load()
-        (idx,) = ctx.saved_tensors
-        b, c, h, w = ctx.shape
-        dy = nhwc(dy)
-        dx = empty_nhwc(b, c, h, w, dy)
-        _lib.check(lib.munit_maxpool2_bwd(_p(dy), _p(idx), _p(dx), b, h, w, c, _stream()), "maxpool2_bwd")
-        return dx
-
-
-def maxpool2(x):
-    """nn.MaxPool2d(2) (scripts/utils.py:1374): floor output size, ties to the first maximal element in window order."""
-    return _MaxPool2.apply(x)
-
-
-class _AvgPool16(Function):
-    @staticmethod
-    @_guarded
-    def forward(ctx, x):
-        lib = _lib.load()
-        _require(x, "avgpool16 input")
-        x = nhwc(x)
-        b, c, h, w = x.shape
-        y = torch.empty((b, c), device=x.device, dtype=torch.float32)
-        _lib.check(lib.munit_avgpool16_fwd(_p(x), _p(y), b, h, w, c, _stream()), "avgpool16_fwd")
-        ctx.shape = x.shape
-        return y
-
-    @staticmethod
-    @_guarded
-    def backward(ctx, dy):
-        lib = _lib.load()
-        b, c, h, w = ctx.shape
-        dy = dy.contiguous()
-        dx = empty_nhwc(b, c, h, w, dy)
-        _lib.check(lib.munit_avgpool16_bwd(_p(dy), _p(dx), b, h, w, c, _stream()), "avgpool16_bwd")
-        return dx
-
-
-def avgpool16(x):
-    """nn.AvgPool2d((16, 16)) + .squeeze() on a map of 16..31 per axis (scripts/utils.py:1378, 1388): (B, C)."""
-    return _AvgPool16.apply(x)
 
 
 # ------------------------------------------------------------------------------------------

@@ -84,6 +84,85 @@ def test_pack_batch_layout():
     assert (descs[3].src_h, descs[3].src_w, descs[3].src_off) == (9, 3, moffs[1])
 
 
+def test_pack_batch_without_masks_still_reserves_the_mask_descriptors():
+    arrays = [np.zeros((5, 7, 3), np.uint8), np.zeros((4, 4, 3), np.uint8)]
+    draws = [(1, 5, 7, 0, 1, 4, 4), (0, 4, 4, 0, 0, 4, 4)]
+    descs, offs, moffs, total = D.pack_batch(arrays, None, draws)
+    assert len(descs) == 4 and bytes(descs)[2 * ctypes.sizeof(ImageDesc):] == bytes(2 * ctypes.sizeof(ImageDesc))
+    assert moffs == [] and offs[0] == 256 and offs == [256, 256 + 112] and total == 256 + 112 + 48
+    assert (descs[1].src_off, descs[1].rs_h, descs[1].rs_w, descs[1].kind) == (offs[1], 4, 4, 0)
+
+
+def test_pack_batch_mask_descriptors_carry_the_draw_but_no_resized_size():
+    arrays = [np.zeros((5, 7, 3), np.uint8), np.zeros((4, 4, 3), np.uint8)]
+    masks = [np.zeros((5, 7), np.uint8), np.zeros((9, 3), np.uint8)]
+    draws = [(1, 5, 7, 0, 1, 4, 4), (0, 6, 5, 2, 1, 4, 4)]
+    descs, offs, moffs, total = D.pack_batch(arrays, masks, draws)
+    assert len(descs) == 4 and len(moffs) == 2
+    for b, (m, d) in enumerate(zip(masks, draws)):
+        md = descs[2 + b]
+        assert (md.rs_h, md.rs_w, md.kind) == (0, 0, 0)
+        assert (md.crop_i, md.crop_j, md.flip) == (d[3], d[4], d[0])
+        assert (md.src_h, md.src_w, md.src_off) == (m.shape[0], m.shape[1], moffs[b])
+        assert (descs[b].rs_h, descs[b].rs_w) == (d[1], d[2])           # the image descriptors do carry it
+
+
+def _mask_batch(rng):
+    """2 images + 2 masks with different source sizes, as launch_transform stages them."""
+    arrays = [rng.randint(0, 256, (h, w, 3)).astype(np.uint8) for h, w in ((5, 7), (9, 4))]
+    masks = [rng.randint(0, 256, (h, w)).astype(np.uint8) for h, w in ((6, 3), (5, 11))]
+    draws = [(1, 5, 7, 0, 1, 4, 4), (0, 9, 4, 3, 0, 4, 4)]
+    return D._image_groups(arrays, masks), 1, draws, arrays + masks
+
+
+def _synth_batch(rng):
+    """3 synthetic samples with the sizes of test_cpu_synth_data.test_packed_batch_layout."""
+    sizes, psizes = [(37, 53), (64, 48), (90, 61)], [(20, 31), (97, 70), (90, 61)]
+    cols = [[rng.randint(0, 256, (h, w, 3)).astype(np.uint8) for h, w in sizes] for _ in range(2)]
+    cols += [[rng.randint(0, 256, (h, w)).astype(np.uint8) for h, w in psizes] for _ in range(3)]
+    draws = [(1, 45, 32, 3, 0, 24, 20), (0, 32, 42, 8, 22, 24, 20), (1, 47, 32, 0, 5, 24, 20)]
+    return D._synth_groups(*cols), 2, draws, [a for col in cols for a in col]
+
+
+@pytest.mark.parametrize("batch", [_mask_batch, _synth_batch])
+def test_host_half_of_the_launch_fills_a_plain_buffer(batch):
+    groups, n_img, draws, payloads = batch(np.random.RandomState(1))
+    descs, offs, total, th, tw = D._lay_out(groups, n_img, draws, "unequal crop sizes")
+    assert (th, tw) == draws[0][5:] and len(offs) == len(payloads) == len(descs)
+    buf = np.full(total + 64, 0xA5, np.uint8)
+    D._fill(buf, descs, offs, groups)
+    head = bytes(descs)
+    assert buf[:len(head)].tobytes() == head
+    written = np.zeros(total + 64, bool)
+    written[:len(head)] = True
+    for d, o, a in zip(descs, offs, payloads):                         # payloads in descriptor order
+        assert d.src_off == o and o % 16 == 0 and o >= (len(head) + 255) // 256 * 256
+        assert np.array_equal(buf[o:o + a.nbytes], a.reshape(-1))
+        assert not written[o:o + a.nbytes].any()
+        written[o:o + a.nbytes] = True
+    assert written[:total].sum() == len(head) + sum(a.nbytes for a in payloads)
+    assert (buf[~written] == 0xA5).all() and not written[total:].any()  # gaps and everything from `total` on: untouched
+
+
+def test_launch_transform_refuses_bad_batches_on_the_host():
+    """Every refusal comes from the host half: no device, stream or library call is reached (device and stream are None)."""
+    good = np.zeros((8, 8, 3), np.uint8)
+    draw = (0, 8, 8, 0, 0, 8, 8)
+
+    def launch(arrays, draws, masks=None):
+        return D.launch_transform(arrays, masks, draws, None, None)
+
+    with pytest.raises(ValueError, match=r"images must be uint8 \(H, W, 3\) arrays"):
+        launch([good.astype(np.float32)], [draw])
+    with pytest.raises(ValueError, match=r"images must be uint8 \(H, W, 3\) arrays"):
+        launch([good, np.zeros((8, 8), np.uint8)], [draw, draw])
+    with pytest.raises(ValueError, match="crop=False needs equally sized images inside a batch"):
+        launch([good, good], [draw, (0, 8, 8, 0, 0, 8, 7)])
+    for outside in ((0, 8, 8, 1, 0, 8, 8), (0, 8, 8, 0, 1, 8, 8), (0, 8, 8, -1, 0, 8, 8), (0, 8, 8, 0, -1, 8, 8)):
+        with pytest.raises(ValueError, match=r"crop window \(-?\d,-?\d,8,8\) outside the resized image \(8,8\)"):
+            launch([good, good], [draw, outside], masks=[good[:, :, 0], good[:, :, 0]])
+
+
 def test_loader_refuses_cpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")

@@ -2,6 +2,7 @@
 mirror of the reference interface (module tree, state_dict keys, init RNG stream, config
 defaults, LR schedule, optimizer state format) and the data-parallel exchange over gloo."""
 import ctypes
+import fnmatch
 import os
 import re
 import subprocess
@@ -956,3 +957,23 @@ def test_parity_pinned_audits_what_the_oracle_consumed():
     assert O.KINK_MASKS is None
     with parity.pinned(None) as audit:                                  # no masks: no pinning, no audit
         assert O.KINK_MASKS is None
+
+
+# ---- the pooling table of munit_amd.ops ------------------------------------------------------------------------------------
+def test_pooling_table_names_every_pool_symbol_once_and_the_two_winner_channels():
+    from munit_amd import _lib, ops
+    assert sorted(ops._POOLS) == ["avgpool16", "avgpool3s2", "avgpool7", "global_avgpool", "maxpool2", "maxpool3s2"]
+    assert all(callable(getattr(ops, name)) for name in ops._POOLS)      # keyed by the public functions' names
+    named = [s for p in ops._POOLS.values() for s in (p.fwd, p.bwd)]
+    want = [s for s in _lib.SIGNATURES if fnmatch.fnmatchcase(s, "munit_*pool*") or fnmatch.fnmatchcase(s, "munit_gap_*")]
+    assert len(want) == 12 and sorted(named) == sorted(want) and len(set(named)) == 12
+    assert all(p.fwd.endswith("_fwd") and p.bwd == p.fwd[:-3] + "bwd" for p in ops._POOLS.values())
+    # a channel is held by NAME: the lists behind SEG_SINK / DANN_SINK exist only while ops.kinks is active
+    assert {n: p.sink for n, p in ops._POOLS.items() if p.sink is not None} == {"maxpool3s2": "seg", "maxpool2": "dann"}
+    assert ops._POOLS["maxpool2"].check is not None and [n for n, p in ops._POOLS.items() if p.check] == ["maxpool2"]
+    with pytest.raises(RuntimeError, match=r"munit_amd.maxpool2: needs H, W >= 2 and C % 4 == 0, got \(1, 6, 4, 4\)"):
+        ops._POOLS["maxpool2"].check(torch.Size((1, 6, 4, 4)))
+    ops._POOLS["maxpool2"].check(torch.Size((1, 4, 2, 2)))
+    assert ops._POOLS["avgpool3s2"].extent(5, 7) == (3, 4) and ops._POOLS["maxpool3s2"].extent(1, 1) == (1, 1)
+    assert ops._POOLS["maxpool2"].extent(5, 3) == (2, 1) and ops._POOLS["global_avgpool"].extent(3, 5) == (1, 1)
+    assert [n for n, p in ops._POOLS.items() if p.flat] == ["global_avgpool"]

@@ -180,6 +180,36 @@ def test_packed_batch_layout():
     assert ctypes.sizeof(D.ImageDesc) == 40          # the layout munit_image_preprocess reads is unchanged
 
 
+def test_launch_synth_transform_refuses_bad_batches_on_the_host():
+    """Every refusal comes from the host half: no device, stream or library call is reached (device and stream are None)."""
+    img, plane = np.zeros((8, 8, 3), np.uint8), np.zeros((5, 6), np.uint8)
+    draw = (0, 8, 8, 0, 0, 8, 8)
+
+    def launch(draws=(draw, draw), **bad):
+        cols = dict(a=[img, img], b=[img, img], mask=[plane, plane], sem_a=[plane, plane], sem_b=[plane, plane])
+        for name, x in bad.items():
+            cols[name] = [cols[name][0], x]
+        return D.launch_synth_transform(cols["a"], cols["b"], cols["mask"], cols["sem_a"], cols["sem_b"], list(draws), None,
+                                        None)
+
+    for name in ("a", "b"):
+        with pytest.raises(ValueError, match=r"images must be uint8 \(H, W, 3\) arrays"):
+            launch(**{name: img.astype(np.float32)})
+    with pytest.raises(ValueError, match=r"images must be uint8 \(H, W, 3\) arrays"):
+        launch(a=img[:, :, 0], b=img[:, :, 0])
+    with pytest.raises(ValueError, match="every sample of a batch needs the same crop size"):
+        launch(draws=(draw, (0, 8, 8, 0, 0, 7, 8)))
+    for outside in ((0, 8, 8, 1, 0, 8, 8), (0, 8, 8, 0, 1, 8, 8), (0, 8, 8, -1, 0, 8, 8), (0, 8, 8, 0, -1, 8, 8)):
+        with pytest.raises(ValueError, match=r"crop window \(-?\d,-?\d,8,8\) outside the resized image \(8,8\)"):
+            launch(draws=(draw, outside))
+    with pytest.raises(ValueError, match=r"the images of a synthetic pair differ in size: \(8, 8\) vs \(8, 9\)"):
+        launch(b=np.zeros((8, 9, 3), np.uint8))
+    for name in ("mask", "sem_a", "sem_b"):
+        for bad in (np.zeros((0, 6), np.uint8), np.zeros((5, 6, 1), np.uint8), plane.astype(np.float32)):
+            with pytest.raises(ValueError, match=r"masks and label maps must be non-empty uint8 \(H, W\) arrays"):
+                launch(**{name: bad})
+
+
 def test_len_and_sharding(tmp_path):
     lists, _ = _files(tmp_path, [(30, 30)] * 9)
     assert len(_loader(lists, batch=2, new_size=30, height=8, width=8)) == 4

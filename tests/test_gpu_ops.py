@@ -819,3 +819,77 @@ def test_kinks_records_one_relu_mask_and_two_l1_signs():
     assert len(k.mask) == 1 and torch.equal(k.mask[0], y > 0) and 0 < int(k.mask[0].sum()) < y.numel()
     assert len(k.l1) == 2 and torch.equal(k.l1[0], a > b) and torch.equal(k.l1[1], a > b)
     assert (ops.MASK_SINK, ops.L1_SINK, ops.SEG_SINK, ops.DANN_SINK) == (None, None, None, None)
+
+
+def _half_up(h, w):
+    return (h - 1) // 2 + 1, (w - 1) // 2 + 1
+
+
+# public function -> (library symbols' stem, output extent or None for (B, C), the kinks channel of its winners, the library
+# takes (B, H*W, C)): the test's own statement of what each wrapper has to hand to the library, not read from ops._POOLS
+_POOL_CALLS = {
+    "avgpool3s2": ("munit_avgpool3s2", _half_up, None, False),
+    "global_avgpool": ("munit_gap", lambda h, w: (1, 1), None, True),
+    "maxpool3s2": ("munit_maxpool3s2", _half_up, "seg", False),
+    "avgpool7": ("munit_avgpool7", lambda h, w: (h, w), None, False),
+    "maxpool2": ("munit_maxpool2", lambda h, w: (h // 2, w // 2), "dann", False),
+    "avgpool16": ("munit_avgpool16", None, None, False),
+}
+_POOL_SHAPES = [("avgpool3s2", (2, 3, 5, 7)), ("avgpool3s2", (1, 1, 1, 1)), ("global_avgpool", (2, 66, 3, 5)),
+                ("maxpool3s2", (1, 3, 5, 7)), ("maxpool3s2", (1, 2, 1, 1)), ("avgpool7", (1, 4, 9, 5)), ("avgpool7", (1, 4, 1, 1)),
+                ("maxpool2", (1, 4, 5, 3)), ("avgpool16", (2, 8, 17, 31))]
+
+
+@pytest.mark.parametrize("layout", ["channels_last", "nchw"])
+@pytest.mark.parametrize("name,shape", _POOL_SHAPES, ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
+def test_pool_wrappers_equal_direct_library_calls(name, shape, layout):
+    """Each public pooling function, forward and backward, bit for bit against direct calls of its two library symbols on
+    dense NHWC copies, writing into buffers filled with NaN (0xEE for the winners) beforehand; and what it leaves in the
+    kink sinks: the max-pools their winners, once, in their own channel, the average pools nothing."""
+    from munit_amd import _lib, ops
+    lib = _lib.load()
+    stem, extent, channel, flat = _POOL_CALLS[name]
+    b, c, h, w = shape
+    x = rnd(shape, 11).float().to(dev())
+    x = x.contiguous(memory_format=torch.channels_last) if layout == "channels_last" else x.contiguous()
+    x.requires_grad_(True)
+    with ops.kinks(seg=True, dann=True) as k:
+        y = getattr(ops, name)(x)
+    out_shape = (b, c) if extent is None else (b, c) + extent(h, w)
+    assert tuple(y.shape) == out_shape and y.dtype == torch.float32
+    if name in ("global_avgpool", "avgpool16"):                  # a non-contiguous view: every second column of (.., 2C, ..)
+        dy = rnd((b, 2 * c) + out_shape[2:], 12).float().to(dev())[:, ::2]
+        assert not dy.is_contiguous()
+    else:
+        dy = rnd(out_shape, 12).float().to(dev())               # plain NCHW: the wrapper makes it NHWC
+    y.backward(dy)
+
+    nan = float("nan")
+    dims = (b, h * w, c) if flat else (b, h, w, c)
+    rows = lambda t: t.permute(0, 2, 3, 1).contiguous() if t.dim() == 4 else t.contiguous()      # dense NHWC / (B, C)
+    x_raw, dy_raw = rows(x.detach()), rows(dy)
+    y_raw = torch.full(dy_raw.shape, nan, device=dev())
+    dx_raw = torch.full(x_raw.shape, nan, device=dev())
+    win = (torch.full(dy_raw.shape, 0xEE, dtype=torch.uint8, device=dev()),) if channel else ()
+    wp = tuple(ops._p(t) for t in win)
+    _lib.check(getattr(lib, stem + "_fwd")(ops._p(x_raw), ops._p(y_raw), *wp, *dims, ops._stream()), stem + "_fwd")
+    _lib.check(getattr(lib, stem + "_bwd")(ops._p(dy_raw), *wp, ops._p(dx_raw), *dims, ops._stream()), stem + "_bwd")
+    assert not torch.isnan(y_raw).any() and not torch.isnan(dx_raw).any()
+    assert torch.equal(rows(y.detach()), y_raw)
+    assert torch.equal(rows(x.grad), dx_raw)
+    got = {"seg": k.seg, "dann": k.dann}
+    for ch, entries in got.items():
+        assert len(entries) == (1 if ch == channel else 0), (ch, len(entries))
+    if channel:
+        assert got[channel][0].dtype == torch.uint8 and torch.equal(got[channel][0], win[0]) and int(win[0].max()) < 9
+    assert ops.SEG_SINK is None and ops.DANN_SINK is None
+
+
+@pytest.mark.parametrize("shape", [(1, 6, 4, 4), (1, 4, 1, 4)])
+def test_maxpool2_refuses_its_precondition_before_any_launch(shape):
+    from munit_amd import ops
+    x = rnd(shape, 1).float().to(dev())
+    with ops.kinks(seg=True, dann=True) as k:
+        with pytest.raises(RuntimeError, match=r"munit_amd\.maxpool2: needs H, W >= 2 and C %% 4 == 0, got \(%d, %d, %d, %d\)" % shape):
+            ops.maxpool2(x)
+    assert k.seg == [] and k.dann == []
