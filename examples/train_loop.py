@@ -1,6 +1,6 @@
 """Minimal end-to-end training loop on munit_amd: the loaders of munit_amd.data feeding MUNIT_Trainer, in the
 shape of the reference's scripts/train.py:157-330 (dis_update / gen_update cadence of `ratio_disc_gen`,
-update_learning_rate first, periodic sample grids, periodic save).  Control plane only -- no comet and no FID.
+update_learning_rate first, periodic sample grids, periodic save, periodic FID).  Control plane only -- no comet.
 
   python examples/train_loop.py --config configs.yaml --data-root /path/with/trainA,trainB,testA,testB [--iters N]
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_loop.py ...      (data parallel, RCCL)
@@ -26,6 +26,12 @@ are taken once before the first iteration; every `image_save_iter` iterations ge
 absent or 0 writes nothing).  All ranks sample -- sample() draws styles from the host RNG -- and rank 0 writes.  Checkpoints
 (--save-every) go to checkpoints/ unless --output names another folder; --output alone keeps its meaning, a bare checkpoint
 folder and no grids.
+
+FID (--fid-every N, default 0): the reference builds get_inception_metrics when `eval_fid` > 0 (scripts/train.py:119-130) but
+never calls it in its loop, so the cadence is this script's.  With eval_fid > 0 and N > 0 the FID loader
+(data_list_fid_a / data_list_fid_b, batch_size_fid) and prepare_inception_metrics(inception_moment_path) are built as the
+reference does -- the Inception weights come from the file MUNIT_INCEPTION_CKPT names -- and rank 0 evaluates and prints `FID`
+after every N-th iteration.
 """
 import argparse
 import os
@@ -162,6 +168,27 @@ def write_samples(trainer, config, it, displays, image_directory, rank=0, write=
             write(outputs, n, image_directory, "train_current", comet_exp)
 
 
+def fid_due(config, it, every):
+    """Whether iteration `it` (counted from 0) ends with an FID evaluation: eval_fid > 0 in the config, --fid-every N > 0,
+    and it + 1 a multiple of N."""
+    return int(config.get("eval_fid") or 0) > 0 and int(every or 0) > 0 and (it + 1) % int(every) == 0
+
+
+def build_fid(config):
+    """(fid_loader factory, get_inception_metrics) as scripts/train.py:119-130 builds them."""
+    from munit_amd import data as D
+    from munit_amd.inception_utils import prepare_inception_metrics
+    loader = lambda: D.get_fid_data_loader(config["data_list_fid_a"], config["data_list_fid_b"], config["batch_size_fid"],
+                                           train=False, new_size=config["new_size"], num_workers=config.get("num_workers", 4))
+    return loader, prepare_inception_metrics(inception_moment=config["inception_moment_path"], parallel=False)
+
+
+def evaluate_fid(trainer, fid):
+    """One FID evaluation with what build_fid returned: a fresh pass over the FID list, quietly; a Python float."""
+    loader, get_inception_metrics = fid
+    return get_inception_metrics(trainer, loader(), prints=False)
+
+
 def main(argv=None, synth_pairs=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
@@ -175,6 +202,8 @@ def main(argv=None, synth_pairs=None):
     ap.add_argument("--output-path", default=None, help="run folder in the reference's layout: checkpoints/ and images/ "
                     "are made inside it, and the sample grids are written")
     ap.add_argument("--save-every", type=int, default=0)
+    ap.add_argument("--fid-every", type=int, default=0, help="with eval_fid > 0 in the config: rank 0 prints FID every N "
+                    "iterations (0: never)")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -227,6 +256,9 @@ def main(argv=None, synth_pairs=None):
         tests = held_out_loaders(config, None if args.mask_list_a else (args.data_root or config.get("data_root")), b, ns, nw)
         displays = (display_batch(loader_a, n), display_batch(loader_b, n)) + \
             ((display_batch(tests[0], n), display_batch(tests[1], n)) if tests else (None, None))
+    fid = None
+    if int(config.get("eval_fid") or 0) > 0 and args.fid_every > 0 and local_rank == 0:
+        fid = build_fid(config)
     it, t0 = 0, time.perf_counter()
     while it < args.iters:
         for batch_a, batch_b in zip(loader_a, loader_b):
@@ -236,6 +268,8 @@ def main(argv=None, synth_pairs=None):
             run_iteration(trainer, config, it, (x_a, x_b, m_a, m_b), synth_pairs)
             if displays is not None:
                 write_samples(trainer, config, it, displays, image_directory, local_rank)
+            if fid is not None and fid_due(config, it, args.fid_every):
+                print("iteration %d  FID %.4f" % (it + 1, evaluate_fid(trainer, fid)))
             it += 1
             if checkpoint_directory and args.save_every and it % args.save_every == 0 and local_rank == 0:
                 trainer.save(checkpoint_directory, it - 1)      # file names carry iterations + 1 (trainer.py:1337-1344)

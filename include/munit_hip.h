@@ -578,6 +578,51 @@ size_t munit_frechet_distance_workspace_bytes(int D);
 int munit_frechet_distance(const float* mu1, const float* sigma1, const float* mu2, const float* sigma2, int D, int iters,
                            float* out, void* ws, size_t ws_bytes, munit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Inception-v3 feature trunk of FID evaluation (scripts/inception_utils.py:27-85, WrapInception; DESIGN.md section 10.7;
+ * csrc/inception.hip).  Inference only, fp32, NHWC, asynchronous on `stream`; every argument check returns MUNIT_ERR_ARG
+ * before any launch: null pointers, x_ld / y_ld shorter than the slice, a stride other than 1 or 2, pads above
+ * (K - 1) / 2, output extents below 1, y overlapping x.
+ *
+ * Rectangular convolution: y = relu?(conv(x, w) + bias), KH x KW filter (each 1..15), one pad per axis, zero padding.
+ *   x: B x H x W pixels of Cin channels, pixel p at x + p * x_ld (x_ld >= Cin); y: B x Ho x Wo pixels of Cout channels,
+ *   pixel p at y + p * y_ld (y_ld >= Cout), Ho = (H + 2 pad_h - KH) / stride + 1.  The per-pixel strides let a layer read a
+ *   channel slice of a wider buffer and write into a channel slice of a concatenated output; the channels of a pixel
+ *   outside the slices are neither read nor written.  x and y must lie in different buffers: the overlap check compares
+ *   the whole byte spans from the first to the last word of each slice, so two disjoint channel slices interleaved in one
+ *   buffer are refused as overlapping.
+ *   wk: the weights as the k-major image [KH][KW][Cin][Cout] (row k = (kh * KW + kw) * Cin + ci holds the Cout values
+ *   w[co][ci][kh][kw]), built once when the layer is loaded.  bias: Cout values.
+ *   Arithmetic: implicit GEMM on v_mfma_f32_32x32x2_f32; every output is one k-ordered fmaf chain from 0, then + bias, then
+ *   ReLU; no split-K, no atomics.  The chain depends neither on the tile shape nor on B: an image's output is bitwise the
+ *   same in any batch.  tile: -1 lets the host choose (the answer of the tile query below: the 64 x 64 tile while 128 x 128
+ *   tiles would number fewer than the current device's compute units (asked once per device; 256 where none answers), else the 128-row tile that pads Cout least), 0 the 128 x 128 tile,
+ *   1 the 64 x 64 tile, 2 the 128 x 64 tile. */
+typedef struct munit_rect_desc {
+  int B, H, W, Cin, x_ld;
+  int Cout, y_ld;
+  int KH, KW, stride; /* stride 1 | 2 */
+  int pad_h, pad_w;
+  int relu;
+} munit_rect_desc;
+int munit_conv2d_rect_out_hw(const munit_rect_desc* d, int* Ho, int* Wo);
+int munit_conv2d_rect_tile(const munit_rect_desc* d); /* 0 | 1 | 2, or MUNIT_ERR_ARG */
+int munit_conv2d_rect_fwd(const munit_rect_desc* d, const float* x, const float* wk, const float* bias, float* y, int tile,
+                          munit_stream_t stream);
+/* The trunk's 3 x 3 pooling.  (Named `window`, not `pool`: the symbols matching munit_*pool* are the autograd pooling table of
+ * munit_amd.ops, one forward and one backward each, and this forward-only kernel is not one of them.)
+ * 3 x 3 window over B x H x W pixels of C channels with the same per-pixel strides (x and y in different buffers, as
+ * above): MUNIT_WINDOW_MAX is F.max_pool2d(3, stride, pad) (padding never wins: negative inputs survive), MUNIT_WINDOW_AVG is
+ * F.avg_pool2d(3, stride, pad) with count_include_pad = True: zero padding, the nine taps summed in window order (kh-major),
+ * the divisor always 9.  stride 1 | 2, pad 0 | 1, C % 4 == 0, x_ld and y_ld multiples of 4, x and y 16-byte aligned. */
+enum { MUNIT_WINDOW_MAX = 0, MUNIT_WINDOW_AVG = 1 };
+int munit_window3_fwd(const float* x, float* y, int B, int H, int W, int C, int x_ld, int y_ld, int mode, int stride,
+                      int pad, munit_stream_t stream);
+/* WrapInception.forward's first lines in one launch: v = ((x + 1) / 2 - mean_c) / std_c with the ImageNet statistics, then
+ * (unless H = W = 299) the bilinear resize with align_corners = True to 299 x 299.  x: B images of 3 x H x W, layout 0
+ * planar [B][3][H][W] or 1 interleaved [B][H][W][3], dense; y: [B][299][299][3]. */
+int munit_inception_input(const float* x, int layout, int B, int H, int W, float* y, munit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

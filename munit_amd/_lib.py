@@ -49,6 +49,15 @@ class GridSrc(Structure):
     _fields_ = [("data", c_void_p), ("n", c_int), ("channels", c_int), ("layout", c_int)]
 
 
+class RectDesc(Structure):
+    """munit_rect_desc."""
+    _fields_ = [("B", c_int), ("H", c_int), ("W", c_int), ("Cin", c_int), ("x_ld", c_int), ("Cout", c_int), ("y_ld", c_int),
+                ("KH", c_int), ("KW", c_int), ("stride", c_int), ("pad_h", c_int), ("pad_w", c_int), ("relu", c_int)]
+
+
+WINDOW = {"max": 0, "avg": 1}     # MUNIT_WINDOW_*
+RECT_TILES = ("128x128", "64x64", "128x64")  # tile argument / answer of munit_conv2d_rect_tile
+
 _P = c_void_p  # device pointers travel as integers
 _DESC = POINTER(ConvDesc)
 
@@ -173,6 +182,11 @@ SIGNATURES = {
     "munit_sqrt_newton_schulz": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "munit_frechet_distance_workspace_bytes": (c_size_t, [c_int]),
     "munit_frechet_distance": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "munit_conv2d_rect_out_hw": (c_int, [POINTER(RectDesc), POINTER(c_int), POINTER(c_int)]),
+    "munit_conv2d_rect_tile": (c_int, [POINTER(RectDesc)]),
+    "munit_conv2d_rect_fwd": (c_int, [POINTER(RectDesc), _P, _P, _P, _P, c_int, _P]),
+    "munit_window3_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "munit_inception_input": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 _lib = None

@@ -1,24 +1,29 @@
 """FID evaluation: the reference's scripts/inception_utils.py with its arithmetic on HIP kernels.
 
 Same names and parameter lists as the reference:
-  WrapInception(net).forward(x)                                inception_utils.py:27-85     (refuses, see below)
+  WrapInception(net).forward(x)                                inception_utils.py:27-85
   torch_cov(m, rowvar=False)                                   inception_utils.py:90-120
   sqrt_newton_schulz(A, numIters, dtype=None)                  inception_utils.py:125-140
   numpy_calculate_frechet_distance(mu1, sigma1, mu2, sigma2)   inception_utils.py:145-202   (host, scipy)
   torch_calculate_frechet_distance(mu1, sigma1, mu2, sigma2)   inception_utils.py:205-241
   accumulate_inception_activations(trainer, fid_loader, net)   inception_utils.py:246-254
-  load_inception_net(parallel=False)                           inception_utils.py:258-264
+  load_inception_net(parallel=False)                           inception_utils.py:258-264   (reads MUNIT_INCEPTION_CKPT)
   prepare_inception_metrics(inception_moment, parallel=False)  inception_utils.py:271-308   (+ net=, see below)
 
 The covariance, the 400 Newton-Schulz iterations on the 2048 x 2048 product and the distance itself run in
 libmunit_hip.so (csrc/fid.hip: munit_fid_moments, munit_sqrt_newton_schulz, munit_frechet_distance, all on the exact-fp32
 dense product munit_gemm_f32).  There is no CPU path for the `torch_*` functions: a host tensor raises.
 
-The one piece that is not here is the Inception-v3 trunk (WrapInception, inception_utils.py:27-85): its weights come from
-the network in the reference and its 1x7 / 7x1 convolutions have no kernel here yet.  The feature network is therefore an
-argument, `prepare_inception_metrics(..., net=f)`: any callable mapping a (B, 3, H, W) image batch in [-1, 1] to (B, D)
-fp32 device features.  DESIGN.md section 10.7.
+The feature network is the Inception-v3 trunk of munit_amd/inception.py (csrc/inception.hip): the input normalisation and
+resize, 94 convolutions with their batch norms folded in, the 3 x 3 pools and the final 8 x 8 mean, all HIP kernels.  Its
+weights are torchvision's `inception_v3` state dict; nothing here downloads it: load_inception_net reads the file named by
+the environment variable MUNIT_INCEPTION_CKPT.  The reference builds the network with transform_input=False, so the
+normalisation of WrapInception.forward is the only one -- there is no second one inside the network.  Any other feature
+network still plugs in as `prepare_inception_metrics(..., net=f)`: a callable mapping a (B, 3, H, W) image batch in [-1, 1]
+to (B, D) fp32 device features.  DESIGN.md section 10.7.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -27,21 +32,34 @@ from . import ops
 NEWTON_SCHULZ_ITERS = 400    # torch_calculate_frechet_distance, inception_utils.py:234
 
 
-_NO_TRUNK = (
-    "munit_amd.inception_utils: the Inception-v3 trunk is not part of this build (its pretrained weights come from the "
-    "network in the reference, and its 1x7 / 7x1 convolutions have no HIP kernel here yet).  Pass your feature network "
-    "as prepare_inception_metrics(inception_moment, net=f): a callable from a (B, 3, H, W) image batch in [-1, 1] to "
-    "(B, D) fp32 device features.")
+CKPT_ENV = "MUNIT_INCEPTION_CKPT"
+
+_NO_CKPT = (
+    "munit_amd.inception_utils: the Inception-v3 trunk needs torchvision's inception_v3 weights, and nothing here downloads "
+    "them: set the environment variable " + CKPT_ENV + " to the state-dict file (inception_v3_google-*.pth), or pass your "
+    "own feature network as prepare_inception_metrics(inception_moment, net=f): a callable from a (B, 3, H, W) image batch "
+    "in [-1, 1] to (B, D) fp32 device features.")
 
 
 class WrapInception(object):
-    """Placeholder under the reference's name for the wrapper of torchvision's inception_v3: it cannot be built here."""
+    """The reference's wrapper of torchvision's inception_v3 on HIP kernels.  net: a munit_amd.inception.InceptionV3, a
+    state-dict mapping, or any object with .state_dict() (a torchvision module).  forward(x): a (B, 3, H, W) fp32 device
+    batch in [-1, 1], planar or channels_last -> (B, 2048) fp32 pool features: ((x + 1) / 2 - mean) / std, the bilinear
+    resize (align_corners=True) to 299 x 299 unless x has that size, the trunk, the mean over the 8 x 8 map."""
 
     def __init__(self, net):
-        raise NotImplementedError(_NO_TRUNK)
+        from .inception import InceptionV3
+        self.net = net if isinstance(net, InceptionV3) else InceptionV3(net)
 
     def forward(self, x):
-        raise NotImplementedError(_NO_TRUNK)
+        if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != 3:
+            raise RuntimeError("munit_amd.inception_utils: WrapInception takes a (B, 3, H, W) batch on a HIP device (no CPU "
+                               "fallback exists); got %s" % (getattr(x, "device", type(x)),))
+        # straight into the trunk's own input buffer
+        pixels = ops.inception_input(x, out=self.net.input_buffer(x.device, x.shape[0]))
+        return ops.pixel_mean(self.net(pixels))
+
+    __call__ = forward
 
 
 def torch_cov(m, rowvar=False):
@@ -105,13 +123,25 @@ def accumulate_inception_activations(trainer, fid_loader, net):
 
 
 def load_inception_net(parallel=False):
-    raise NotImplementedError(_NO_TRUNK)
+    """WrapInception over the state dict in the file the environment variable MUNIT_INCEPTION_CKPT names (torchvision's
+    inception_v3_google-*.pth).  Never downloads and searches no cache: without the variable NotImplementedError, with a
+    missing file FileNotFoundError."""
+    if parallel:
+        raise NotImplementedError("munit_amd.inception_utils: parallel=True (nn.DataParallel over the feature network) is "
+                                  "not supported; evaluate on one device")
+    path = os.environ.get(CKPT_ENV)
+    if not path:
+        raise NotImplementedError(_NO_CKPT)
+    if not os.path.isfile(path):
+        raise FileNotFoundError("munit_amd.inception_utils: %s names %r, which is not a file" % (CKPT_ENV, path))
+    return WrapInception(torch.load(path, map_location="cpu", weights_only=True))
 
 
 def prepare_inception_metrics(inception_moment, parallel=False, net=None):
     """Returns get_inception_metrics(trainer, fid_loader, prints=True, use_torch=True) -> FID as a Python float, against
     the moments `mu` (D,) and `sigma` (D, D) stored in the .npz file `inception_moment`.  net: the feature network (the one
-    extension over the reference's parameter list; None asks for the built-in Inception trunk, which does not exist)."""
+    extension over the reference's parameter list; None: load_inception_net(), the Inception trunk with the weights
+    MUNIT_INCEPTION_CKPT names)."""
     if parallel:
         raise NotImplementedError("munit_amd.inception_utils: parallel=True (nn.DataParallel over the feature network) is "
                                   "not supported; evaluate on one device")

@@ -1684,3 +1684,153 @@ def frechet_distance(mu1, sigma1, mu2, sigma2, iters=400):
         _lib.check(lib.munit_frechet_distance(_p(mu1), _p(sigma1), _p(mu2), _p(sigma2), d, int(iters), _p(out), _p(ws),
                                               ws.numel(), _stream()), "frechet_distance")
     return out
+
+
+# ------------------------------------------------------------------------------------------
+# Inception-v3 feature trunk (include/munit_hip.h: munit_conv2d_rect_fwd ...; inception.hip; munit_amd/inception.py).
+# Inference only.  Activations are physical (B, H, W, C) fp32 tensors whose pixels are dense runs of C channels at one
+# per-pixel stride -- a whole buffer, or a channel slice `buf[..., lo:hi]` of a wider one, which is how the branches of a
+# Mixed block write into its concatenated output without a copy.
+# ------------------------------------------------------------------------------------------
+def _pixels(t, name):
+    """(B, H, W, C, per-pixel stride) of a (B, H, W, C) fp32 HIP tensor or channel slice of one."""
+    _require(t, name)
+    if t.dim() != 4 or min(t.shape) < 1:
+        raise RuntimeError("munit_amd: %s must be a non-empty (B, H, W, C) tensor, got shape %s" % (name, tuple(t.shape)))
+    b, h, w, c = t.shape
+    ld = t.stride(2) if w > 1 else (t.stride(1) if h > 1 else (t.stride(0) if b > 1 else c))
+    want = (h * w * ld, w * ld, ld, 1)
+    if ld < c or any(size > 1 and st != ws for size, st, ws in zip(t.shape, t.stride(), want)):
+        raise RuntimeError("munit_amd: %s (shape %s, strides %s) is not a channel slice of a dense (B, H, W, C) buffer"
+                           % (name, tuple(t.shape), t.stride()))
+    return b, h, w, c, ld
+
+
+def rect_weight_image(w):
+    """The k-major image (KH * KW * Cin, Cout) munit_conv2d_rect_fwd reads, from a (Cout, Cin, KH, KW) weight: a re-layout,
+    done once when a layer is loaded."""
+    cout, cin, kh, kw = w.shape
+    return w.permute(2, 3, 1, 0).contiguous().view(kh * kw * cin, cout)
+
+
+def conv2d_rect_launch(x, w_image, bias, kh, kw, stride=1, pad_h=0, pad_w=0, relu=True, out=None, tile=None):
+    """(launch, out): everything conv2d_rect checks and builds, done once; launch() enqueues the convolution on the current
+    stream with nothing left to do on the host but the C call.  For a plan that runs the same layer on the same buffers
+    again and again (munit_amd/inception.py); the tensors must stay alive and where they are."""
+    lib = _lib.load()
+    b, h, w, cin, x_ld = _pixels(x, "x")
+    _dense(w_image, "weight image", 2)
+    _dense(bias, "bias", 1)
+    cout = w_image.shape[1]
+    if w_image.shape[0] != kh * kw * cin or bias.shape[0] != cout:
+        raise RuntimeError("munit_amd.conv2d_rect: weight image %s / bias %s do not fit a %d x %d filter over %d channels"
+                           % (tuple(w_image.shape), tuple(bias.shape), kh, kw, cin))
+    d = _lib.RectDesc(b, h, w, cin, x_ld, cout, cout, kh, kw, int(stride), int(pad_h), int(pad_w), int(bool(relu)))
+    ho, wo = c_int(), c_int()
+    _lib.check(lib.munit_conv2d_rect_out_hw(byref(d), byref(ho), byref(wo)), "conv2d_rect_out_hw")
+    _same_device(x, w_image, bias, out)
+    if out is None:
+        with _on(x):
+            out = torch.empty((b, ho.value, wo.value, cout), dtype=torch.float32, device=x.device)
+    ob, oh, ow, oc, y_ld = _pixels(out, "out")
+    if (ob, oh, ow, oc) != (b, ho.value, wo.value, cout):
+        raise RuntimeError("munit_amd.conv2d_rect: out is %s, the result %s" % (tuple(out.shape), (b, ho.value, wo.value, cout)))
+    d.y_ld = y_ld
+    fn, dref, t = lib.munit_conv2d_rect_fwd, byref(d), -1 if tile is None else _lib.RECT_TILES.index(tile)
+    px, pw_, pb, py, keep = _p(x), _p(w_image), _p(bias), _p(out), (x, w_image, bias, out, d)
+
+    def launch():
+        with _on(keep[0]):
+            rc = fn(dref, px, pw_, pb, py, t, _stream())
+        if rc:
+            _lib.check(rc, "conv2d_rect_fwd")
+
+    return launch, out
+
+
+def conv2d_rect(x, w_image, bias, kh, kw, stride=1, pad_h=0, pad_w=0, relu=True, out=None, tile=None):
+    """relu?(conv(x, w) + bias) for a kh x kw filter (munit_conv2d_rect_fwd).  x: (B, H, W, Cin) pixels (see above); w_image:
+    rect_weight_image of the weight; bias (Cout,); out: (B, Ho, Wo, Cout) pixels to write into, allocated dense when None;
+    a slice of another buffer than x's (the library compares whole byte spans: slices interleaved in one buffer are refused).
+    tile: None lets the library choose, "128x128" / "64x64" / "128x64" forces a tile shape.  Returns out."""
+    launch, out = conv2d_rect_launch(x, w_image, bias, kh, kw, stride, pad_h, pad_w, relu, out, tile)
+    launch()
+    return out
+
+
+def conv2d_rect_tile(b, h, w, cin, cout, kh, kw, stride=1, pad_h=0, pad_w=0):
+    """The tile shape the library chooses for a layer ("128x128", "64x64" or "128x64")."""
+    d = _lib.RectDesc(b, h, w, cin, cin, cout, cout, kh, kw, int(stride), int(pad_h), int(pad_w), 0)
+    rc = _lib.load().munit_conv2d_rect_tile(byref(d))
+    if rc < 0:
+        _lib.check(rc, "conv2d_rect_tile")
+    return _lib.RECT_TILES[rc]
+
+
+def window3_launch(x, mode, stride, pad, out=None):
+    """(launch, out) of window3, as conv2d_rect_launch."""
+    lib = _lib.load()
+    b, h, w, c, x_ld = _pixels(x, "x")
+    ho, wo = (h + 2 * pad - 3) // stride + 1, (w + 2 * pad - 3) // stride + 1
+    _same_device(x, out)
+    if out is None:
+        with _on(x):
+            out = torch.empty((b, max(ho, 1), max(wo, 1), c), dtype=torch.float32, device=x.device)
+    ob, oh, ow, oc, y_ld = _pixels(out, "out")
+    if ho >= 1 and wo >= 1 and (ob, oh, ow, oc) != (b, ho, wo, c):
+        raise RuntimeError("munit_amd.window3: out is %s, the result %s" % (tuple(out.shape), (b, ho, wo, c)))
+    fn, px, py, keep = lib.munit_window3_fwd, _p(x), _p(out), (x, out)
+    args = (b, h, w, c, x_ld, y_ld, _lib.WINDOW[mode], int(stride), int(pad))
+
+    def launch():
+        with _on(keep[0]):
+            rc = fn(px, py, *args, _stream())
+        if rc:
+            _lib.check(rc, "window3_fwd")
+
+    return launch, out
+
+
+def window3(x, mode, stride, pad, out=None):
+    """3 x 3 max / average window over (B, H, W, C) pixels (munit_window3_fwd): mode "max" is F.max_pool2d(3, stride, pad),
+    "avg" F.avg_pool2d(3, stride, pad) with the divisor always 9.  out as in conv2d_rect."""
+    launch, out = window3_launch(x, mode, stride, pad, out)
+    launch()
+    return out
+
+
+def inception_input(x, out=None):
+    """((x + 1) / 2 - mean) / std and the bilinear resize (align_corners=True) to 299 x 299 of a (B, 3, H, W) batch, planar-
+    or interleaved-dense in memory (read from the strides; anything else is refused, not copied): (B, 299, 299, 3) pixels
+    (munit_inception_input), written into `out` (dense, that shape) when given."""
+    lib = _lib.load()
+    _require(x, "image batch")
+    if x.dim() != 4 or x.shape[1] != 3 or min(x.shape) < 1:
+        raise RuntimeError("munit_amd.inception_input: a (B >= 1, 3, H, W) batch is expected, got %s" % (tuple(x.shape),))
+    layout = _grid_layout(x)
+    if layout is None:
+        raise RuntimeError("munit_amd.inception_input: the batch (shape %s, strides %s) is neither planar- nor "
+                           "interleaved-dense in memory" % (tuple(x.shape), x.stride()))
+    b, _, h, w = x.shape
+    if out is not None:
+        _dense(out, "out", 4)
+        _same_device(x, out)
+        if tuple(out.shape) != (b, 299, 299, 3):
+            raise RuntimeError("munit_amd.inception_input: out is %s, the result %s" % (tuple(out.shape), (b, 299, 299, 3)))
+    with _on(x):
+        if out is None:
+            out = torch.empty((b, 299, 299, 3), dtype=torch.float32, device=x.device)
+        _lib.check(lib.munit_inception_input(_p(x), layout, b, h, w, _p(out), _stream()), "inception_input")
+    return out
+
+
+def pixel_mean(x):
+    """Mean over the H x W pixels of dense (B, H, W, C) pixels: (B, C) (munit_gap_fwd: four interleaved partial sums over
+    the pixels, added in order, divided by H * W)."""
+    lib = _lib.load()
+    _dense(x, "pixels", 4)
+    b, h, w, c = x.shape
+    with _on(x):
+        out = torch.empty((b, c), dtype=torch.float32, device=x.device)
+        _lib.check(lib.munit_gap_fwd(_p(x), _p(out), b, h * w, c, _stream()), "gap_fwd")
+    return out
