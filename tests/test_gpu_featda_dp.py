@@ -29,8 +29,9 @@ DEV = "cuda:0"
 EPS, MOM = 1e-5, 0.1
 # (W, R_local, C): all variance between the ranks (the per-rank batch-1 case); a single partial block; rows that are no
 # multiple of the block's row lanes with more than one partial block; several partial blocks; a channel mean of 100 against
-# unit spread (the two-float mean and the merge)
-CASES = [(2, 1, 4), (2, 7, 64), (3, 257, 128), (2, 1024, 64), (4, 33, 128)]
+# unit spread (the two-float mean and the merge); C > 256, where the row, combine and finish kernels (one thread per
+# channel) run over several blocks: C = 1024 at one row lane (4 blocks), and C = 512 (2 blocks) with 3 partial blocks of 11 rows
+CASES = [(2, 1, 4), (2, 7, 64), (3, 257, 128), (2, 1024, 64), (4, 33, 128), (2, 5, 1024), (3, 33, 512)]
 
 
 def _p(t):
@@ -169,7 +170,7 @@ def test_a_combine_over_one_rank_is_not_the_joined_batch():
     assert float((b.rstd[0][:4].cpu().double() / rrstd).min()) > 10.0
 
 
-@pytest.mark.parametrize("wrc", [(2, 7, 64), (3, 257, 128)])
+@pytest.mark.parametrize("wrc", [(2, 7, 64), (3, 257, 128), (2, 5, 1024)])
 def test_guard_bands_cross_rank_batchnorm(wrc):
     lib = _lib.load()
     w, r, c = wrc
