@@ -212,6 +212,13 @@ int munit_instnorm_bwd(const float* x, const float* dy, const float* stats, floa
                        int C, const float* adain, float* d_adain, int ad_ld, int w_off, int b_off,
                        int relu, void* ws, size_t ws_bytes, munit_stream_t stream);
 
+/* The kernels a forward or backward at (B, HW, C) of MUNIT_DTYPE_* tensors runs, asked of the host predicates the launches
+ * act on: 0 = flat (statistics, fold, apply), 1 = channel-sliced (statistics, apply), 2 = one-pass forward (one kernel that
+ * keeps the plane of a (sample, 16-channel group) in registers: fp32, C % 64 == 0, at most 16 splits of at most 256 pixels;
+ * the backward of such a shape runs the channel-sliced kernels).  -1 for dimensions the entry points refuse.  All routes give
+ * the same bits and leave the same split partials in the workspace. */
+int munit_instnorm_route(int B, int HW, int C, int dtype);
+
 /* bf16-storage forms (x, y, dy, dx, residual are bf16 tensors; statistics, AdaIN parameters and their gradients fp32) */
 int munit_instnorm_fwd_bf16(const void* x, void* y, float* stats, int B, int HW, int C,
                             const float* adain, int ad_ld, int w_off, int b_off, const void* residual,

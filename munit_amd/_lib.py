@@ -91,6 +91,7 @@ SIGNATURES = {
     "munit_linear_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P, c_size_t, _P]),
     "munit_act_bwd": (c_int, [c_int, c_float, _P, _P, _P, c_size_t, _P]),
     "munit_instnorm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "munit_instnorm_route": (c_int, [c_int, c_int, c_int, c_int]),
     "munit_instnorm_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int,
                                    c_float, _P, c_size_t, _P]),
     "munit_instnorm_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int,

@@ -1,7 +1,8 @@
 // Normalisation layers of the MUNIT generator, NHWC, fp32, HBM-bound:
 //   instance norm / AdaIN  (networks.py:657, 810-848)   per-(b,c) stats over H*W
 //   MUNIT LayerNorm        (networks.py:851-878)        per-sample stats over C*H*W
-// Every pass is two kernels: a partial-statistics kernel over (pixel split, sample) blocks
+// (The forward of the residual trunk's instance norm / AdaIN is ONE kernel that keeps the plane in registers: "One-pass form".)
+// Every other pass is two kernels: a partial-statistics kernel over (pixel split, sample) blocks
 // -- per-thread fp32 accumulators over a channel quad, wavefront/LDS reduction across the
 // pixel lanes of the block -- and an apply kernel that folds the split partials in its
 // prologue (kept in LDS) and streams float4s.  Sums are taken relative to a pivot (the
@@ -467,6 +468,166 @@ __global__ __launch_bounds__(NT) void in_bwd_apply_sliced_kernel(const T* __rest
 }
 
 // ---------------------------------------------------------------------------------------
+// One-pass form (fp32, C a multiple of 64, at most 16 splits of at most 256 pixels -- onepass_split below): a block =
+// (sample, 16 consecutive channels) holds its whole plane in registers, at most 4096 pixels x 64 B = 256 KB, half a CU's
+// register file.  x is read ONCE: the statistics are reduced from the registers and y is computed from them, so the forward
+// moves 2 tensors instead of 3 in one launch instead of two.
+// A wave is one pixel split: thread = (split s, pixel lane pl of 16, channel quad q of 4) owns pixels s * per + pl + 16 j of
+// its quad, the assignment of in_stats_kernel under make_lay(SLICE).  Per-thread sums, the in-order sum over the pixel lanes,
+// the split partials (written to the workspace where the two-pass form leaves them) and fold_slice's order over the splits are
+// those of the two-pass kernels, expression for expression: y and stats are bitwise the same.
+// FORWARD ONLY.  The same kernel for the backward (g = dy * act' held in registers, 1024 threads; or x and g held, 8-channel
+// blocks of 512 threads) is 15 % faster than the sliced pair when it runs alone and 25 % slower inside the step, 1.3 - 2 ms
+// per step: a block that needs a whole CU's registers waits for one beside the backward-weight kernels of the other streams,
+// where the small blocks of the sliced pair slip in.
+// ---------------------------------------------------------------------------------------
+constexpr int OP_CH = 16;                   // channels of a block
+constexpr int OP_Q = OP_CH / 4;             // its channel quads
+constexpr int OP_PL = 16;                   // pixel lanes of a split
+constexpr int OP_NV = 16;                   // float4 values a thread holds per tensor
+constexpr int OP_MAX_SPLIT = 16;            // splits of a block
+constexpr int OP_TPS = OP_PL * OP_Q;        // threads of a split
+constexpr int OP_NT = OP_TPS * OP_MAX_SPLIT;
+constexpr int OP_LINE = 32 / OP_CH;         // blocks that share a 128-byte line of a pixel
+static_assert(OP_TPS == 4 * OP_CH, "onepass_fold: four split groups of OP_CH threads in the smallest block");
+
+// (sample, first channel) of a block.  OP_CH channels are a part of a 128-byte line and the neighbouring groups read the rest:
+// the groups of a line are blocks i, i + 8, ..., which land on the same XCD (blocks go round the 8 XCDs in order) at the same
+// time, so the line crosses the fabric once.  A last group of fewer than 8 * OP_LINE blocks keeps its order.
+__device__ inline void onepass_block(int C, int& b, int& c0) {
+  constexpr int GRP = 8 * OP_LINE;
+  const int i = blockIdx.x, grp = i / GRP, r = i % GRP;
+  const bool full = (grp + 1) * GRP <= (int)gridDim.x;
+  const int cg = grp * GRP + (full ? ((r & 7) * OP_LINE + (r >> 3)) : r);
+  const int G = C / OP_CH;
+  b = cg / G;
+  c0 = (cg % G) * OP_CH;
+}
+
+// The sums of a split's pixel lanes, added in lane order as in_stats_kernel's pl == 0 threads add them, written to the
+// workspace and kept in part[split][2][OP_CH].  v1, v2: a thread's sums over its own pixels of its quad's four channels.
+__device__ inline void onepass_lanes(const double (&v1)[4], const double (&v2)[4], double* __restrict__ lane,
+                                     double (*part)[2][OP_CH], double* __restrict__ partial, int b, int C, int nsplit, int c0) {
+  const int s = threadIdx.x / OP_TPS, ln = threadIdx.x % OP_TPS;
+  double* mine = lane + (s * OP_PL) * OP_CH;   // [pl][OP_CH channels] of this split
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) mine[ln * 4 + e] = which ? v2[e] : v1[e];   // ln * 4 = pl * OP_CH + q * 4
+    __syncthreads();
+    if (ln < OP_CH) {
+      double a = mine[ln];
+      for (int l = 1; l < OP_PL; ++l) a += mine[l * OP_CH + ln];
+      partial[((long long)(b * nsplit + s) * 2 + which) * C + c0 + ln] = a;
+      part[s][which][ln] = a;
+    }
+    __syncthreads();
+  }
+}
+
+// fold_slice over part[][][]: valid in threads < OP_CH (channel c0 + threadIdx.x)
+__device__ inline void onepass_fold(const double (*part)[2][OP_CH], int nsplit, double (*red)[OP_CH][2], double& s1, double& s2) {
+  const int cl = threadIdx.x % OP_CH, g = threadIdx.x / OP_CH;
+  s1 = 0.0;
+  s2 = 0.0;
+  if (g < 4) {
+    for (int k = g; k < nsplit; k += 4) {
+      s1 += part[k][0][cl];
+      s2 += part[k][1][cl];
+    }
+    if (g > 0) {
+      red[g - 1][cl][0] = s1;
+      red[g - 1][cl][1] = s2;
+    }
+  }
+  __syncthreads();
+  if (g == 0) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      s1 += red[j][cl][0];
+      s2 += red[j][cl][1];
+    }
+  }
+}
+
+__global__ __launch_bounds__(OP_NT) void in_onepass_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                           double* __restrict__ partial, float* __restrict__ stats, int HW,
+                                                           int C, int nsplit, const float* __restrict__ adain, int ad_ld,
+                                                           int w_off, int b_off, float eps,
+                                                           const float* __restrict__ residual, int relu) {
+  __shared__ double lane[OP_MAX_SPLIT * OP_PL * OP_CH];
+  __shared__ double part[OP_MAX_SPLIT][2][OP_CH];
+  __shared__ double red[3][OP_CH][2];
+  __shared__ __attribute__((aligned(16))) float scale[OP_CH], shift[OP_CH];
+  int b, c0;
+  onepass_block(C, b, c0);
+  const int s = threadIdx.x / OP_TPS, pl = (threadIdx.x % OP_TPS) / OP_Q, q = threadIdx.x % OP_Q;
+  const int per = (HW + nsplit - 1) / nsplit;
+  const int p0 = s * per + pl, p1 = min(HW, s * per + per);
+  const long long plane = (long long)b * HW * C + c0;
+  const unsigned to = (unsigned)(p0 * C + q * 4);   // the thread's offset; j adds a uniform OP_PL * C to the base pointer
+  const float* xb = x + plane;
+  const float* rb = residual != nullptr ? residual + plane : nullptr;
+  f32x4 v[OP_NV];
+#pragma unroll
+  for (int j = 0; j < OP_NV; ++j) {
+    const int p = p0 + OP_PL * j;
+    v[j] = p < p1 ? ld4(xb + j * OP_PL * C + to) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const f32x4 piv = ld4(xb + q * 4);
+  double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < OP_NV; ++j) {
+    if (p0 + OP_PL * j < p1) {
+      const f32x4 d = v[j] - piv;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s1[e] += (double)d[e];
+        s2[e] += (double)d[e] * (double)d[e];
+      }
+    }
+  }
+  onepass_lanes(s1, s2, lane, part, partial, b, C, nsplit, c0);
+  double t1, t2;
+  onepass_fold(part, nsplit, red, t1, t2);
+  if (threadIdx.x < OP_CH) {   // the arithmetic of in_apply_sliced_kernel
+    const int c = c0 + threadIdx.x;
+    const double inv_n = 1.0 / (double)HW;
+    const double d = t1 * inv_n;
+    const float mean = (float)((double)x[plane + threadIdx.x] + d);   // pivot = first pixel of the plane
+    double var = t2 * inv_n - d * d;
+    var = var > 0.0 ? var : 0.0;
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    float w = 1.f, bb = 0.f;
+    if (adain != nullptr) {
+      w = adain[(long long)b * ad_ld + w_off + c];
+      bb = adain[(long long)b * ad_ld + b_off + c];
+    }
+    stats[((long long)b * C + c) * 2] = mean;
+    stats[((long long)b * C + c) * 2 + 1] = rstd;
+    scale[threadIdx.x] = rstd * w;
+    shift[threadIdx.x] = bb - mean * rstd * w;
+  }
+  __syncthreads();
+  const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + q * 4);
+  const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + q * 4);
+  float* yb = y + plane;
+#pragma unroll
+  for (int j = 0; j < OP_NV; ++j) {
+    const int p = p0 + OP_PL * j;
+    if (p < p1) {
+      f32x4 r = v[j] * sc + sh;
+      if (relu) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = norm_act(r[e], relu);
+      }
+      if (rb != nullptr) r += ld4(rb + j * OP_PL * C + to);
+      st4(yb + j * OP_PL * C + to, r);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // MUNIT LayerNorm
 // ---------------------------------------------------------------------------------------
 __device__ inline double block_sum(double v, double* red) {
@@ -702,6 +863,19 @@ size_t in_partial_bytes(int B, int C) { return align_up((size_t)B * MAX_SPLIT * 
 bool in_sliced(int C) { return C % SLICE == 0 && !MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_SLICED_NORM"); }
 // pixel splits of the sliced grid: pick_split's block count shared out over the C / 64 slices
 int sliced_split(int B, int HW, int C) { return std::max(1, pick_split(B, HW) / (C / SLICE)); }
+// Splits (= waves of a block) of the one-pass form, 0 where a pass keeps its two kernels: fp32 tensors on the sliced path
+// whose split is at most 16 x 16 pixels per thread quad -- planes of up to 4096 pixels, and fewer where a large batch or
+// many slices leave the sliced grid fewer than HW / 256 splits.
+int onepass_split(int B, int HW, int C, bool f32) {
+  if (!f32 || !in_sliced(C) || MUNIT_ENV_FLAG("MUNIT_DEBUG_NO_ONEPASS_NORM")) return 0;
+  const int ns = sliced_split(B, HW, C);
+  return (ns <= OP_MAX_SPLIT && cdiv(HW, ns) <= OP_PL * OP_NV) ? ns : 0;
+}
+}
+extern "C" int munit_instnorm_route(int B, int HW, int C, int dtype) {
+  if (B <= 0 || HW <= 0 || C <= 0 || C % 4 != 0 || C > MAX_NORM_C) return -1;
+  if (onepass_split(B, HW, C, dtype == MUNIT_DTYPE_F32)) return 2;
+  return in_sliced(C) ? 1 : 0;
 }
 // [split partials (fp64)][per-(sample, channel) coefficients of the apply kernels: 6 floats]
 extern "C" size_t munit_instnorm_workspace_bytes(int B, int HW, int C) {
@@ -721,6 +895,14 @@ int instnorm_fwd_t(const T* x, T* y, float* stats, int B, int HW, int C, const f
   }
   hipStream_t st = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws);
+  if constexpr (std::is_same<T, float>::value) {
+    if (const int ns = onepass_split(B, HW, C, true)) {
+      hipLaunchKernelGGL(in_onepass_kernel, dim3(B * (C / OP_CH)), dim3(OP_TPS * ns), 0, st, x, y, partial, stats, HW, C, ns, adain,
+                         ad_ld, w_off, b_off, eps, residual, relu);
+      MUNIT_CHECK_LAUNCH("in_onepass");
+      return MUNIT_OK;
+    }
+  }
   if (in_sliced(C)) {
     const int ns = sliced_split(B, HW, C);
     const Lay Ls = make_lay(SLICE);
