@@ -316,6 +316,46 @@ int munit_nsgan_fwd(const float* const* x, const size_t* n, const float* target,
                     void* ws, size_t ws_bytes, munit_stream_t stream);
 int munit_nsgan_bwd(const float* const* x, const size_t* n, const float* target, int nseg, const float* gout,
                     float* const* dx, munit_stream_t stream);
+/* ------------------------------------------------------------------------------------
+ * Spectral normalisation (dis.norm: sn; SpectralNorm, scripts/networks.py:885-942).  A normalised convolution runs as the
+ * ordinary convolution with weight_bar (no bias, no activation) followed by the scale-bias-activation below:
+ * conv(x, W / sigma) = conv(x, W) / sigma, so no weight image depends on sigma and sigma never reaches the host.
+ *
+ * Power iteration over ALL normalised layers of a module in one call (four launches, no grid synchronisation): items_dev is a
+ * DEVICE array of n descriptors.  Per layer, with W = weight_bar viewed (O, I * KH * KW):
+ *   v <- l2n(W^T u),  u <- l2n(W v),  sigma = u . (W v),   l2n(a) = a / (|a| + 1e-12);
+ * sigma[2 * slot] = sigma and sigma[2 * slot + 1] = 1 / sigma.  w is read in place in its [O][KH][KW][I] memory order; v is
+ * kept in the reference's column order (i, kh, kw), so state dicts interchange.  max_O / max_N: the largest O and I * KH * KW of
+ * the table (they size the grid and the workspace; a layer beyond them is left untouched); max_N <= 8192.  fp32 with fp32
+ * accumulation, every sum in a fixed order: two calls on the same state are bitwise equal. */
+typedef struct munit_sn_item {
+  const float* w; /* weight_bar */
+  float* u;       /* O */
+  float* v;       /* I * KH * KW */
+  int O, KH, KW, I;
+  int slot;
+} munit_sn_item;
+size_t munit_sn_power_iter_workspace_bytes(int n, int max_O, int max_N);
+int munit_sn_power_iter(const munit_sn_item* items_dev, int n, int max_O, int max_N, float* sigma, void* ws, size_t ws_bytes,
+                        munit_stream_t stream);
+/* y = act(raw * *inv_sigma + bias[c]) over npix pixels of C channels (NHWC fp32); bias nullable.  inv_sigma: the layer's
+ * device slot (sigma + 2 * slot + 1). */
+int munit_sn_act_fwd(const float* raw, const float* inv_sigma, const float* bias, float* y, size_t npix, int C, int act,
+                     float slope, munit_stream_t stream);
+/* Backward of the above from dy and y: dz = dy * act'(y); draw = dz * *inv_sigma (what the convolution's backward receives,
+ * so that its backward-weight yields G = wgrad(x, dZ / sigma)); db[c] = beta * db[c] + sum dz (beta 0 or 1; 0 never reads db);
+ * coef[0] = sum dz * raw * inv_sigma^2 = <G, W> / sigma, the coefficient of the rank-1 correction below.  Two deterministic
+ * stages through ws.  db and coef both NULL (the layer's parameters take no gradient): draw alone, one launch, raw and ws
+ * unused. */
+size_t munit_sn_act_bwd_workspace_bytes(size_t npix, int C);
+int munit_sn_act_bwd(const float* dy, const float* y, const float* raw, const float* inv_sigma, float* draw, float* db,
+                     float beta, float* coef, size_t npix, int C, int act, float slope, void* ws, size_t ws_bytes,
+                     munit_stream_t stream);
+/* dw = beta * dw - coef[0] * u (x) v in the weight's memory order ([O][KH][KW][I]; v in the reference's column order), beta 0
+ * or 1: the sigma term of d weight_bar, taken with the u, v of the time of the call (the reference's `.data` swaps leave
+ * autograd with the latest pair for every pass). */
+int munit_sn_grad_fix(float* dw, const float* coef, const float* u, const float* v, int O, int KH, int KW, int I, float beta,
+                      munit_stream_t stream);
 /* out = sum_i w[i] * *(terms[i]); n <= 32; terms are device scalars, w host floats. */
 int munit_weighted_sum(const float* const* terms, const float* w, int n, float* out,
                        munit_stream_t stream);

@@ -33,6 +33,12 @@ class PrepItem(Structure):
                 ("kind", c_int), ("ps", c_int), ("bf16", c_int)]
 
 
+class SnItem(Structure):
+    """munit_sn_item."""
+    _fields_ = [("w", c_void_p), ("u", c_void_p), ("v", c_void_p), ("O", c_int), ("KH", c_int), ("KW", c_int), ("I", c_int),
+                ("slot", c_int)]
+
+
 class ImageDesc(Structure):
     """munit_image_desc."""
     _fields_ = [("src_off", ctypes.c_longlong), ("src_h", c_int), ("src_w", c_int), ("rs_h", c_int), ("rs_w", c_int),
@@ -126,7 +132,13 @@ SIGNATURES = {
     "munit_nsgan_workspace_bytes": (c_size_t, [c_int]),
     "munit_nsgan_fwd": (c_int, [POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float), c_int, _P, _P, _P, c_size_t, _P]),
     "munit_nsgan_bwd": (c_int, [POINTER(c_void_p), POINTER(c_size_t), POINTER(c_float), c_int, _P, POINTER(c_void_p), _P]),
-    "munit_weighted_sum": (c_int, [POINTER(c_void_p), POINTER(c_float), c_int, _P, _P]),
+    "munit_sn_power_iter_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "munit_sn_power_iter": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "munit_sn_act_fwd": (c_int, [_P, _P, _P, _P, c_size_t, c_int, c_int, c_float, _P]),
+    "munit_sn_act_bwd_workspace_bytes": (c_size_t, [c_size_t, c_int]),
+    "munit_sn_act_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_float, _P, c_size_t, c_int, c_int, c_float, _P, c_size_t, _P]),
+    "munit_sn_grad_fix": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "munit_weighted_sum":(c_int, [POINTER(c_void_p), POINTER(c_float), c_int, _P, _P]),
     "munit_adam_step": (c_int, [_P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int,
                                 _P]),
     "munit_extraadam_step": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double,

@@ -52,6 +52,56 @@ class Conv2d(nn.Module):
                                                       self.stride)
 
 
+def l2normalize(v, eps=1e-12):
+    """networks.py:881-882."""
+    return v / (v.norm() + eps)
+
+
+class SpectralNorm(nn.Module):
+    """networks.py:885-942 around a Conv2d (power_iterations 1, the reference's only use).  State as in the reference: the
+    wrapped module owns `bias`, `weight_u` (O,), `weight_v` (I * kh * kw, in the reference's (i, kh, kw) column order) and
+    `weight_bar` (O, I, kh, kw), in that order, and no `weight` -- so weights_init passes these layers by, as it does there
+    (the reference's inner convolution has no `weight` attribute before its first forward).  weight_u / weight_v take no
+    gradient and are drawn after the convolution's own parameters: u ~ N(0, 1), then v, both l2-normalised.
+
+    Every forward advances u and v by one power iteration, also under no_grad and in eval(), and runs
+    act(conv(pad(x), weight_bar) / sigma + bias): the convolution kernels and their prepared weight images see weight_bar
+    alone.  The owner of several wrappers (MsImageDis) iterates all of them in one call and hands each its slot through
+    `assign`; a wrapper called on its own iterates itself."""
+
+    def __init__(self, module):
+        super().__init__()
+        if not isinstance(module, Conv2d):
+            raise NotImplementedError("munit_amd.SpectralNorm wraps a munit_amd Conv2d (LinearBlock's norm='sn' is not "
+                                      "reachable from any config)")
+        self.module = module
+        w = module.weight
+        height, width = w.shape[0], w[0].numel()
+        u = nn.Parameter(l2normalize(torch.empty(height).normal_(0, 1)), requires_grad=False)
+        v = nn.Parameter(l2normalize(torch.empty(width).normal_(0, 1)), requires_grad=False)
+        w_bar = nn.Parameter(w.data)
+        del module._parameters["weight"]
+        module.register_parameter("weight_u", u)
+        module.register_parameter("weight_v", v)
+        module.register_parameter("weight_bar", w_bar)
+        self.__dict__["_inv_sigma"] = None       # this forward's 1 / sigma (a device scalar), set by assign()
+
+    def layer(self):
+        m = self.module
+        return m.weight_bar, m.weight_u, m.weight_v
+
+    def assign(self, inv_sigma):
+        self.__dict__["_inv_sigma"] = inv_sigma
+
+    def forward(self, x, pad=0, pad_type="zero", act="none", slope=0.2):
+        m = self.module
+        inv_sigma, self.__dict__["_inv_sigma"] = self._inv_sigma, None
+        if inv_sigma is None:
+            inv_sigma = ops.sn_power_iter(*ops.sn_table([self.layer()]))[1:2]
+        raw = ops.conv2d(x, m.weight_bar, None, m.stride, pad, pad_type, False, "none")
+        return ops.sn_act(raw, m.weight_bar, m.bias, m.weight_u, m.weight_v, inv_sigma, act, slope)
+
+
 class Linear(nn.Module):
     """Stands in for nn.Linear (networks.py:712)."""
 
@@ -168,10 +218,10 @@ class Conv2dBlock(nn.Module):
             self.norm = LayerNorm(norm_dim)
         elif norm == "adain":
             self.norm = AdaptiveInstanceNorm2d(norm_dim)
-        elif norm == "none":
+        elif norm == "none" or norm == "sn":
             self.norm = None
-        elif norm in ("bn", "sn"):
-            raise NotImplementedError("munit_amd: norm=%r is outside the MUNIT hot path (configs use none/in/ln/adain)"
+        elif norm == "bn":
+            raise NotImplementedError("munit_amd: norm=%r is outside the MUNIT hot path (configs use none/in/ln/adain/sn)"
                                       % norm)
         else:
             assert 0, "Unsupported normalization: {}".format(norm)
@@ -181,10 +231,17 @@ class Conv2dBlock(nn.Module):
             assert 0, "Unsupported activation: {}".format(activation)
         self.activation = activation
         self.conv = Conv2d(input_dim, output_dim, kernel_size, stride, bias=self.use_bias)
+        self.sn = norm == "sn"
+        if self.sn:                 # networks.py:684-689: the convolution inside SpectralNorm, keys conv.module.*
+            self.conv = SpectralNorm(self.conv)
 
     def forward(self, x, upsample=False, residual=None, out_dtype=None, link_open=None, link_close=None):
         """link_open / link_close: the ops.ResidualLink of the ResBlock this block opens (its convolution's backward-data
         adds the skip gradient) / closes (its norm's backward parks the skip gradient instead of returning it)."""
+        if self.sn:
+            if upsample or residual is not None or link_open is not None or (out_dtype not in (None, torch.float32)):
+                raise NotImplementedError("munit_amd: a spectrally normalised block is a plain fp32 discriminator layer")
+            return self.conv(x, self.pad.padding, self.pad.kind, self.activation)
         if self.norm is None:
             y = self.conv(x, self.pad.padding, self.pad.kind, upsample, self.activation, out_dtype=out_dtype, link=link_open)
             if residual is not None:
@@ -555,6 +612,10 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         self.cnns = nn.ModuleList()
         for _ in range(self.num_scales):
             self.cnns.append(self._make_net())
+        # dis.norm sn: the wrappers of all scales in module order, iterated by ONE call at the top of forward(); the descriptor
+        # table lives on the device and is rebuilt when a parameter has moved (.to(device), the optimizer's bind)
+        self.__dict__["_sn"] = [m for m in self.modules() if isinstance(m, SpectralNorm)]
+        self.__dict__["_sn_table"] = None
         # called at the top of forward() -- calc_dis_loss / calc_gen_loss reach forward() directly, as the reference's do
         # (networks.py:84-85, 104), so a module pre-hook would not see them
         self.__dict__["before_forward"] = None
@@ -585,6 +646,8 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
         if self.before_forward is not None:      # data parallel: order this stream behind a deferred optimizer step (follow)
             self.before_forward()
         x = ops.nhwc(x)
+        if self._sn:
+            self._sn_iterate()
         outputs = []
         for i, model in enumerate(self.cnns):
             h = x
@@ -595,13 +658,25 @@ class MsImageDis(_ApplyRefreshesImages, nn.Module):
                 x = self.downsample(x)
         return outputs
 
+    def _sn_iterate(self):
+        """One power iteration of every normalised layer (networks.py:899-911 runs it per layer inside each forward), and each
+        wrapper gets the 1 / sigma of this forward."""
+        layers = [m.layer() for m in self._sn]
+        key = tuple(t.data_ptr() for layer in layers for t in layer)
+        if self._sn_table is None or self._sn_table[0] != key:
+            self.__dict__["_sn_table"] = (key, ops.sn_table(layers))
+        sigma = ops.sn_power_iter(*self._sn_table[1])
+        for k, m in enumerate(self._sn):
+            m.assign(sigma[2 * k + 1:2 * k + 2])
+
     def _pair(self, first, second):
         """The discriminator's outputs for a (first -> 0, second -> 1) pair, as (outs, targets) of ops.lsgan_loss /
         ops.nsgan_loss.  BATCH_DIS_PAIR and equal shapes: one pass over [first; second] -- every layer of the discriminator
         is per-sample (no batch statistics), so the two halves of each output are exactly the reference's outs0 / outs1
         (networks.py:84-91) -- half the launches, and the small scales (16x16 ... 4x4 maps), which cannot fill the chip at
-        B = 8, cost about the same at 2 B; every target is the pair (0.0, 1.0).  Else two passes, outs0 + outs1."""
-        if BATCH_DIS_PAIR and first.shape == second.shape and first.dtype == second.dtype:
+        B = 8, cost about the same at 2 B; every target is the pair (0.0, 1.0).  Else two passes, outs0 + outs1: always under
+        dis.norm sn, where the second pass runs with the sigma of one more power iteration than the first."""
+        if BATCH_DIS_PAIR and not self._sn and first.shape == second.shape and first.dtype == second.dtype:
             nb = first.shape[0]
             n0 = len(ops.MASK_SINK) if ops.MASK_SINK is not None else 0
             outs = self.forward(torch.cat([ops.nhwc(first), ops.nhwc(second)], 0))

@@ -449,6 +449,7 @@ def join_side_streams():
     """Make the current stream wait for every backward-weight launched so far (call before the optimizer step)."""
     for (_, index), st in _SIDE.items():
         stream_wait(torch.cuda.current_stream(torch.device("cuda", index)), st)
+    _SN_PENDING.clear()
 
 
 FUSE_SKIP_GRAD = not os.environ.get("MUNIT_NO_FUSE_SKIP_GRAD")   # A/B switch of ResidualLink
@@ -562,7 +563,157 @@ def linear(x, weight, bias=None, act="none"):
     return y.reshape(b, n)
 
 
-_NORM_ACT = {False: 0, True: 1, None: 0, "none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
+# ------------------------------------------------------------------------------------------
+# spectral normalisation (dis.norm: sn; include/munit_hip.h: munit_sn_*)
+# ------------------------------------------------------------------------------------------
+# devices on which a rank-1 correction launched on the backward-weight side stream may still be reading u / v: the next power
+# iteration (which rewrites them) waits for that stream first
+_SN_PENDING = set()
+
+
+def sn_table(layers):
+    """Descriptor table of a module's normalised layers.  layers: [(weight_bar (O, I, kh, kw) in channels_last memory,
+    weight_u (O,), weight_v (I * kh * kw,))]; layer k owns slot k of the sigma tensor.  Returns (device uint8 tensor of
+    munit_sn_item structs, n, largest O, largest I * kh * kw)."""
+    items, max_o, max_n = [], 0, 0
+    for slot, (w, u, v) in enumerate(layers):
+        _require(w, "weight_bar")
+        _require(u, "weight_u")
+        _require(v, "weight_v")
+        _same_device(w, u, v, layers[0][0])
+        o, i, kh, kw = w.shape
+        if not _is_nhwc(w) or not u.is_contiguous() or not v.is_contiguous():
+            raise RuntimeError("munit_amd.sn_table: weight_bar must be channels_last, weight_u / weight_v contiguous")
+        if u.numel() != o or v.numel() != i * kh * kw:
+            raise RuntimeError("munit_amd.sn_table: weight_u / weight_v do not fit weight_bar %s" % (tuple(w.shape),))
+        items.append(_lib.SnItem(w.data_ptr(), u.data_ptr(), v.data_ptr(), o, kh, kw, i, slot))
+        max_o, max_n = max(max_o, o), max(max_n, i * kh * kw)
+    n = len(items)
+    arr = (_lib.SnItem * n)(*items)
+    host = torch.frombuffer(bytearray(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr))), dtype=torch.uint8)
+    return host.to(layers[0][0].device), n, max_o, max_n
+
+
+def sn_power_iter(table, n, max_o, max_n):
+    """One power iteration of every layer of `table` (sn_table), in place on weight_u / weight_v, in four launches.  Returns
+    a fresh (2 n,) tensor: sigma of layer k at [2 k], 1 / sigma at [2 k + 1] -- a tensor per call, because the backward of a
+    pass needs the sigma of that pass after later forwards have moved on."""
+    lib = _lib.load()
+    dev = table.device
+    with _on(table):
+        if dev.index in _SN_PENDING:
+            stream_wait(torch.cuda.current_stream(dev), _side_stream(dev))
+            _SN_PENDING.discard(dev.index)
+        nbytes = lib.munit_sn_power_iter_workspace_bytes(n, max_o, max_n)
+        if not nbytes:
+            raise NotImplementedError("munit_amd.sn_power_iter: %d layers up to (%d, %d) are beyond the kernel (at most 8192 "
+                                      "columns Cin * kh * kw)" % (n, max_o, max_n))
+        sigma = torch.empty(2 * n, dtype=torch.float32, device=dev)
+        ws = workspace(nbytes, dev)
+        _lib.check(lib.munit_sn_power_iter(_p(table), n, max_o, max_n, _p(sigma), _p(ws), ws.numel(), _stream()),
+                   "sn_power_iter")
+    return sigma
+
+
+def sn_act_fwd_raw(raw, inv_sigma, bias, act, slope=0.2):
+    lib = _lib.load()
+    raw = nhwc(raw)
+    b, c, h, w = raw.shape
+    with _on(raw):
+        y = empty_nhwc(b, c, h, w, raw)
+        _lib.check(lib.munit_sn_act_fwd(_p(raw), _p(inv_sigma), _p(bias), _p(y), b * h * w, c, ACT[act], c_float(slope),
+                                        _stream()), "sn_act_fwd")
+    return y
+
+
+def sn_act_bwd_raw(dy, y, raw, inv_sigma, act, slope=0.2, db=None, beta=0.0, reduce=True):
+    """-> (draw, db, coef).  reduce False: draw alone (db, coef None).  db given: accumulated in place (beta)."""
+    lib = _lib.load()
+    dy, y = nhwc(dy), nhwc(y)
+    b, c, h, w = y.shape
+    npix = b * h * w
+    with _on(y):
+        draw = empty_nhwc(b, c, h, w, y)
+        coef = ws = None
+        if reduce:
+            raw = nhwc(raw)
+            if db is None:
+                db, beta = torch.empty(c, dtype=torch.float32, device=y.device), 0.0
+            coef = torch.empty(1, dtype=torch.float32, device=y.device)
+            ws = workspace(lib.munit_sn_act_bwd_workspace_bytes(npix, c), y.device)
+        else:
+            db = None
+        _lib.check(lib.munit_sn_act_bwd(_p(dy), _p(y), _p(raw) if reduce else None, _p(inv_sigma), _p(draw), _p(db),
+                                        c_float(beta), _p(coef), npix, c, ACT[act], c_float(slope), _p(ws),
+                                        ws.numel() if ws is not None else 0, _stream()), "sn_act_bwd")
+    return draw, db, coef
+
+
+def sn_grad_fix_raw(coef, u, v, weight_shape, dw=None, beta=0.0, stream=None):
+    """dw = beta * dw - coef * u (x) v in the weight's memory order; a fresh channels_last dw when none is given.  `stream`: as
+    in conv2d_wgrad_raw."""
+    lib = _lib.load()
+    o, i, kh, kw = weight_shape
+    with _on(coef):
+        if dw is None:
+            if stream is not None:
+                raise RuntimeError("munit_amd.sn_grad_fix_raw: give dw when launching on another stream")
+            dw, beta = torch.empty(tuple(weight_shape), device=coef.device, dtype=torch.float32, memory_format=_CL), 0.0
+        st = _stream() if stream is None else c_void_p(stream.cuda_stream)
+        _lib.check(lib.munit_sn_grad_fix(_p(dw), _p(coef), _p(u), _p(v), o, kh, kw, i, c_float(beta), st), "sn_grad_fix")
+    return dw
+
+
+class _SnAct(Function):
+    """y = act(raw / sigma + bias) behind the raw convolution of a spectrally normalised layer.  weight_bar enters only to
+    receive the sigma term of its gradient, -(<G, W> / sigma) u (x) v with the u, v of backward time (the convolution's own
+    backward-weight supplies G): into the flat gradient buffer when the parameter is bound to one -- on the backward-weight
+    side stream, where every write to that buffer is ordered -- and as an ordinary autograd gradient otherwise."""
+
+    @staticmethod
+    @_guarded
+    def forward(ctx, raw, weight_bar, bias, u, v, inv_sigma, act, slope, wbuf, bbuf):
+        _require(raw, "sn_act input")
+        y = sn_act_fwd_raw(raw, inv_sigma, bias, act, slope)
+        if MASK_SINK is not None and act in ("relu", "lrelu"):
+            MASK_SINK.append(y > 0)
+        ctx.cfg = (act, slope, tuple(weight_bar.shape), bias is not None)
+        ctx.state = (u, v, inv_sigma, wbuf, bbuf if bias is not None else None)
+        ctx.save_for_backward(nhwc(raw), y)
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        raw, y = ctx.saved_tensors
+        act, slope, wshape, has_bias = ctx.cfg
+        u, v, inv_sigma, wbuf, bbuf = ctx.state
+        none = (None,) * 7
+        if not (ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])):
+            return (sn_act_bwd_raw(dy, y, None, inv_sigma, act, slope, reduce=False)[0], None, None) + none
+        if wbuf is None:
+            draw, db, coef = sn_act_bwd_raw(dy, y, raw, inv_sigma, act, slope)
+            return (draw, sn_grad_fix_raw(coef, u, v, wshape), db if has_bias else None) + none
+        draw, _, coef = sn_act_bwd_raw(dy, y, raw, inv_sigma, act, slope, db=bbuf, beta=1.0)
+        if SIDE_STREAM_WGRAD:
+            side = _side_stream(dy.device)
+            with _on(dy):
+                _lib.check(_lib.load().munit_stream_wait_stream(c_void_p(side.cuda_stream), _stream()), "stream_wait_stream")
+            sn_grad_fix_raw(coef, u, v, wshape, dw=wbuf, beta=1.0, stream=side)
+            coef.record_stream(side)
+            _SN_PENDING.add(dy.device.index)
+        else:
+            sn_grad_fix_raw(coef, u, v, wshape, dw=wbuf, beta=1.0)
+        return (draw, None, None) + none
+
+
+def sn_act(raw, weight_bar, bias, u, v, inv_sigma, act="none", slope=0.2):
+    """act(raw * inv_sigma + bias): the tail of a spectrally normalised convolution whose raw = conv2d(x, weight_bar).
+    inv_sigma: the layer's one-element slice of sn_power_iter's result."""
+    return _SnAct.apply(raw, weight_bar, bias, u, v, inv_sigma, act, slope, _gbuf(weight_bar), _gbuf(bias))
+
+
+_NORM_ACT ={False: 0, True: 1, None: 0, "none": 0, "relu": 1, "lrelu": 2, "tanh": 3}
 
 
 def _norm_act(relu):

@@ -605,6 +605,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self._check_featda(hyperparameters, self.use_classifier_sr)
         self._check_outda(hyperparameters, self.use_output_classifier_sr)
         self._check_seghead(hyperparameters, self.train_seg)
+        self._check_sn(hyperparameters)
 
         if self.gen_state == 0:
             self.gen_a = AdaINGen(hyperparameters["input_dim_a"], hyperparameters["gen"])
@@ -758,6 +759,19 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             raise NotImplementedError("munit_amd: %s are not implemented for optimizer %r: the reference's update calls "
                                       "step() without extrapolation(), on which its ExtraAdam raises"
                                       % (keys, hp["optimizer"]))
+
+    @staticmethod
+    def _check_sn(hp):
+        """Refusals of dis.norm: sn (spectral normalisation of the discriminators and output classifiers), before anything is
+        built."""
+        if hp.get("dis", {}).get("norm") != "sn":
+            return
+        if hp.get("precision", "f32") != "f32":
+            raise NotImplementedError("munit_amd: dis.norm: sn runs in fp32 only (precision %r)" % hp["precision"])
+        if dp_size() > 1:
+            raise NotImplementedError("munit_amd: dis.norm: sn is not implemented for data-parallel training (world size %d): "
+                                      "every rank would draw and iterate its own weight_u / weight_v, and how they are to be "
+                                      "exchanged is not settled" % dp_size())
 
     @staticmethod
     def _check_seghead(hp, built, update=False):
@@ -1121,6 +1135,7 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         d_params = list(self.dis_a.parameters()) + list(self.dis_b.parameters())
         if fool_out:        # ... and so would the output classifiers' (zeroed by the next update's zero_grad, trainer.py:1271)
             d_params += list(self.output_classifier_sr_a.parameters()) + list(self.output_classifier_sr_b.parameters())
+        d_params = [p for p in d_params if p.requires_grad]     # dis.norm sn: weight_u / weight_v never take a gradient
         for p in d_params:  # D weight gradients made here would be discarded (trainer.py:1145)
             p.requires_grad_(False)
         try:
