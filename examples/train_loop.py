@@ -220,6 +220,8 @@ def main(argv=None, synth_pairs=None):
     from munit_amd import data as D
 
     config = get_config(args.config)
+    if "vgg_model_path" not in config and args.output_path:
+        config["vgg_model_path"] = args.output_path      # scripts/train.py:62: vgg_w > 0 reads <it>/models/vgg16.weight
     torch.manual_seed(1234)                       # identical initial weights on every rank
     trainer = MUNIT_Trainer(config)
     trainer.to(dev)

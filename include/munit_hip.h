@@ -670,6 +670,31 @@ int munit_window3_fwd(const float* x, float* y, int B, int H, int W, int C, int 
  * planar [B][3][H][W] or 1 interleaved [B][H][W][3], dense; y: [B][299][299][3]. */
 int munit_inception_input(const float* x, int layout, int B, int H, int W, float* y, munit_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Domain-invariant perceptual loss (vgg_w; scripts/trainer.py:618-636; csrc/vgg.hip).  fp32, NHWC,
+ * asynchronous on `stream`; every argument check returns MUNIT_ERR_ARG before any launch.  The frozen VGG16 itself runs on
+ * the convolution entry points and the 2x2 max-pool above.
+ *
+ * vgg_preprocess (utils.py:1051-1063): x, y are npix pixels of 3 channels in different buffers; y[p][c] =
+ * (x[p][2 - c] + 1) * 255 * 0.5 - mean_c with mean = (103.939, 116.779, 123.680) for the B, G, R planes of y -- the
+ * reference's operations in its order, hence torch's result bit for bit.  bwd: dx[p][c] = 127.5 * dy[p][2 - c]. */
+int munit_vgg_input_fwd(const float* x, float* y, size_t npix, munit_stream_t stream);
+int munit_vgg_input_bwd(const float* dy, float* dx, size_t npix, munit_stream_t stream);
+/* out[0] = mean over all B * HW * C elements of (IN(f) - IN(t))^2, IN = instance norm without affine: per (b, c) over the HW
+ * pixels, biased variance, eps 1e-5 inside the square root.  f, t: [B][HW][C], C % 4 == 0, B <= 65535; they may be the same
+ * buffer.  stats [2][B][C][2] floats receives (mean, 1 / sqrt(var + eps)) of f, then of t, for the backward.  Statistics and the
+ * sum are taken in fp64 and reduced in a fixed order in two stages (no atomics): two calls on the same data are bitwise equal,
+ * and f == t gives exactly 0.  ws: munit_in_mse_workspace_bytes; a shorter one is refused with MUNIT_ERR_WORKSPACE before
+ * anything is written.
+ * bwd, to f only: with n_f, n_t the normalised maps, N = B * HW * C and g = 2 gout[0] (n_f - n_t) / N,
+ *   df = (g - mean_hw(g) - n_f * mean_hw(g * n_f)) / sqrt(var_f + eps),
+ * from the statistics the forward saved; df [B][HW][C] is written in full and must not alias f or t. */
+size_t munit_in_mse_workspace_bytes(int B, int C);
+int munit_in_mse_fwd(const float* f, const float* t, int B, int HW, int C, float* out, float* stats, void* ws, size_t ws_bytes,
+                     munit_stream_t stream);
+int munit_in_mse_bwd(const float* f, const float* t, const float* stats, int B, int HW, int C, const float* gout, float* df,
+                     munit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,11 @@ SIGNATURES = {
     "munit_conv2d_rect_fwd": (c_int, [POINTER(RectDesc), _P, _P, _P, _P, c_int, _P]),
     "munit_window3_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "munit_inception_input": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "munit_vgg_input_fwd": (c_int, [_P, _P, c_size_t, _P]),
+    "munit_vgg_input_bwd": (c_int, [_P, _P, c_size_t, _P]),
+    "munit_in_mse_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "munit_in_mse_fwd": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "munit_in_mse_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
 }
 
 _lib = None

@@ -26,7 +26,7 @@ _ws_cache = {}
 # bench.py sets this to a list to time every convolution pass (forward, backward-data, backward-weight) with HIP events on
 # the launch stream: entries are (pass 0/1/2, the layer's _Plan, start event, end event).
 PROFILE = None
-# The four kink sinks of the parity harness.  Each is None (recording off: one `is not None` test per op) or a list that the
+# The five kink sinks of the parity harness.  Each is None (recording off: one `is not None` test per op) or a list that the
 # ops append to in call order, so that the fp64 oracle can take the same branch at every kink.  `kinks` below is the only code
 # that assigns to them; everything else only reads them.
 # MASK_SINK: the sign pattern (output > 0) behind every ReLU / LeakyReLU of a forward pass
@@ -39,6 +39,8 @@ SEG_SINK = None
 # DANN_SINK: the feature classifiers of adv_lambda / dfeat_lambda (networks.domainClassifier): the max-pool winners, the
 # ReLU sign patterns behind batch_norm and the block tails
 DANN_SINK = None
+# VGG_SINK: the frozen VGG16 of the perceptual loss (munit_amd/vgg.py): its ReLU sign patterns and max-pool winners
+VGG_SINK = None
 # Data-parallel batch norm (adaptation.data_parallel: 1): the world size of the process group whose ranks share the batch
 # statistics of training-mode batch_norm, 0 = every process normalises its own batch.  Set by the trainer around the feature
 # classifiers' forward passes (bn_world); a backward pass takes the value its forward ran with.
@@ -58,23 +60,24 @@ def _count(pl, which):
 @contextlib.contextmanager
 def kinks(**channels):
     """Record the kinks of the ops run inside the block: `with kinks(mask=True, l1=True) as k:` -> k.mask, k.l1.
-    Keywords mask / l1 / seg / dann name MASK_SINK / L1_SINK / SEG_SINK / DANN_SINK.  True records into a fresh list, a list
-    records into that list, None switches the channel off; a channel that is not named keeps what it has.  The object
-    yielded carries the four active lists (or None).  On exit, also when the block raises, every channel is back at its
+    Keywords mask / l1 / seg / dann / vgg name MASK_SINK / L1_SINK / SEG_SINK / DANN_SINK / VGG_SINK.  True records into a
+    fresh list, a list records into that list, None switches the channel off; a channel that is not named keeps what it has.
+    The object yielded carries the five active lists (or None).  On exit, also when the block raises, every channel is back at its
     value on entry, so blocks nest."""
-    global MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK
-    saved = {"mask": MASK_SINK, "l1": L1_SINK, "seg": SEG_SINK, "dann": DANN_SINK}
+    global MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK, VGG_SINK
+    saved = {"mask": MASK_SINK, "l1": L1_SINK, "seg": SEG_SINK, "dann": DANN_SINK, "vgg": VGG_SINK}
     for name, v in channels.items():
         if name not in saved:
-            raise TypeError("munit_amd: kinks() has no channel %r (mask, l1, seg, dann)" % name)
+            raise TypeError("munit_amd: kinks() has no channel %r (mask, l1, seg, dann, vgg)" % name)
         if v is not True and v is not None and not isinstance(v, list):
             raise TypeError("munit_amd: kinks(%s=...) takes True, a list or None, got %r" % (name, v))
     now = dict(saved, **{name: [] if v is True else v for name, v in channels.items()})
     try:
-        MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK = now["mask"], now["l1"], now["seg"], now["dann"]
+        MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK, VGG_SINK = now["mask"], now["l1"], now["seg"], now["dann"], now["vgg"]
         yield types.SimpleNamespace(**now)
     finally:
-        MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK = saved["mask"], saved["l1"], saved["seg"], saved["dann"]
+        MASK_SINK, L1_SINK, SEG_SINK, DANN_SINK, VGG_SINK = (saved["mask"], saved["l1"], saved["seg"], saved["dann"],
+                                                             saved["vgg"])
 
 
 # Arithmetic of the conv / linear contractions: "f32" (exact fp32 MFMA, the reference's arithmetic) or "bf16"
@@ -318,7 +321,8 @@ def prepare_weights_batch(table, n):
 def conv2d_fwd_raw(x, weight, bias, stride, pad, pad_type, upsample, act, slope=0.2, owner=None, out_dtype=None, seg=False):
     """out_dtype: torch.float32 / torch.bfloat16 of y; default = x's dtype when Cout is a multiple of 64, else fp32
     (3-channel images, small heads).  A bf16 x runs the bf16-storage kernels (weights stay fp32 parameters).
-    seg: a layer of the segmentation network (its ReLU signs go to SEG_SINK, not MASK_SINK)."""
+    seg: a layer of a frozen network: True or "seg" (the segmentation network) sends its ReLU signs to SEG_SINK, "vgg" (the
+    VGG16 of the perceptual loss) to VGG_SINK, instead of MASK_SINK."""
     lib = _lib.load()
     x, weight = nhwc(x), nhwc(weight)
     _same_device(x, weight, bias)
@@ -342,7 +346,7 @@ def conv2d_fwd_raw(x, weight, bias, stride, pad, pad_type, upsample, act, slope=
             e1.record()
             PROFILE.append((0, pl, e0, e1))
         _count(pl, 0)
-    sink = SEG_SINK if seg else MASK_SINK
+    sink = MASK_SINK if not seg else VGG_SINK if seg == "vgg" else SEG_SINK
     if sink is not None and act in ("relu", "lrelu"):
         sink.append(y > 0)
     return y
@@ -867,7 +871,7 @@ def layer_norm(x, gamma, beta, relu=False, eps=1e-5):
 # The six pools (csrc/pointwise.hip, seg.hip, dann.hip) differ in data only.  fwd / bwd: the library symbols; tag: what their
 # failures are reported as; noun: what _require calls the input; extent(h, w): the output map's (ho, wo), None where the
 # output has the input's shape; form: "map" (an NHWC map), "bc11" ((B, C, 1, 1)) or "bc" (plain (B, C)); flat: the library
-# takes (B, H*W, C), not (B, H, W, C); sink: None, or the NAME of the kinks channel ("seg" / "dann") that records the pool's
+# takes (B, H*W, C), not (B, H, W, C); sink: None, or the NAME of the kinks channel ("seg" / "dann" / "vgg") that records the pool's
 # uint8 winners (B, Ho, Wo, C) -- the name, because `kinks` rebinds the sink globals while the ops run; check: an optional
 # precondition on the NHWC input's shape.
 _Pool = collections.namedtuple("_Pool", "fwd bwd tag noun extent form flat sink check")
@@ -919,7 +923,8 @@ class _Pooling(Function):
         winners = () if idx is None else (_p(idx),)
         dims = (b, h * w, c) if pool.flat else (b, h, w, c)
         _lib.check(getattr(lib, pool.fwd)(_p(x), _p(y), *winners, *dims, _stream()), pool.tag + "_fwd")
-        sink = SEG_SINK if pool.sink == "seg" else DANN_SINK if pool.sink == "dann" else None    # the globals, as they are now
+        # the globals, as they are now
+        sink = {"seg": SEG_SINK, "dann": DANN_SINK, "vgg": VGG_SINK}[pool.sink] if pool.sink else None
         if sink is not None:
             sink.append(idx)
         ctx.pool, ctx.shape, ctx.dims = pool, x.shape, dims
@@ -960,9 +965,16 @@ def avgpool7(x):
     return _Pooling.apply(x, _POOLS["avgpool7"])
 
 
-def maxpool2(x):
-    """nn.MaxPool2d(2) (scripts/utils.py:1374): floor output size, ties to the first maximal element in window order."""
-    return _Pooling.apply(x, _POOLS["maxpool2"])
+def maxpool2(x, sink="dann"):
+    """nn.MaxPool2d(2) (scripts/utils.py:1374; F.max_pool2d(h, 2, 2) of networks.Vgg16): floor output size, ties to the first
+    maximal element in window order.  sink: the kinks channel that records the winners -- "dann" (the feature classifiers,
+    the table's entry) or "vgg" (the VGG16 of the perceptual loss: the same kernels, another channel)."""
+    pool = _POOLS["maxpool2"]
+    if sink != pool.sink:
+        if sink != "vgg":
+            raise ValueError("munit_amd.maxpool2: sink must be 'dann' or 'vgg', got %r" % (sink,))
+        pool = pool._replace(sink=sink)
+    return _Pooling.apply(x, pool)
 
 
 def avgpool16(x):
@@ -1309,18 +1321,144 @@ def seg_input(*xs):
     return _SegInput.apply(*xs)
 
 
+# ------------------------------------------------------------------------------------------
+# perceptual loss (vgg_w; munit_amd/vgg.py; include/munit_hip.h, vgg.hip)
+# ------------------------------------------------------------------------------------------
+class _VggInput(Function):
+    """vgg_preprocess (utils.py:1051-1063) of several image tensors into ONE batch, as _SegInput gathers the segmentation
+    network's: RGB -> BGR, [-1, 1] -> [0, 255], minus the Caffe means.  One launch per input, written at its offset."""
+    @staticmethod
+    @_guarded
+    def forward(ctx, *xs):
+        lib = _lib.load()
+        xs = [nhwc(x) for x in xs]
+        for x in xs:
+            _require(x, "VGG input")
+            if x.dim() != 4 or x.shape[1] != 3 or x.shape[2:] != xs[0].shape[2:]:
+                raise RuntimeError("munit_amd.vgg_input: images must be (B, 3, H, W) of one size, got %s" % (tuple(x.shape),))
+        _same_device(*xs)
+        _, _, h, w = xs[0].shape
+        y = empty_nhwc(sum(x.shape[0] for x in xs), 3, h, w, xs[0])
+        off = 0
+        for x in xs:
+            n = x.shape[0] * h * w
+            _lib.check(lib.munit_vgg_input_fwd(_p(x), c_void_p(y.data_ptr() + off * 12), n, _stream()), "vgg_input_fwd")
+            off += n
+        ctx.sizes = [x.shape for x in xs]
+        return y
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, dy):
+        lib = _lib.load()
+        dy = nhwc(dy)
+        out, off = [], 0
+        for i, shp in enumerate(ctx.sizes):
+            n = shp[0] * shp[2] * shp[3]
+            if ctx.needs_input_grad[i]:
+                dx = empty_nhwc(shp[0], 3, shp[2], shp[3], dy)
+                _lib.check(lib.munit_vgg_input_bwd(c_void_p(dy.data_ptr() + off * 12), _p(dx), n, _stream()),
+                           "vgg_input_bwd")
+                out.append(dx)
+            else:
+                out.append(None)
+            off += n
+        return tuple(out)
+
+
+def vgg_input(*xs):
+    return _VggInput.apply(*xs)
+
+
+class _InMse(Function):
+    """mean((IN(feat) - IN(target)) ** 2), IN = nn.InstanceNorm2d(C, affine=False) (trainer.py:89, 634-636).  The gradient
+    goes to feat only: the target is the features of an original image."""
+    @staticmethod
+    @_guarded
+    def forward(ctx, feat, target):
+        lib = _lib.load()
+        _require(feat, "in_mse features")
+        _require(target, "in_mse target")
+        if feat.dim() != 4 or feat.shape != target.shape:
+            raise RuntimeError("munit_amd.in_mse: two (B, C, h, w) maps of one shape expected, got %s and %s"
+                               % (tuple(feat.shape), tuple(target.shape)))
+        _same_device(feat, target)
+        f, t = nhwc(feat), nhwc(target)
+        b, c, h, w = f.shape
+        if c % 4:
+            raise RuntimeError("munit_amd.in_mse: C %% 4 == 0 needed, got %s" % (tuple(f.shape),))
+        out = torch.empty((), device=f.device, dtype=torch.float32)
+        stats = torch.empty((2, b, c, 2), device=f.device, dtype=torch.float32)
+        ws = workspace(lib.munit_in_mse_workspace_bytes(b, c), f.device)
+        _lib.check(lib.munit_in_mse_fwd(_p(f), _p(t), b, h * w, c, _p(out), _p(stats), _p(ws), ws.numel(), _stream()),
+                   "in_mse_fwd")
+        ctx.save_for_backward(f, t, stats)
+        return out
+
+    @staticmethod
+    @_guarded
+    def backward(ctx, gout):
+        lib = _lib.load()
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError("munit_amd.in_mse: the target takes no gradient (detach it, or run its network under no_grad)")
+        f, t, stats = ctx.saved_tensors
+        b, c, h, w = f.shape
+        gout = gout.contiguous()
+        df = torch.empty_like(f)
+        _lib.check(lib.munit_in_mse_bwd(_p(f), _p(t), _p(stats), b, h * w, c, _p(gout), _p(df), _stream()), "in_mse_bwd")
+        return df, None
+
+
+def in_mse(feat, target):
+    """compute_vgg_loss's last line (trainer.py:634-636) on the two feature maps."""
+    return _InMse.apply(feat, target)
+
+
+class _SplitBatch(Function):
+    """The parts x[0:n0], x[n0:n0 + n1], ... of a batch that several inputs were gathered into (views); the backward joins the
+    parts' gradients into one NHWC batch (layout plumbing: one copy, no zero-filled full-size gradient per part)."""
+    @staticmethod
+    def forward(ctx, x, *sizes):
+        if sum(sizes) != x.shape[0]:
+            raise RuntimeError("munit_amd.split_batch: parts %s do not add up to the batch of %d" % (sizes, x.shape[0]))
+        ctx.shape = x.shape
+        out, off = [], 0
+        for n in sizes:
+            out.append(x[off:off + n])
+            off += n
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if any(g is None for g in grads):
+            raise RuntimeError("munit_amd.split_batch: every part must be used (a part came back without a gradient)")
+        b, c, h, w = ctx.shape
+        dx, off = empty_nhwc(b, c, h, w, grads[0]), 0
+        for g in grads:
+            dx[off:off + g.shape[0]].copy_(g)
+            off += g.shape[0]
+        return (dx,) + (None,) * len(grads)
+
+
+def split_batch(x, sizes):
+    return _SplitBatch.apply(x, *sizes)
+
+
 class _FrozenConv(Function):
     """Convolution (+ bias + optional ReLU) with a frozen weight.  w_dgrad: the weight backward-data multiplies by -- the
     weight itself, or for the odd-kernel stride-2 layers its zero-extension to an even kernel (same output extent on
     even inputs, same result; the phase form of backward-data needs KH % stride == 0).  link_in: dx += the gradient parked
     there (the block's skip path); link_out: park dx there instead of returning it (the downsample branch, whose gradient
-    the block's first convolution adds)."""
+    the block's first convolution adds).  An input that needs no gradient (the network's first layer on images under
+    no_grad, or a target pass) costs no backward-data: autograd does not run this node."""
     @staticmethod
     @_guarded
-    def forward(ctx, x, weight, bias, w_dgrad, stride, pad, act, link_in, link_out):
+    def forward(ctx, x, weight, bias, w_dgrad, stride, pad, act, link_in, link_out, sink="seg"):
         _require(x, "conv input")
+        if sink not in ("seg", "vgg"):
+            raise ValueError("munit_amd.frozen_conv: sink must be 'seg' or 'vgg', got %r" % (sink,))
         x = nhwc(x)
-        y = conv2d_fwd_raw(x, weight, bias, stride, pad, "zero", False, act, seg=True)
+        y = conv2d_fwd_raw(x, weight, bias, stride, pad, "zero", False, act, seg=sink)
         ctx.cfg = (stride, pad, act, x.shape)
         ctx.w_dgrad = w_dgrad
         ctx.links = (link_in, link_out)
@@ -1346,11 +1484,12 @@ class _FrozenConv(Function):
         if link_out is not None:
             link_out.park(dx)
             dx = None
-        return dx, None, None, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None, None, None
 
 
-def frozen_conv(x, weight, bias, w_dgrad, stride, pad, act="none", link_in=None, link_out=None):
-    return _FrozenConv.apply(x, weight, bias, w_dgrad, stride, pad, act, link_in, link_out)
+def frozen_conv(x, weight, bias, w_dgrad, stride, pad, act="none", link_in=None, link_out=None, sink="seg"):
+    """sink: the kinks channel of the layer's ReLU signs -- "seg" (the segmentation network) or "vgg"."""
+    return _FrozenConv.apply(x, weight, bias, w_dgrad, stride, pad, act, link_in, link_out, sink)
 
 
 class _AddRelu(Function):

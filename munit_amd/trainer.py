@@ -56,9 +56,16 @@ the plain step().  The encoders run without a tape there: the reference back-pro
 that gradient before any use.  fp32, Adam and one process only; update_learning_rate does not step scheduler_seg and
 save / resume do not carry the head, as in the reference.
 
-With that every live branch of scripts/train.py's loop runs here.  The two weights still refused, vgg_w and domain_adv_w,
-cannot run in the reference either (load_vgg16 raises unconditionally; the a/b domain classifier's loss builds a
-4-element target for any batch and save / resume read an attribute that does not exist).
+The domain-invariant perceptual loss (vgg_w > 0 with a vgg_model_path, trainer.py:493-502 and 618-636): the frozen VGG16
+of munit_amd/vgg.py, read from <vgg_model_path>/models/vgg16.weight -- the cache file of the reference's load_vgg16, whose
+download-and-convert step cannot run any more; the user supplies the file.  gen_update runs the two translations through
+the network as one batch of 2B with gradient and the two originals as one batch of 2B without, and takes
+mean((IN(f) - IN(t))^2) of relu5_3 per pair in one kernel pair (ops.in_mse); self.instancenorm stays the parameter-free
+attribute the reference has, and the network is kept out of state_dict().  fp32 only, crops of at least 16x16.
+
+With that every live branch of scripts/train.py's loop runs here.  The one weight still refused, domain_adv_w, cannot run
+in the reference either (the a/b domain classifier's loss builds a 4-element target for any batch and save / resume read
+an attribute that does not exist); vgg_w without a vgg_model_path is refused because the reference's load_vgg16 is dead.
 """
 import os
 import warnings
@@ -72,6 +79,7 @@ from .networks import (AdaINGen, AdaINGen_double, ContentEncoder, InstanceNorm2d
                        domainClassifier)
 from .segmentation import SegmentationHead, colorize, load_segmentation_head, seg_head_loss, seg_loss
 from .utils import get_model_list, get_scheduler, load_segmentation_model, normalize_config, weights_init
+from .vgg import check_hw as check_vgg_hw, load_vgg16, vgg_loss
 
 
 class StepGate:
@@ -606,6 +614,9 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self._check_outda(hyperparameters, self.use_output_classifier_sr)
         self._check_seghead(hyperparameters, self.train_seg)
         self._check_sn(hyperparameters)
+        self.use_vgg = hyperparameters.get("vgg_w", 0) > 0
+        if self.use_vgg:
+            self._check_vgg(hyperparameters)
 
         if self.gen_state == 0:
             self.gen_a = AdaINGen(hyperparameters["input_dim_a"], hyperparameters["gen"])
@@ -647,6 +658,11 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
             self._check_semantic(hyperparameters)
             self.segmentation_model = load_segmentation_model(hyperparameters["semantic_ckpt_path"], 19)
 
+        # domain-invariant perceptual loss (trainer.py:129-134): the VGG16 of <vgg_model_path>/models/vgg16.weight, frozen, in
+        # eval mode.  A plain attribute, not a sub-module: state_dict() is the same with and without the loss, and the
+        # network makes its own device copy of the weights at first use (Vgg16.weights), so .to() need not move it.
+        self.__dict__["vgg"] = load_vgg16(hyperparameters["vgg_model_path"] + "/models") if self.use_vgg else None
+
         # feature classifiers of the simulated / real adaptation (trainer.py:161-179): one optimizer over both, a scheduler
         # that update_learning_rate never steps, nothing of them in save / resume
         if self.use_classifier_sr:
@@ -683,8 +699,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         """construct False (gen_update): the both-weights rule of the output classifiers is a rule of construction -- a
         trainer that owns them may be handed output_adv_lambda 0 for a step."""
         bad = []
-        if hp.get("vgg_w", 0) > 0:
-            bad.append("vgg_w")
+        if hp.get("vgg_w", 0) > 0 and not hp.get("vgg_model_path"):
+            bad.append("vgg_w (without a vgg_model_path that holds models/vgg16.weight)")
         if hp.get("semantic_w", 0) > 0 and not hp.get("semantic_ckpt_path"):
             bad.append("semantic_w (without a semantic_ckpt_path)")
         if hp.get("domain_adv_w", 0) > 0:
@@ -701,10 +717,22 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                        "nothing reads: set both)")
         if bad:
             raise NotImplementedError(
-                "munit_amd: set these weights to 0: " + ", ".join(bad) + ".  vgg_w and domain_adv_w cannot run in the "
-                "reference either (load_vgg16 raises unconditionally; the a/b domain classifier's loss builds a 4-element "
-                "target for any batch size); semantic_w and adaptation.sem_seg_lambda need the user's Resnet34_8s "
+                "munit_amd: set these weights to 0: " + ", ".join(bad) + ".  domain_adv_w cannot run in the reference "
+                "either (the a/b domain classifier's loss builds a 4-element target for any batch size), and the reference's "
+                "load_vgg16 raises unconditionally: vgg_w needs the file it would have cached, "
+                "<vgg_model_path>/models/vgg16.weight; semantic_w and adaptation.sem_seg_lambda need the user's Resnet34_8s "
                 "checkpoint (semantic_ckpt_path)")
+
+    @staticmethod
+    def _check_vgg(hp, built=True):
+        """Refusals of vgg_w > 0, before any device work.  built: whether this trainer was constructed with the weight and
+        a vgg_model_path (it then owns the network)."""
+        if not built:
+            raise ValueError("munit_amd: vgg_w > 0 needs a trainer constructed with vgg_w > 0 and a vgg_model_path (the VGG16 "
+                             "is loaded under that weight)")
+        if hp.get("precision", "f32") != "f32":
+            raise NotImplementedError("munit_amd: vgg_w > 0 runs in fp32 only (precision %r)" % hp["precision"])
+        check_vgg_hw(hp["crop_image_height"], hp["crop_image_width"])
 
     @staticmethod
     def _check_featda(hp, built):
@@ -1117,6 +1145,9 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         if gts is not None and x_a.device.type != "cuda":
             raise NotImplementedError("munit_amd: semantic_gt_a / semantic_gt_b run on the device only (there is no host "
                                       "path for any loss); move the trainer and the images to a HIP device")
+        vgg_on = hp.get("vgg_w", 0) > 0
+        if vgg_on:     # ahead of _check_aux: a trainer built without the network is the caller's error whatever else hp lacks
+            self._check_vgg(dict(hp, crop_image_height=x_a.shape[2], crop_image_width=x_a.shape[3]), self.vgg is not None)
         self._check_aux(normalize_config(hp), construct=False)
         self._check_featda(hp, self.use_classifier_sr)
         self._check_outda(hp, self.use_output_classifier_sr)
@@ -1227,8 +1258,12 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
                     self.loss_gen_cycrecon_x_b, self.loss_gen_adv_a, self.loss_gen_adv_b, sr_a, sr_b, osr_a, osr_b)
             self.loss_classifier_sr = ops.scalar_sum([sr_a, sr_b]) if fool_sr else 0
             self.loss_output_classifier_sr = ops.scalar_sum([osr_a, osr_b]) if fool_out else 0
-            if pair_term or self.semantic_w:
+            if pair_term or self.semantic_w or vgg_on:
                 br.join(x_ab, x_ba)            # both translations on the caller's stream
+            self.loss_gen_vgg_a = self.loss_gen_vgg_b = 0
+            if vgg_on:
+                # trainer.py:493-502: vgg(x_ba, x_b), vgg(x_ab, x_a); the network runs twice on 2B images, not four times on B
+                self.loss_gen_vgg_a, self.loss_gen_vgg_b = vgg_loss(self.vgg, [x_ba, x_ab], [x_b, x_a])
             if pair_term:
                 # after the cycle terms: its two L1 sign patterns (x_ab > x_b, x_ba > x_a) are the last of the step
                 self.loss_gen_recon_synth = ops.pair_l1(x_a, x_b, x_ab, x_ba)
@@ -1239,7 +1274,6 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         finally:
             for p in d_params:
                 p.requires_grad_(True)
-        self.loss_gen_vgg_a = self.loss_gen_vgg_b = 0
         self.domain_adv_loss = 0
 
         pairs = [(hp["gan_w"], self.loss_gen_adv_a), (hp["gan_w"], self.loss_gen_adv_b),
@@ -1249,6 +1283,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         if cyc:
             pairs += [(hp["recon_x_cyc_w"], self.loss_gen_cycrecon_x_a),
                       (hp["recon_x_cyc_w"], self.loss_gen_cycrecon_x_b)]
+        if vgg_on:
+            pairs += [(hp["vgg_w"], self.loss_gen_vgg_a), (hp["vgg_w"], self.loss_gen_vgg_b)]
         if self.semantic_w:
             pairs.append((hp["semantic_w"], self.loss_sem_seg))
         if pair_term:
@@ -1284,7 +1320,8 @@ class MUNIT_Trainer(_ApplyRefreshesImages, nn.Module):
         self._log(comet_exp, ("loss_gen_adv_a", "loss_gen_adv_b", "loss_gen_recon_x_a", "loss_gen_recon_s_a",
                               "loss_gen_recon_c_a", "loss_gen_recon_x_b", "loss_gen_recon_s_b",
                               "loss_gen_recon_c_b", "loss_gen_cycrecon_x_a", "loss_gen_cycrecon_x_b",
-                              "loss_gen_total") + (("loss_sem_seg",) if self.semantic_w else ())
+                              "loss_gen_total") + (("loss_gen_vgg_a", "loss_gen_vgg_b") if vgg_on else ())
+                  + (("loss_sem_seg",) if self.semantic_w else ())
                   + (("loss_gen_recon_synth",) if synth else ()) + (("loss_classifier_sr",) if fool_sr else ()))
         if fool_out and comet_exp is not None and self.iterations % 100 == 0:     # trainer.py:612-616
             comet_exp.log_metric("loss_output_classifier_adv_sr", self.loss_output_classifier_sr.cpu().detach())
